@@ -3,16 +3,22 @@
 Gramian, factorisation, whitening, row solve and -- on more than one GPU -- the Gramian all-reduce and the exchange of
 the freshly solved block) over a synthetic confidence matrix that is already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3] [--also cfg2|none] [--scaling strong|weak] [--zipf A]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3] [--scaling strong|weak] [--zipf A]
+                    [--dump-outputs DIR] [--full [--also cfg2|none] [--no-cpu-baseline]]
 
 Default workload = BASELINE.json configs[2] (the configuration the north-star target is quoted on): k = 128 with
-user / item biases, 10 M x 1 M, ~100 M stored entries.  configs[1] (cfg2: k = 64, 1 M x 100 K, 20 M entries) is timed
-in the same process afterwards and reported under "also".  For N > 1 the driver launches one rank per GPU through
+user / item biases, 10 M x 1 M, ~100 M stored entries.  For N > 1 the driver launches one rank per GPU through
 torch.distributed.run (RCCL); the default there is STRONG scaling -- BASELINE.json configs[3]: the same 10 M x 1 M
-matrix at k = 128, users and items dealt over the N GPUs -- with the bias-free variant (cfg4) under "also".
-Rank 0 prints ONE JSON line.
+matrix at k = 128, users and items dealt over the N GPUs.  Rank 0 prints ONE JSON line.
 
-Roofline bookkeeping.  Every kernel launch is timed with HIP events on its own stream
+A plain run sets the workload up, runs W warm-up and K timed steps and prints the line: "value" = row updates per second
+and "ms_per_step" = milliseconds per ALS iteration over the K timed steps, with no per-launch events recorded (a --full
+run records them, and its ms_per_step includes their cost: the two are not the same quantity).  --dump-outputs DIR then
+writes the factor matrices of the last timed step (dump_outputs).  Everything else needs --full: the per-kernel table and rooflines below,
+the eval pass, the CPU baseline and host boundary, and further workloads under "also" -- on one GPU cfg2 (configs[1]:
+k = 64, 1 M x 100 K, 20 M entries), cfg3 + Zipf, cfg5s, cfg5s + Zipf and the float64 path; on several the bias-free cfg4.
+
+Roofline bookkeeping (--full).  Every kernel launch is timed with HIP events on its own stream
 (wmf_profile_* in the C ABI), keyed by the symbol rocprofv3 prints and by the half step it ran in.  Algorithmic bytes
 of a row kernel = sum over ITS rows of (4f + 8) x entries + (4f + 4): what the reference's Y[idx] gather, the CSR
 entry and the written row amount to, whatever the kernel really moves.  "traffic" is NOT measured in this run: it is
@@ -58,7 +64,21 @@ def parse():
                          "the all-gather of a chunk overlaps the solve of the next)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-users", type=int, default=0, help="user rows in the CPU-baseline sample (0 = auto)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: per-kernel table and rooflines, eval pass, CPU baseline, host "
+                         "boundary, the workloads under 'also' and the float64 path (a plain run sets up, warms up, times the "
+                         "steps of the main workload and prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the user and item factors of the last step to DIR/<side>.npy (float32; "
+                         "a fixed seeded sample of rows where a side is large, its row ids in DIR/<side>_rows.npy)")
+    args = ap.parse_args()
+    # options that only select or size what --full measures; "--also none" and --no-cpu-baseline ask for nothing a plain
+    # run does, so they are accepted without it
+    if not args.full and args.also not in ("auto", "none"):
+        ap.error(f"--also {args.also}: the workloads under 'also' are measured by --full runs only")
+    if not args.full and args.cpu_users:
+        ap.error("--cpu-users: the CPU baseline is measured by --full runs only")
+    return args
 
 
 def cpu_share():
@@ -234,7 +254,34 @@ def traffic_of(table, name, side, both_sides):
     return k.get("hbm_bytes_mean_corrected")
 
 
-def run_workload(cfg_name, args, world, rank, dev, lib, scaling, with_cpu, zipf=None):
+DUMP_BYTES = 56_000_000     # --dump-outputs: at most this many bytes in all, half per side (row ids included)
+
+
+def dump_outputs(eng, out_dir, rank):
+    """--dump-outputs: what the timed path hands a caller after its last step, the user and item factor matrices [n, f]
+    (reference layout, id order), as DIR/users.npy and DIR/items.npy in float32.  A side larger than its half of DUMP_BYTES is
+    written as a fixed seeded sample of rows, the same for every run with the same arguments; DIR/<side>_rows.npy holds
+    the ids of the written rows (float64).  Every rank takes part (the need-list gather is collective); rank 0 writes.
+    A side in need-list mode (several GPUs) goes through get_factors, which copies the whole matrix to the host once."""
+    arrays = {}
+    for i, side in enumerate(SIDES):
+        n, f = eng.n[side], eng.f
+        cap = (DUMP_BYTES // 2) // (4 * f + 8)
+        ids = np.arange(n) if n <= cap else np.sort(np.random.default_rng(1993 + i).choice(n, cap, replace=False))
+        if eng.sparse[side]:
+            rows = eng.get_factors(side)[ids]
+        else:                                        # get_factors restricted to the sampled ids: no full copy to the host
+            eng._ensure_gathered(side)
+            pos = eng.positions(side, torch.as_tensor(ids, dtype=torch.int64, device=eng.device))
+            rows = eng.X[side][pos][:, : f].cpu().numpy()
+        arrays[side], arrays[side + "_rows"] = np.ascontiguousarray(rows, dtype=np.float32), ids.astype(np.float64)
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def run_workload(cfg_name, args, world, rank, dev, lib, scaling, with_cpu, zipf=None, full=True, dump_dir=None):
     zipf = args.zipf if zipf is None else float(zipf)
     n_users_1, n_items, dbar, k, bias = synth.CONFIGS[cfg_name]
     n_users = n_users_1 * world if scaling == "weak" else n_users_1
@@ -290,10 +337,11 @@ def run_workload(cfg_name, args, world, rank, dev, lib, scaling, with_cpu, zipf=
         step()
     barrier()
     eng.check_numerics()
-    for s_ in SIDES:
-        eng.iter_stats(s_)                          # (clears the counters of the warm-up iterations)
-    lib.wmf_profile_reset()
-    lib.wmf_profile_enable(1)
+    if full:                                        # per-kernel HIP events and path counters: --full only
+        for s_ in SIDES:
+            eng.iter_stats(s_)                      # (clears the counters of the warm-up iterations)
+        lib.wmf_profile_reset()
+        lib.wmf_profile_enable(1)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -302,6 +350,30 @@ def run_workload(cfg_name, args, world, rank, dev, lib, scaling, with_cpu, zipf=
     elapsed = time.perf_counter() - t0
     lib.wmf_profile_enable(0)
     eng.check_numerics()
+    if dump_dir:
+        dump_outputs(eng, dump_dir, rank)
+    config = {"workload": f"{cfg_name}: WMF k={k}{'+bias' if bias else ''}, {n_users}x{n_items} CSR, "
+                          f"{nnz} nnz, alpha-log confidence, gamma={gamma}, zipf_a={zipf}",
+              "n_users": n_users, "n_items": n_items, "nnz": nnz, "k": k, "bias": bias,
+              "exchange": {s_: (("reduce" if eng.reduce[s_] else "need-list" if eng.sparse[s_] else "all-gather")
+                                + ("+pipelined" if eng.pipe[s_] else "")) + f" x{len(eng.chunk_bounds[s_])}"
+                           for s_ in SIDES} if world > 1 or eng.exchange else None,
+              "sharding": f"users+items dealt by cost (nnz f^2 + f^3) over {world} GPU(s), every rank loads 1/{world} of the user "
+                          f"rows; exchange users: "
+                          f"{'reduce-scatter of partial systems' if eng.reduce['users'] else ('need-list all-to-all (%.0f %% of the rows per rank)' % (100 * eng.need['users']['needed_fraction']) if eng.sparse['users'] else 'all-gather')} in "
+                          f"{len(eng.chunk_bounds['users'])} chunk(s), items: "
+                          f"{'reduce-scatter of partial systems' if eng.reduce['items'] else 'all-gather'} in "
+                          f"{len(eng.chunk_bounds['items'])} chunk(s); accumulation pipelined over arriving chunks: "
+                          f"{[s_ for s_ in SIDES if eng.pipe[s_]] or 'no'}"}
+    if not full:
+        if world > 1:
+            tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+            torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
+            elapsed = float(tmax.item())
+        del eng, indptr, indices, counts, values
+        torch.cuda.empty_cache()
+        return {"value": (n_users + n_items) * args.steps / elapsed, "ms_per_step": elapsed / args.steps * 1e3,
+                "config": config, "nnz_per_s": 2.0 * nnz * args.steps / elapsed, "setup_s": t_setup}
     table = _lib.profile_table(lib)
     lib.wmf_profile_reset()
     # what the matrix-free iteration kernel did with its candidates in the timed iterations (data dependent: see csrc/wmf_iter.hip)
@@ -402,19 +474,7 @@ def run_workload(cfg_name, args, world, rank, dev, lib, scaling, with_cpu, zipf=
         per_rank_nnz = [int(t.item()) for t in gathered]
     out = {
         "value": (n_users + n_items) * args.steps / elapsed, "ms_per_step": elapsed / args.steps * 1e3,
-        "config": {"workload": f"{cfg_name}: WMF k={k}{'+bias' if bias else ''}, {n_users}x{n_items} CSR, "
-                               f"{nnz} nnz, alpha-log confidence, gamma={gamma}, zipf_a={zipf}",
-                   "n_users": n_users, "n_items": n_items, "nnz": nnz, "k": k, "bias": bias,
-                   "exchange": {s_: (("reduce" if eng.reduce[s_] else "need-list" if eng.sparse[s_] else "all-gather")
-                                     + ("+pipelined" if eng.pipe[s_] else "")) + f" x{len(eng.chunk_bounds[s_])}"
-                                for s_ in SIDES} if world > 1 or eng.exchange else None,
-                   "sharding": f"users+items dealt by cost (nnz f^2 + f^3) over {world} GPU(s), every rank loads 1/{world} of the user "
-                               f"rows; exchange users: "
-                               f"{'reduce-scatter of partial systems' if eng.reduce['users'] else ('need-list all-to-all (%.0f %% of the rows per rank)' % (100 * eng.need['users']['needed_fraction']) if eng.sparse['users'] else 'all-gather')} in "
-                               f"{len(eng.chunk_bounds['users'])} chunk(s), items: "
-                               f"{'reduce-scatter of partial systems' if eng.reduce['items'] else 'all-gather'} in "
-                               f"{len(eng.chunk_bounds['items'])} chunk(s); accumulation pipelined over arriving chunks: "
-                               f"{[s_ for s_ in SIDES if eng.pipe[s_]] or 'no'}"},
+        "config": config,
         "nnz_per_s": 2.0 * nnz * args.steps / elapsed,
         "epoch_algorithmic_GBps": epoch_bytes * args.steps / elapsed / 1e9,
         "epoch_hbm_frac": epoch_bytes * args.steps / elapsed / 1e9 / (HBM_PEAK_GBS * world),
@@ -526,16 +586,23 @@ def compact_roofline(r):
     return out
 
 
-def compact_line(full, detail_path):
-    """The one stdout line: the contract keys, config, roofline (dominant kernel + the two half steps' solves), cpu_baseline,
-    ranks and one small object per further workload.  Everything else is in ``detail_path`` / on stderr."""
+def headline(full):
+    """The start of the stdout line of every run, plain or --full: the contract keys, the workload and nnz_per_s."""
     line = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                                  "vs_baseline", "dtype", "data")}
     line["value"], line["ms_per_step"] = _r(line["value"], 6), _r(line["ms_per_step"], 6)
     c = full["config"]
     line["config"] = {"workload": c["workload"], "n_users": c["n_users"], "n_items": c["n_items"], "nnz": c["nnz"], "k": c["k"],
                       "bias": c["bias"], "exchange": c["exchange"]}
-    line["nnz_per_s"], line["epoch_hbm_frac"] = _r(full["nnz_per_s"]), _r(full["epoch_hbm_frac"])
+    line["nnz_per_s"] = _r(full["nnz_per_s"])
+    return line
+
+
+def compact_line(full, detail_path):
+    """The one stdout line of a --full run: headline(), roofline (dominant kernel + the two half steps' solves), cpu_baseline,
+    ranks and one small object per further workload.  Everything else is in ``detail_path`` / on stderr."""
+    line = headline(full)
+    line["epoch_hbm_frac"] = _r(full["epoch_hbm_frac"])
     line["roofline"] = compact_roofline(full.get("roofline"))
     cpu = full.get("cpu_baseline")
     if cpu:
@@ -604,11 +671,12 @@ def main():
 
     scaling = args.scaling if args.scaling != "auto" else "strong"     # (one GPU: the first point of the same series)
     main_res = run_workload(args.config, args, world, rank, dev, lib, scaling,
-                            with_cpu=(rank == 0 and world == 1 and not args.no_cpu_baseline))
+                            with_cpu=(args.full and rank == 0 and world == 1 and not args.no_cpu_baseline), full=args.full,
+                            dump_dir=args.dump_outputs)
     # further workloads of the same run, under "also": names of synth.CONFIGS, optionally "name:zipf=A", comma separated.
     # auto on one GPU: cfg2 (configs[1], with its CPU baseline), then the skewed variant of the main workload and cfg5's
     # one-GPU slice with and without the power law (the README's other rows, driver-timed); on several GPUs the bias-free cfg4
-    also_arg = args.also
+    also_arg = args.also if args.full else "none"
     if also_arg == "auto":
         also_arg = {"cfg3": "cfg2,cfg3:zipf=1.1,cfg5s,cfg5s:zipf=1.1" if world == 1 else "cfg4"}.get(args.config, "none")
         if args.zipf:
@@ -625,7 +693,7 @@ def main():
         also[item.replace(":zipf=", "_zipf")] = {"metric": "ALS user+item row-updates/sec", "unit": "row-updates/s", **r2}
 
     f64_block = None
-    if rank == 0 and world == 1 and args.config == "cfg3" and args.also == "auto" and not args.zipf:
+    if args.full and rank == 0 and world == 1 and args.config == "cfg3" and args.also == "auto" and not args.zipf:
         try:
             f64_block = float64_path("cfg2", dev, lib)
             if also and "cfg2" in also:
@@ -656,7 +724,14 @@ def main():
     out.update(main_res)
     out["cpu_baseline"] = cpu
     out["also"] = also
-    if rank == 0:
+    if rank == 0 and not args.full:
+        # a plain run: the contract keys, the workload and the timed path's rates; nothing else was measured
+        print(f"[bench] {args.config}: {out['ms_per_step']:.3f} ms per iteration", file=sys.stderr, flush=True)
+        line = headline(out)
+        line["setup_s"] = _r(out["setup_s"])
+        sys.stdout.flush()
+        os.write(result_fd, (json.dumps(line) + "\n").encode())
+    elif rank == 0:
         # The FULL record (per-kernel tables of every workload, row bins, host boundary, notes) goes to a file and to stderr;
         # stdout carries ONE compact line (a few KB) that the driver's record can hold whole.
         detail_path = os.path.join(ROOT, "gpurun_out", "bench_detail.json")

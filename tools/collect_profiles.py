@@ -70,7 +70,7 @@ for name, v in raw.items():
         "hbm_bytes_mean_corrected": None if fetch is None else (2.0 * fetch + (write or 0.0)) * 1024.0,
     }
 json.dump({
-    "command": f"rocprofv3 --pmc FETCH_SIZE | --pmc WRITE_SIZE (separate runs) -- python3 bench.py --no-cpu-baseline {bench_args}",
+    "command": f"rocprofv3 --pmc FETCH_SIZE | --pmc WRITE_SIZE (separate runs) -- python3 bench.py --full --no-cpu-baseline {bench_args}",
     "workload": prefix.split("_", 1)[1],
     "correction": "read bytes = 2 x FETCH_SIZE x 1024 (gfx950 counts half of wide/segment reads), write bytes = WRITE_SIZE x 1024",
     "kernels": kernels}, open(os.path.join(out, prefix + "_traffic.json"), "w"), indent=1)
