@@ -86,6 +86,9 @@ int wmf_factorize(const double* G_sum, int f, int ld, double lambda,
 /* out[r, :] = in~[r, :] . W  for rows [0, m), in/out [m, ld], W [f, ld]; padding columns are written as zero.
  * set_col0_one != 0 (whitening of the fixed side of a bias model): in~ is `in` with column 0 read as 1, and the bias
  * in[r,0] (wmf_model.py:328-331) is copied to col0_out[r] (may be NULL).
+ * out == in (in place) is allowed wherever out has the layout of in -- every call but the split-layout and rolled whitening
+ * below: a wave reads its 16 rows whole before it writes them (for f > 176 W is then read from global memory, one launch
+ * instead of the column slices: slower, same arithmetic; tests/test_gpu_dense.py runs it at every block count).
  * SPLIT LAYOUT.  For the widths with wmf_whitened_row_floats(f, ld, 1) == f - 1 -- f = 16 m + 1 <= 144 with ld = f + 3:
  * k = 16, 32, 64, 80, 96, 128 with biases -- set_col0_one != 0 writes the whitened side in the form the row kernels gather
  * cheapest: out is a PACKED body, out[r * (f - 1) + c] = feature c < f - 1 of row r (64 m bytes a row, whole 128-byte lines,

@@ -389,17 +389,17 @@ __device__ __forceinline__ double rl_f64(double v, int lane) {
     return __hiloint2double(hi, lo);
 }
 template <int K, int FP>
-__device__ __forceinline__ void chol64_col(double (&a)[FP], bool& ok) {
+__device__ __forceinline__ void chol64_col(double (&a)[FP], int& fail) {
     const double dk = rl_f64(a[K], K);
-    if (!(dk > 0.0)) ok = false;
+    if (!(dk > 0.0) && !fail) fail = K + 1;         // the first leading minor that is not positive definite
     const double inv = 1.0 / sqrt(dk);
     a[K] *= inv;                                    // lane K: sqrt(dk); lanes > K: L[i][K]
 #pragma unroll
     for (int j = K + 1; j < FP; ++j) a[j] -= a[K] * rl_f64(a[K], j);
 }
 template <int FP, int... Ks>
-__device__ __forceinline__ void chol64_sweep(double (&a)[FP], bool& ok, std::integer_sequence<int, Ks...>) {
-    (chol64_col<Ks, FP>(a, ok), ...);
+__device__ __forceinline__ void chol64_sweep(double (&a)[FP], int& fail, std::integer_sequence<int, Ks...>) {
+    (chol64_col<Ks, FP>(a, fail), ...);
 }
 template <int I, int FP>
 __device__ __forceinline__ void inv64_row(const double (&a)[FP], double (&x)[FP], int lane) {
@@ -425,9 +425,10 @@ __global__ __launch_bounds__(64, 1) void factorize64_kernel(const double* __rest
         if (lane < f && j < f) v = G[lane * f + j] + (lane == j ? lambda : 0.0);
         a[j] = v;
     }
-    bool ok = true;
-    chol64_sweep<FP>(a, ok, std::make_integer_sequence<int, FP>{});
-    if (lane == 0 && !ok) *info = 1;           // sticky (see factorize_kernel)
+    int fail = 0;
+    chol64_sweep<FP>(a, fail, std::make_integer_sequence<int, FP>{});
+    const bool ok = fail == 0;
+    if (lane == 0 && !ok) *info = fail;        // sticky (see factorize_kernel)
     double x[FP];
     inv64_sweep<FP>(a, x, lane, std::make_integer_sequence<int, FP>{});
     // lane j holds column j of X = L^-1:  Wunwhite[i][j] = X[i][j],  Wwhite[j][i] = X[i][j]
@@ -481,17 +482,18 @@ __device__ __forceinline__ void fz_store(double* T, int lt, const f64x4& c, int 
 }
 // Cholesky of the 16 x 16 block D (lower part read) -> L into Lt (upper part zeroed), L^-1 into Xt.  Lane i < 16
 // owns row i of D and L; lane j builds column j of the inverse.  One copy of the unrolled code for all blocks.
-__device__ __noinline__ bool fz_diag(const double* D, double* Lt, double* Xt, int lt, int lane) {
+// Returns 0, or K + 1 for the first column K of the block whose pivot is not positive (wave-uniform).
+__device__ __noinline__ int fz_diag(const double* D, double* Lt, double* Xt, int lt, int lane) {
     const int row = lane & 15;
     double a[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) a[j] = D[row * lt + j];
-    bool ok = true;
+    int fail = 0;
     double rinv[16];                                               // 1 / L[K][K]: the substitution below multiplies by it
 #pragma unroll
     for (int K = 0; K < 16; ++K) {
         const double dk = rl_f64(a[K], K);
-        if (!(dk > 0.0)) ok = false;
+        if (!(dk > 0.0) && !fail) fail = K + 1;
         // 1 / sqrt(dk): hardware estimate + two Newton steps (full double precision; the library sqrt and divide are
         // each a long dependent sequence, and this chain is serial over the 16 columns)
         double y = __builtin_amdgcn_rsq(dk);
@@ -517,7 +519,7 @@ __device__ __noinline__ bool fz_diag(const double* D, double* Lt, double* Xt, in
             Xt[j * lt + row] = x[j];                               // column `row` of L^-1 (zero above the diagonal)
         }
     }
-    return ok;
+    return fail;
 }
 
 __global__ __launch_bounds__(64, 1) void factorize64m_kernel(const double* __restrict__ G, int f, int ld, double lambda,
@@ -539,11 +541,12 @@ __global__ __launch_bounds__(64, 1) void factorize64m_kernel(const double* __res
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    bool ok = true;
+    int fail = 0;                                                    // first leading minor that is not positive definite
     auto tile = [&](double* M, int bi, int bj) { return M + (16 * bi) * FZ_LD + 16 * bj; };
     auto sync = [&]() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); };
     for (int p = 0; p < nb; ++p) {
-        ok = fz_diag(tile(Gs, p, p), tile(Gs, p, p), tile(Xs, p, p), FZ_LD, lane) && ok;     // in place: row i is read before it is written
+        const int bad = fz_diag(tile(Gs, p, p), tile(Gs, p, p), tile(Xs, p, p), FZ_LD, lane);   // in place: row i is read before it is written
+        if (bad && !fail) fail = 16 * p + bad;
         sync();
         for (int i = p + 1; i < nb; ++i) {                           // L_ip = G_ip . (L_pp^-1)^T
             const f64x4 c = fz_mul_abt(tile(Gs, i, p), FZ_LD, tile(Xs, p, p), FZ_LD, f64x4{0.0, 0.0, 0.0, 0.0}, r, q, 1.0);
@@ -569,7 +572,8 @@ __global__ __launch_bounds__(64, 1) void factorize64m_kernel(const double* __res
             fz_store(tile(Xs, i, p), FZ_LD, c, r, q);
             sync();
         }
-    if (lane == 0 && !ok) *info = 1;           // sticky (see factorize_kernel)
+    const bool ok = fail == 0;
+    if (lane == 0 && !ok) *info = fail;        // sticky (see factorize_kernel)
     // Wunwhite[i][j] = X[i][j],  Wwhite[j][i] = X[i][j]; padding columns [f, ld) zero
 #pragma unroll 8
     for (int i = 0; i < 64; ++i) {
@@ -608,8 +612,8 @@ __global__ __launch_bounds__(512, 1) void factorize_blocked_kernel(const double*
     auto tile = [&](double* M, int bi, int bj) { return M + (size_t)(16 * bi) * LD + 16 * bj; };
     for (int p = 0; p < nb; ++p) {
         if (wave == 0) {
-            const bool ok = fz_diag(tile(A, p, p), tile(A, p, p), tile(X, p, p), LD, lane);
-            if (!ok && lane == 0) bad = 1;
+            const int fail = fz_diag(tile(A, p, p), tile(A, p, p), tile(X, p, p), LD, lane);
+            if (fail && lane == 0 && !bad) bad = 16 * p + fail;          // the first leading minor that is not positive definite
         }
         __syncthreads();
         for (int i = p + 1 + wave; i < nb; i += 8) {                 // L_ip = A_ip . (L_pp^-1)^T, in place
@@ -642,7 +646,7 @@ __global__ __launch_bounds__(512, 1) void factorize_blocked_kernel(const double*
         }
     __syncthreads();
     const bool ok = bad == 0;
-    if (tid == 0 && !ok) *info = 1;            // sticky (see factorize_kernel)
+    if (tid == 0 && !ok) *info = bad;          // sticky (see factorize_kernel)
     for (int e = tid; e < f * ld; e += 512) {
         const int i = e / ld, j = e % ld;
         float wu = 0.f, ww = 0.f;

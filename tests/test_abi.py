@@ -126,3 +126,18 @@ def test_lds_dma_kernel_leaves_in_flight_registers_alone():
     res = subprocess.run([sys.executable, script], capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout + res.stderr
     assert "0 violations" in res.stdout
+
+
+def test_iteration_kernel_leaves_in_flight_registers_alone():
+    """wmf_iter.hip (the default k = 128 path since round 4) reads LDS through inline-asm ds_reads too: the same scan of its
+    gfx950 assembly, and it must have found the reads it is there to check."""
+    import re
+    import subprocess
+    import sys
+    script = os.path.join(ROOT, "tools", "check_inflight_regs.py")
+    src = os.path.join(ROOT, "recmodel_amd", "csrc", "wmf_iter.hip")
+    res = subprocess.run([sys.executable, script, src], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert "0 violations" in res.stdout
+    assert int(re.search(r"(\d+) inline-asm ds_reads checked", res.stdout).group(1)) > 0
+
