@@ -292,20 +292,38 @@ int wmf_profile_set_tag(int tag);
 int wmf_profile_collect(void);
 int wmf_profile_entry(int i, char* name, int name_cap, int* tag, double* ms, int64_t* launches, double* min_ms, double* max_ms);
 int wmf_profile_reset(void);
-/* Kernel-SELECTION switches for timing experiments (tools/kernel_lab.py); default 0, process-wide, not synchronised
- * with running solves.  Every selection computes the same results (the parity suite runs under each of them):
- *       64 plain 32 x 32 Gauss-Jordan for rows with 17..32 entries, 256 no border column, 1024 run-time-indexed eight-wave
- *       kernel for f > 144, 2048 no two-rows-per-wave kernel, 4096 register-ring heavy kernel at k = 128 (instead of the
- *       LDS-DMA ring), 8192 f32 MFMA accumulation in the LDS-DMA kernel, 65536 register-ring heavy kernel at k = 64 (instead of the LDS-DMA ring),
- *       131072 f32 Gramian and 262144 f32 row transform for f = 97 .. 144, 524288 f32 S tiles for rows with <= 32 entries,
- *       2097152 f32 MFMA kernel for f > 144 (it does not split rows above 4096 entries), 16777216 the k = 128 heavy-row
- *       kernel with 16-entry groups at one wave per SIMD (instead of 8-entry groups at two), 268435456 no matrix-free
- *       iteration kernel (csrc/wmf_iter.hip): every row above 32 entries is eliminated, as in round 3, 536870912 the VALU forms
- *       of the float64 Gramian and row transform (csrc/wmf_f64.hip) instead of the v_mfma_f64_16x16x4_f64 ones, 1073741824
- *       wmf_rolled_layout_supported() answers 0 (callers then keep the plain split layout).
- * The ablation switches 1 / 2 / 8 (no elimination / no accumulation MFMAs / no tile inverse: results WRONG) exist only
- * in a -DWMF_LAB build; the shipped library returns WMF_EINVAL for them. */
+/* Kernel-SELECTION switches (tools/kernel_lab.py, recmodel_amd/_lib.py DEBUG_FLAGS): a bit mask, default 0, process-wide,
+ * not synchronised with running solves.  Without the word `lab` a switch is accepted by the shipped library, computes the
+ * same results as the default, and is set by a GPU test (tests/test_abi.py checks that each of them occurs in one).  With
+ * `lab` it exists only in a -DWMF_LAB build (make -C recmodel_amd/csrc lab): the shipped wmf_debug_set_flags answers
+ * WMF_EINVAL for it, and the kernels only it reaches are not compiled in.  (Bit 512 is reserved: it selected the first two
+ * generations of the factorisation kernel until they were deleted.) */
+enum {
+    WMF_DBG_NO_ELIMINATION      = 1,          /* lab  ablation, results WRONG: no elimination */
+    WMF_DBG_NO_ACCUMULATION     = 2,          /* lab  ablation, results WRONG: no accumulation MFMAs */
+    WMF_DBG_NO_TILE_INVERSE     = 8,          /* lab  ablation, results WRONG: no tile inverse */
+    WMF_DBG_LOW32_GAUSS_JORDAN  = 64,         /* lab  plain 32 x 32 Gauss-Jordan for rows with 17 .. 32 entries */
+    WMF_DBG_NO_BORDER           = 256,        /* lab  no border column (and so no split layout) at f = 16 m + 1 */
+    WMF_DBG_WIDE_EIGHT_WAVES    = 1024,       /* lab  the run-time-indexed eight-wave kernel for every f > 144 */
+    WMF_DBG_NO_ROW_PAIRS        = 2048,       /* lab  no two-rows-per-wave kernel for rows with at most 8 entries */
+    WMF_DBG_HEAVY_REG_RING      = 4096,       /*      register-ring heavy-row kernel at k = 128 (instead of the LDS-DMA ring) */
+    WMF_DBG_HEAVY_F32_ACC       = 8192,       /* lab  f32 MFMA accumulation in the LDS-DMA kernel */
+    WMF_DBG_HEAVY_REG_RING_K64  = 65536,      /* lab  register-ring heavy-row kernel at k = 64 (instead of the LDS-DMA ring) */
+    WMF_DBG_F32_GRAM            = 131072,     /*      f32 MFMA Gramian for f = 97 .. 144 (instead of split bf16) */
+    WMF_DBG_F32_TRANSFORM       = 262144,     /* lab  f32 MFMA row transform for f = 97 .. 144 (no rolled layout then) */
+    WMF_DBG_LOW_F32_TILES       = 524288,     /* lab  f32 S tiles for rows with at most 32 entries */
+    WMF_DBG_WIDE_F32            = 2097152,    /* lab  f32 MFMA kernel for f > 144 (it does not split rows above 4096 entries) */
+    WMF_DBG_HEAVY_ONE_WAVE      = 16777216,   /*      k = 128 heavy-row kernel with 16-entry groups at one wave per SIMD (instead of 8 at two) */
+    WMF_DBG_HEAVY_PIVOTED_LU    = 33554432,   /* lab  every row of 33 .. 4096 entries (f <= 144) through the pivoted f32 LU kernel */
+    WMF_DBG_F64_TEAMS           = 67108864,   /* lab  float64 half step: workgroup teams at every width */
+    WMF_DBG_F64_NO_LOW_RANK     = 134217728,  /*      float64 half step: no whitened low-rank path (nor its iteration), every row by the direct f x f kernels */
+    WMF_DBG_NO_ITER             = 268435456,  /*      no matrix-free iteration kernel (csrc/wmf_iter.hip): every row above 32 entries is eliminated */
+    WMF_DBG_F64_VALU            = 536870912,  /*      VALU forms of the float64 Gramian and row transform (instead of v_mfma_f64_16x16x4_f64) */
+    WMF_DBG_NO_ROLLED_LAYOUT    = 1073741824  /* lab  wmf_rolled_layout_supported() answers 0 (callers keep the plain split layout) */
+};
+/* Returns WMF_EINVAL, and leaves the switches as they were, for a bit this build does not accept. */
 int wmf_debug_set_flags(int flags);
+int wmf_debug_get_flags(void);
 
 #ifdef __cplusplus
 }

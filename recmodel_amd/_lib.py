@@ -64,7 +64,48 @@ SIGNATURES = {
     "wmf_profile_entry": (c_int, [c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "wmf_profile_reset": (c_int, []),
     "wmf_debug_set_flags": (c_int, [c_int]),
+    "wmf_debug_get_flags": (c_int, []),
 }
+
+# The kernel-selection switches of wmf_debug_set_flags: the enum of include/wmf_hip.h, name for name (tests/test_abi.py compares
+# the two).  The shipped library accepts those of SHIPPED_DEBUG_FLAGS -- each is set by a GPU test -- and answers WMF_EINVAL for
+# the others, which exist in a lab build only (make -C recmodel_amd/csrc lab; WMF_HIP_LIB=build/lab/libwmf_hip_lab.so).
+DEBUG_FLAGS = {
+    "WMF_DBG_NO_ELIMINATION": 1,
+    "WMF_DBG_NO_ACCUMULATION": 2,
+    "WMF_DBG_NO_TILE_INVERSE": 8,
+    "WMF_DBG_LOW32_GAUSS_JORDAN": 64,
+    "WMF_DBG_NO_BORDER": 256,
+    "WMF_DBG_WIDE_EIGHT_WAVES": 1024,
+    "WMF_DBG_NO_ROW_PAIRS": 2048,
+    "WMF_DBG_HEAVY_REG_RING": 4096,
+    "WMF_DBG_HEAVY_F32_ACC": 8192,
+    "WMF_DBG_HEAVY_REG_RING_K64": 65536,
+    "WMF_DBG_F32_GRAM": 131072,
+    "WMF_DBG_F32_TRANSFORM": 262144,
+    "WMF_DBG_LOW_F32_TILES": 524288,
+    "WMF_DBG_WIDE_F32": 2097152,
+    "WMF_DBG_HEAVY_ONE_WAVE": 16777216,
+    "WMF_DBG_HEAVY_PIVOTED_LU": 33554432,
+    "WMF_DBG_F64_TEAMS": 67108864,
+    "WMF_DBG_F64_NO_LOW_RANK": 134217728,
+    "WMF_DBG_NO_ITER": 268435456,
+    "WMF_DBG_F64_VALU": 536870912,
+    "WMF_DBG_NO_ROLLED_LAYOUT": 1073741824,
+}
+SHIPPED_DEBUG_FLAGS = ("WMF_DBG_HEAVY_REG_RING", "WMF_DBG_F32_GRAM", "WMF_DBG_HEAVY_ONE_WAVE", "WMF_DBG_F64_NO_LOW_RANK",
+                       "WMF_DBG_NO_ITER", "WMF_DBG_F64_VALU")
+
+
+def parse_debug_flags(text):
+    """A switch mask from a number ("268435456", "0x1000") or from names joined by `|` ("NO_ITER|WMF_DBG_F64_VALU"): what
+    WMF_DEBUG_FLAGS and the command lines of the tools accept."""
+    value = 0
+    for part in str(text).split("|"):
+        part = part.strip()
+        name = part if part.startswith("WMF_DBG_") else "WMF_DBG_" + part
+        value |= DEBUG_FLAGS[name] if name in DEBUG_FLAGS else int(part, 0)
+    return value
 
 
 class WmfLibraryError(RuntimeError):
@@ -91,11 +132,11 @@ def load():
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError here = header and library out of sync
         fn.restype, fn.argtypes = res, args
-    # kernel-SELECTION switches for experiments (include/wmf_hip.h, wmf_debug_set_flags): every selection computes the same
-    # results; e.g. WMF_DEBUG_FLAGS=268435456 runs the whole parity suite without the matrix-free iteration kernel
+    # kernel-selection switches for experiments (DEBUG_FLAGS above): e.g. WMF_DEBUG_FLAGS=WMF_DBG_NO_ITER (or =268435456) runs
+    # the whole parity suite without the matrix-free iteration kernel; a switch this library does not have is an error
     flags = os.environ.get("WMF_DEBUG_FLAGS")
-    if flags:
-        lib.wmf_debug_set_flags(int(flags, 0))
+    if flags and lib.wmf_debug_set_flags(parse_debug_flags(flags)) != WMF_OK:
+        raise ValueError(lib.wmf_last_error().decode("utf-8", "replace"))
     _lib = lib
     return lib
 

@@ -96,14 +96,15 @@ void wmf_prof_end(hipStream_t st) {
 extern "C" {
 
 int wmf_debug_set_flags(int flags) {
-#ifndef WMF_LAB
-    // Ablation switches that make results WRONG (1, 2, 8) and the f32-MFMA accumulation of the LDS-DMA kernel (8192) exist only
-    // in a -DWMF_LAB build (tools/build_variant.sh)
-    if (flags & (1 | 2 | 8 | 8192)) { wmf_set_error("wmf_debug_set_flags: flags 1/2/8/8192 need a -DWMF_LAB build"); return WMF_EINVAL; }
-#endif
+    if (flags & ~WMF_DBG_ACCEPTED) {
+        wmf_set_error("wmf_debug_set_flags: %d holds switches this build does not have (%s; include/wmf_hip.h, WMF_DBG_*)", flags,
+                      (flags & ~(WMF_DBG_SHIPPED | WMF_DBG_LAB)) ? "unknown bits" : "they need a -DWMF_LAB build");
+        return WMF_EINVAL;
+    }
     wmf_debug_flags = flags;
     return WMF_OK;
 }
+int wmf_debug_get_flags(void) { return wmf_debug_flags; }
 int wmf_profile_enable(int on) { g_prof_on.store(on != 0); return WMF_OK; }
 int wmf_profile_set_tag(int tag) { std::lock_guard<std::mutex> lk(g_prof_mu); g_prof_tag = tag; return WMF_OK; }
 int wmf_profile_reset(void) {
@@ -373,14 +374,14 @@ int wmf_solve_rows_ex(const wmf_plan* plan, const float* V, const float* bias_fi
         wmf_set_error("wmf_solve_rows_ex: WMF_SOLVE_ROLLED needs bias_fixed and wmf_rolled_layout_supported(f=%d, ld=%d)", f, ld);
         return WMF_EINVAL;
     }
-    if (plan) plan->rolled = (flags & WMF_SOLVE_ROLLED) ? 1 : 0;
     if (!plan || !V || !indptr || !g || !fail_count) { wmf_set_error("wmf_solve_rows: null pointer"); return WMF_EINVAL; }
     if (bias_fixed && !plan->bias) { wmf_set_error("wmf_solve_rows: bias_fixed given, but the plan was created with bias = 0"); return WMF_EINVAL; }
     if (plan->n != n || plan->f != f) { wmf_set_error("wmf_solve_rows: plan was built for n=%lld f=%d", (long long)plan->n, plan->f); return WMF_EINVAL; }
     if (n == 0) return WMF_OK;
-    const int lrc = wmf_launch_solve(plan, V, bias_fixed, indptr, indices, values, f, ld, g, fail_count, (hipStream_t)stream);
+    const int lrc = wmf_launch_solve(plan, V, bias_fixed, indptr, indices, values, f, ld, g, fail_count,
+                                     (flags & WMF_SOLVE_ROLLED) != 0, (hipStream_t)stream);
     if (lrc == -2) { wmf_set_error("wmf_solve_rows: hipMemsetAsync failed"); return WMF_EHIP; }
-    if (lrc == -3) { wmf_set_error("wmf_solve_rows: the plan was created for the split layout of the whitened factors, the call is not (wmf_debug_set_flags(256) changed in between?)"); return WMF_EINVAL; }
+    if (lrc == -3) { wmf_set_error("wmf_solve_rows: the plan was created for the split layout of the whitened factors, the call is not"); return WMF_EINVAL; }
     if (lrc) { wmf_set_error("wmf_solve_rows: no kernel for f=%d, ld=%d", f, ld); return WMF_EINVAL; }
     return check_launch("wmf_solve_rows");
 }

@@ -229,7 +229,7 @@ static int launch_gram_nfb(const float* Y, int64_t m, int f, int ld, int bias, f
     const int64_t nsteps = (m + 3) / 4;
     const int64_t spw = (nsteps + nwaves - 1) / nwaves;
     if constexpr (NFB >= 7 && NFB <= 9) {                     // wide and still one accumulator set per wave: split-bf16 products
-        if (!(wmf_debug_flags & 131072)) {                    // (debug flag 131072: the f32 MFMA kernel)
+        if (!(wmf_debug_flags & WMF_DBG_F32_GRAM)) {          // (WMF_DBG_F32_GRAM, 131072: the f32 MFMA kernel)
             static const char* nm = wmf_kname("gram6_kernel<%d>", NFB);
             WMF_LAUNCH(nm, (gram6_kernel<NFB>), dim3(nwaves), dim3(64), 0, st, Y, m, f, ld, bias, partial, spw);
             return 0;
@@ -282,178 +282,19 @@ int wmf_launch_gram(const float* Y, int64_t m, int f, int ld, int bias, double* 
 }
 
 // ------------------------------------------------------------------------------------- factorize
-// Single workgroup.  A (fp64, row stride lda odd) lives in LDS when it fits, else in the global
-// workspace.  Right-looking Cholesky with one thread per trailing column, then the in-place
-// inverse of the lower triangle (column by column from the last), then the two fp32 outputs.
-// USE_LDS is a template parameter so that the matrix pointer keeps its address space: through a generic
-// pointer every access becomes a flat_load that waits for both memory counters (measured 10x slower).
-template <bool USE_LDS>
-__global__ __launch_bounds__(256) void factorize_kernel(const double* __restrict__ G, int f, int ld, double lambda,
-                                                        float* __restrict__ Wwhite, float* __restrict__ Wunwhite,
-                                                        int32_t* __restrict__ info, double* __restrict__ gA) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const int lda = f | 1;
-    const int t = threadIdx.x;
-    // the flag lives behind the matrix in the dynamic region (no static LDS in front of it)
-    volatile int& s_fail = *reinterpret_cast<volatile int*>(smem_raw + (USE_LDS ? (size_t)f * lda * sizeof(double) : 0));
-    auto body = [&](auto* A) {
-    if (t == 0) s_fail = 0;
-    for (int e = t; e < f * f; e += 256) {
-        const int i = e / f, j = e % f;
-        A[i * lda + j] = G[e] + (i == j ? lambda : 0.0);
-    }
-    __syncthreads();
-    // ---- Cholesky (lower).  Column k: scale, then thread j owns trailing column j.
-    for (int k = 0; k < f; ++k) {
-        const double dk = A[k * lda + k];
-        if (!(dk > 0.0)) {            // same value seen by every thread: uniform exit
-            if (t == 0) s_fail = k + 1;
-            break;
-        }
-        const double sk = sqrt(dk), inv = 1.0 / sk;
-        __syncthreads();              // everyone has read A[k][k] before it is overwritten
-        for (int i = k + 1 + t; i < f; i += 256) A[i * lda + k] *= inv;
-        if (t == 0) A[k * lda + k] = sk;
-        __syncthreads();
-        {
-            // trailing update A[i][j] -= L[i][k] L[j][k], i >= j > k.  P threads share a column
-            // (rows i = j + part, j + part + P, ...); four rows per trip so the LDS reads overlap.
-            const int ncol = f - k - 1;
-            if (ncol > 0) {
-                const int P = ncol >= 256 ? 1 : min(256 / ncol, 8);
-                const int part = t / ncol;
-                for (int j = k + 1 + (t % ncol); j < f && part < P; j += (ncol >= 256 ? 256 : f)) {
-                    const double ljk = A[j * lda + k];
-                    for (int i = j + part; i < f; i += 4 * P) {
-                        const int i1 = i + P, i2 = i + 2 * P, i3 = i + 3 * P;
-                        const double a0 = A[i * lda + k], c0 = A[i * lda + j];
-                        const double a1 = i1 < f ? A[i1 * lda + k] : 0.0, c1 = i1 < f ? A[i1 * lda + j] : 0.0;
-                        const double a2 = i2 < f ? A[i2 * lda + k] : 0.0, c2 = i2 < f ? A[i2 * lda + j] : 0.0;
-                        const double a3 = i3 < f ? A[i3 * lda + k] : 0.0, c3 = i3 < f ? A[i3 * lda + j] : 0.0;
-                        A[i * lda + j] = c0 - a0 * ljk;
-                        if (i1 < f) A[i1 * lda + j] = c1 - a1 * ljk;
-                        if (i2 < f) A[i2 * lda + j] = c2 - a2 * ljk;
-                        if (i3 < f) A[i3 * lda + j] = c3 - a3 * ljk;
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-    __syncthreads();
-    const int fail = s_fail;
-    if (t == 0 && fail) *info = fail;          // sticky: only the caller resets it (a later success must not hide a failure)
-    if (fail) {                       // poison nothing: write zero transforms so downstream stays finite
-        for (int e = t; e < f * ld; e += 256) { Wwhite[e] = 0.f; Wunwhite[e] = 0.f; }
-        return;
-    }
-    // ---- in-place inverse of lower-triangular L (unblocked trti2, lower, non-unit):
-    // for j = f-1 .. 0:  X[j][j] = 1/L[j][j];  X[i][j] = -X[j][j] * sum_{k=j+1..i} X[i][k] L[k][j]  (i > j)
-    for (int j = f - 1; j >= 0; --j) {
-        const double xjj = 1.0 / A[j * lda + j];
-        double y0 = 0.0;
-        const int i0 = j + 1 + t;      // f <= 260 and 256 threads: at most 2 rows per thread
-        const int i1 = i0 + 256;
-        double y1 = 0.0;
-        if (i0 < f) for (int k = j + 1; k <= i0; ++k) y0 += A[i0 * lda + k] * A[k * lda + j];
-        if (i1 < f) for (int k = j + 1; k <= i1; ++k) y1 += A[i1 * lda + k] * A[k * lda + j];
-        __syncthreads();              // all reads of column j done before it is overwritten
-        if (i0 < f) A[i0 * lda + j] = -xjj * y0;
-        if (i1 < f) A[i1 * lda + j] = -xjj * y1;
-        if (t == 0) A[j * lda + j] = xjj;
-        __syncthreads();
-    }
-    // ---- outputs: Wunwhite[a][b] = Linv[a][b] (a >= b), Wwhite[a][b] = Linv[b][a] (b >= a)
-    for (int e = t; e < f * ld; e += 256) {
-        const int a = e / ld, b = e % ld;
-        float wu = 0.f, ww = 0.f;
-        if (b < f) {
-            if (a >= b) wu = (float)A[a * lda + b];
-            if (b >= a) ww = (float)A[b * lda + a];
-        }
-        Wunwhite[e] = wu;
-        Wwhite[e] = ww;
-    }
-    };
-    if constexpr (USE_LDS) body(reinterpret_cast<double*>(smem_raw));
-    else body(gA);
-}
-
-// ---- f <= 64: one wave, one lane per matrix row, the whole fp64 matrix in registers ------------
-// Right-looking Cholesky with the pivot column broadcast by v_readlane (two halves per double), then
-// lane j builds column j of L^-1 by forward substitution.  No LDS, no barriers: ~10x faster than the
-// workgroup version at f = 64, where 2 x 64 barrier-separated steps are pure latency.
+// a double of another lane: v_readlane on its two halves
 __device__ __forceinline__ double rl_f64(double v, int lane) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
     const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
     return __hiloint2double(hi, lo);
 }
-template <int K, int FP>
-__device__ __forceinline__ void chol64_col(double (&a)[FP], int& fail) {
-    const double dk = rl_f64(a[K], K);
-    if (!(dk > 0.0) && !fail) fail = K + 1;         // the first leading minor that is not positive definite
-    const double inv = 1.0 / sqrt(dk);
-    a[K] *= inv;                                    // lane K: sqrt(dk); lanes > K: L[i][K]
-#pragma unroll
-    for (int j = K + 1; j < FP; ++j) a[j] -= a[K] * rl_f64(a[K], j);
-}
-template <int FP, int... Ks>
-__device__ __forceinline__ void chol64_sweep(double (&a)[FP], int& fail, std::integer_sequence<int, Ks...>) {
-    (chol64_col<Ks, FP>(a, fail), ...);
-}
-template <int I, int FP>
-__device__ __forceinline__ void inv64_row(const double (&a)[FP], double (&x)[FP], int lane) {
-    double s = (I == lane) ? 1.0 : 0.0;             // X[I][lane] = (delta - sum_{k<I} L[I][k] X[k][lane]) / L[I][I]
-#pragma unroll
-    for (int k = 0; k < I; ++k) s -= rl_f64(a[k], I) * x[k];
-    x[I] = s / rl_f64(a[I], I);
-}
-template <int FP, int... Is>
-__device__ __forceinline__ void inv64_sweep(const double (&a)[FP], double (&x)[FP], int lane, std::integer_sequence<int, Is...>) {
-    (inv64_row<Is, FP>(a, x, lane), ...);
-}
-
-template <int FP>
-__global__ __launch_bounds__(64, 1) void factorize64_kernel(const double* __restrict__ G, int f, int ld, double lambda,
-                                                            float* __restrict__ Wwhite, float* __restrict__ Wunwhite,
-                                                            int32_t* __restrict__ info) {
-    const int lane = threadIdx.x;
-    double a[FP];
-#pragma unroll
-    for (int j = 0; j < FP; ++j) {
-        double v = (lane == j) ? 1.0 : 0.0;         // identity padding for rows / columns >= f
-        if (lane < f && j < f) v = G[lane * f + j] + (lane == j ? lambda : 0.0);
-        a[j] = v;
-    }
-    int fail = 0;
-    chol64_sweep<FP>(a, fail, std::make_integer_sequence<int, FP>{});
-    const bool ok = fail == 0;
-    if (lane == 0 && !ok) *info = fail;        // sticky (see factorize_kernel)
-    double x[FP];
-    inv64_sweep<FP>(a, x, lane, std::make_integer_sequence<int, FP>{});
-    // lane j holds column j of X = L^-1:  Wunwhite[i][j] = X[i][j],  Wwhite[j][i] = X[i][j]
-    if (lane < f) {
-#pragma unroll
-        for (int i = 0; i < FP; ++i) {
-            if (i < f) {
-                const float v = ok ? (float)x[i] : 0.f;
-                Wunwhite[i * ld + lane] = v;
-                Wwhite[lane * ld + i] = v;
-            }
-        }
-    }
-    for (int e = lane; e < f * (ld - f); e += 64) {                      // zero padding columns [f, ld)
-        const int row = e / (ld - f), col = f + e % (ld - f);
-        Wunwhite[row * ld + col] = 0.f;
-        Wwhite[row * ld + col] = 0.f;
-    }
-}
 
 // ---- f <= 64, blocked: 16 x 16 blocks, fp64 MFMA for every block product -------------------------------
-// The register-resident version above is correct but 32 000 instructions long (every (column, row) pair of both
-// sweeps is unrolled): four times the instruction cache, so it runs at fetch speed (0.12 ms).  Here only the
-// 16 x 16 diagonal blocks are factored and inverted with unrolled scalar code (one copy, called per block); panels,
-// trailing updates and the block forward substitution of L^-1 are v_mfma_f64_16x16x4_f64 products on tiles in LDS.
+// A register-resident version of the whole 64 x 64 problem (one lane per row, every (column, row) pair of both sweeps
+// unrolled; deleted, see git log) was 32 000 instructions long: four times the instruction cache, so it ran at fetch
+// speed (0.12 ms).  Here only the 16 x 16 diagonal blocks are factored and inverted with unrolled scalar code (one copy,
+// called per block); panels, trailing updates and the block forward substitution of L^-1 are v_mfma_f64_16x16x4_f64 products
+// on tiles in LDS.
 //   A operand: lane (r = l & 15, q = l >> 4) supplies A[r][4 kk + q];  B: B[4 kk + q][r];
 //   D: lane holds D[q + 4 v][r] in element v (the f64 form's row order differs from the f32 one).
 typedef double f64x4 __attribute__((ext_vector_type(4)));
@@ -573,7 +414,7 @@ __global__ __launch_bounds__(64, 1) void factorize64m_kernel(const double* __res
             sync();
         }
     const bool ok = fail == 0;
-    if (lane == 0 && !ok) *info = fail;        // sticky (see factorize_kernel)
+    if (lane == 0 && !ok) *info = fail;        // sticky: only the caller resets it (a later success must not hide a failure)
     // Wunwhite[i][j] = X[i][j],  Wwhite[j][i] = X[i][j]; padding columns [f, ld) zero
 #pragma unroll 8
     for (int i = 0; i < 64; ++i) {
@@ -646,7 +487,7 @@ __global__ __launch_bounds__(512, 1) void factorize_blocked_kernel(const double*
         }
     __syncthreads();
     const bool ok = bad == 0;
-    if (tid == 0 && !ok) *info = bad;          // sticky (see factorize_kernel)
+    if (tid == 0 && !ok) *info = bad;          // sticky: only the caller resets it (a later success must not hide a failure)
     for (int e = tid; e < f * ld; e += 512) {
         const int i = e / ld, j = e % ld;
         float wu = 0.f, ww = 0.f;
@@ -658,39 +499,13 @@ __global__ __launch_bounds__(512, 1) void factorize_blocked_kernel(const double*
 
 int wmf_launch_factorize(const double* G_sum, int f, int ld, double lambda, float* Wwhite, float* Wunwhite,
                          int32_t* info, double* gA, hipStream_t st) {
-    if (f <= 64 && !(wmf_debug_flags & 512)) {       // blocked single-wave version (fp64 MFMA)
+    if (f <= 64) {                                   // blocked single-wave version (fp64 MFMA)
         WmfProfScope ps("factorize64m_kernel", st);
         hipLaunchKernelGGL(factorize64m_kernel, dim3(1), dim3(64), 0, st, G_sum, f, ld, lambda, Wwhite, Wunwhite, info);
         return 0;
     }
-    if (f <= 64) {                                   // register-resident single-wave version (debug flag 512: A/B timing)
-        WmfProfScope ps("factorize64_kernel", st);
-        if (f <= 16) hipLaunchKernelGGL(factorize64_kernel<16>, dim3(1), dim3(64), 0, st, G_sum, f, ld, lambda, Wwhite, Wunwhite, info);
-        else if (f <= 32) hipLaunchKernelGGL(factorize64_kernel<32>, dim3(1), dim3(64), 0, st, G_sum, f, ld, lambda, Wwhite, Wunwhite, info);
-        else if (f <= 48) hipLaunchKernelGGL(factorize64_kernel<48>, dim3(1), dim3(64), 0, st, G_sum, f, ld, lambda, Wwhite, Wunwhite, info);
-        else hipLaunchKernelGGL(factorize64_kernel<64>, dim3(1), dim3(64), 0, st, G_sum, f, ld, lambda, Wwhite, Wunwhite, info);
-        return 0;
-    }
-    if (!(wmf_debug_flags & 512)) {                  // blocked workgroup version (fp64 MFMA); flag 512: the older kernel below
-        WmfProfScope ps("factorize_blocked_kernel", st);
-        hipLaunchKernelGGL(factorize_blocked_kernel, dim3(1), dim3(512), 0, st, G_sum, f, ld, lambda, Wwhite, Wunwhite, info, gA);
-        return 0;
-    }
-    const int lda = f | 1;
-    const size_t bytes = (size_t)f * lda * sizeof(double);
-    const bool use_lds = bytes <= 150 * 1024;
-    static bool attr_set = false;
-    if (use_lds && !attr_set) {
-        (void)hipFuncSetAttribute((const void*)factorize_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  150 * 1024 + 16);
-        attr_set = true;
-    }
-    WmfProfScope ps("factorize_kernel", st);
-    if (use_lds)
-        hipLaunchKernelGGL(factorize_kernel<true>, dim3(1), dim3(256), bytes + 16, st, G_sum, f, ld, lambda, Wwhite, Wunwhite,
-                           info, gA);
-    else
-        hipLaunchKernelGGL(factorize_kernel<false>, dim3(1), dim3(256), 16, st, G_sum, f, ld, lambda, Wwhite, Wunwhite, info, gA);
+    WmfProfScope ps("factorize_blocked_kernel", st);     // blocked workgroup version (fp64 MFMA)
+    hipLaunchKernelGGL(factorize_blocked_kernel, dim3(1), dim3(512), 0, st, G_sum, f, ld, lambda, Wwhite, Wunwhite, info, gA);
     return 0;
 }
 
@@ -1020,13 +835,18 @@ static void launch_transform_nfb(const float* in, int64_t m, int f, int ld, cons
     int64_t grid = (nblk + 7) / 8;
     if (grid > 1024) grid = 1024;
     if (grid < 1) grid = 1;
-    if constexpr (NFB >= 7 && NFB <= 9) {                     // wide factors: split-bf16 products (debug flag 262144: f32 MFMAs)
-        if (!(wmf_debug_flags & 262144)) {
+    // wide factors: split-bf16 products.  The f32 kernel below at those widths (WMF_DBG_F32_TRANSFORM, 262144) is compiled into
+    // lab builds only.
+    constexpr bool WIDE = NFB >= 7 && NFB <= 9;
+    if constexpr (WIDE) {
+        if (!WMF_LAB_BUILD || !(wmf_debug_flags & WMF_DBG_F32_TRANSFORM)) {
             launch_transform6<NFB>(in, m, f, ld, W, set_col0_one, out, col0_out, grid, nblk, st);
             return;
         }
     }
-    if constexpr (lds <= 150 * 1024) {
+    if constexpr (WIDE && !WMF_LAB_BUILD) {
+        // (not reached: every launch took the branch above)
+    } else if constexpr (lds <= 150 * 1024) {
         launch_transform_slice<NFB, 0, NFB>(in, m, f, ld, W, set_col0_one, out, col0_out, grid, nblk, st);
     } else if (in != out) {
         // W does not fit LDS (f > 176): two or three column slices of W, one launch each; every launch reads the

@@ -290,7 +290,7 @@ __global__ __launch_bounds__(64, (NFB <= 4 || GE == 8) ? 2 : 1) void solve_direc
             else if (younger == 1) dl_wait_vm<NI>();
             else if (itn < count) dl_wait_vm<2>();       // only the next row's two metadata requests are younger
             else dl_wait_vm<0>();
-            if (WMF_ABL(dbg, 2)) return;
+            if (WMF_ABL(dbg, WMF_DBG_NO_ACCUMULATION)) return;
             const unsigned par = ((mb + (G >> 2)) & 3) * 256;
             const int nk = min(4, (d - 16 * G + 3) >> 2);        // k-steps of this group that hold entries of the row
             // LDS operands of k-step t + 1 are requested before the MFMAs of k-step t (only the first k-step of a group
@@ -401,7 +401,7 @@ __global__ __launch_bounds__(64, (NFB <= 4 || GE == 8) ? 2 : 1) void solve_direc
                 issue_rows(S, G + 4, mb);
                 if (G + 5 < ngroups) issue_rows(S + 1, G + 5, mb);
             }
-            if (WMF_ABL(dbg, 2)) return;
+            if (WMF_ABL(dbg, WMF_DBG_NO_ACCUMULATION)) return;
             // right-hand side and border on the VALU from the raw values; MFMA operands scaled by sqrt(w) and split.
             // Block column by block column: the split of column bj + 1 (VALU) has no dependence on the MFMAs of column bj,
             // and a bf16 MFMA leaves half of its cycles to the VALU.
@@ -581,7 +581,7 @@ int wmf_launch_directl(const int32_t* rows, int64_t count, const float* V, const
     const dim3 grid((unsigned)(count < cap ? count : cap));
     const int dbg = wmf_debug_flags;
 #ifdef WMF_LAB
-    const bool x6 = !(dbg & 8192);                              // debug flag 8192 (lab builds only): f32 MFMA accumulation
+    const bool x6 = !(dbg & WMF_DBG_HEAVY_F32_ACC);             // (8192, lab builds only): f32 MFMA accumulation
 #else
     constexpr bool x6 = true;                                   // (the f32-MFMA accumulation variants are compiled into -DWMF_LAB builds only)
 #endif
@@ -595,11 +595,11 @@ int wmf_launch_directl(const int32_t* rows, int64_t count, const float* V, const
 #define DL_PICK(N) do { if (f % 16) DL_LAUNCH(N, true, true); else DL_LAUNCH(N, false, true); } while (0)
 #endif
     if (nfb == 4) DL_PICK(4);
-    else if (x6 && !(dbg & 16777216)) {
+    else if (x6 && !(dbg & WMF_DBG_HEAVY_ONE_WAVE)) {
         // k = 128: 8-entry groups (16 KB ring, 16-entry chunks with 16x16x16 MFMAs, w_p in LDS by inline asm, lane coordinates
         // re-formed at every pivot), TWO waves per SIMD on 256 registers each (249 used, no scratch).  The second wave
         // overlaps what one wave cannot -- rocprofv3 --pmc at cfg3: VALU active 80 % + MFMA busy 38 % of the SIMD cycles,
-        // SQ_WAIT_ANY 16 % of the wave cycles, where the one-wave kernel (debug flag 16777216) shows 63 + 19 and 19 that
+        // SQ_WAIT_ANY 16 % of the wave cycles, where the one-wave kernel (WMF_DBG_HEAVY_ONE_WAVE, 16777216) shows 63 + 19 and 19 that
         // add up -- for 19.9 against 21.2 ms.  On the way there: every scratch reload is a VMEM operation that returns in
         // order, i.e. behind every LDS-DMA of the ring (27.3 ms with reloads of spilled lane constants inside the chunk loop,
         // 21.0 with none there, 19.9 with none at all); hipcc puts s_waitcnt vmcnt(0) in front of every LDS access it can see.

@@ -149,7 +149,7 @@ __global__ __launch_bounds__(64, DwCfg<NFB>::OCC) void solve_directw_kernel(cons
         auto step = [&](auto slot, int G) {
             constexpr int S = decltype(slot)::value;
             if (G >= ngroups) return;
-            if (!WMF_ABL(dbg, 2)) {
+            if (!WMF_ABL(dbg, WMF_DBG_NO_ACCUMULATION)) {
 #pragma unroll
                 for (int t = 0; t < GS; ++t) {
                     float fw[NFB];
@@ -287,19 +287,19 @@ __global__ __launch_bounds__(64, DwCfg<NFB>::OCC) void solve_directw_kernel(cons
 
 template <int NFB, bool BORDER>
 static void launch_directw_nfb(const wmf_plan* pl, const float* V, const float* side, const int64_t* indptr,
-                               const int32_t* indices, const float* vals, int f, int ld, float* g, int dbg, hipStream_t st) {
+                               const int32_t* indices, const float* vals, int f, int ld, float* g, int dbg, bool rolled, hipStream_t st) {
     constexpr int waves_per_cu = 4 * DwCfg<NFB>::OCC;
     const int64_t cap = 256 * waves_per_cu * 3;                  // resident waves, three rounds queued
     const int32_t* rows = pl->rows[WMF_BIN_MFMA];
     const int64_t normal = pl->count[WMF_BIN_MFMA] - pl->heavy_count;
     // ROUND 4: the first iter_count of the normal rows (at most wmf_iter_dmax entries each, wmf_plan_create) go to the
     // matrix-free iteration kernel (wmf_iter.hip); what it cannot solve to float32 accuracy in a few applications of the
-    // row's operator comes back as a device-side list and is eliminated below like every other row.  Debug flag 268435456
+    // row's operator comes back as a device-side list and is eliminated below like every other row.  WMF_DBG_NO_ITER (268435456)
     // switches the iteration off (everything eliminated, as in round 3).
     const int64_t n_iter = wmf_iter_rows(pl, f, ld, side != nullptr);
     if (n_iter > 0)
         (void)wmf_launch_iter(rows, n_iter, V, side, indptr, indices, vals, f, ld, g, pl->iter_bounce_rows, pl->fallback_count + 1,
-                              pl->iter_stats, pl->iter_info, st, (side && pl->rolled) ? 1 : 0);
+                              pl->iter_stats, pl->iter_info, st, (side && rolled) ? 1 : 0);
     // two launches of the elimination kernel: the rows that were never candidates (count on the host), then the bounced ones
     // (count on the device; the grid is sized for the list's capacity and exits at once when the list is empty)
     for (int pass = 0; pass < 2; ++pass) {
@@ -307,12 +307,12 @@ static void launch_directw_nfb(const wmf_plan* pl, const float* V, const float* 
         const int64_t pcount = pass ? n_iter : normal - n_iter;
         const int32_t* pdev = pass ? pl->fallback_count + 1 : nullptr;
         if (pcount <= 0) continue;
-        // k = 128 with or without biases: the LDS-DMA ring kernel (wmf_directl.hip); debug flag 4096 keeps the register ring
+        // k = 128 with or without biases: the LDS-DMA ring kernel (wmf_directl.hip); WMF_DBG_HEAVY_REG_RING (4096) keeps the register ring
         // and k = 64 since round 2: with the split-f16 accumulation AND elimination the LDS-DMA kernel, two waves per SIMD there,
         // takes 0.97 ms for cfg2's item side where the f32 register-ring kernel takes 1.39 (round 1, bf16 x 3 accumulation
-        // and f32 elimination: 1.34 against 1.30; debug flag 65536 keeps the register ring at k = 64)
+        // and f32 elimination: 1.34 against 1.30; WMF_DBG_HEAVY_REG_RING_K64, 65536, keeps the register ring at k = 64 in lab builds)
         // (side: NULL, or the {last feature, bias} pairs of the split layout, V then being the packed body)
-        if (wmf_directl_supported(f, ld) && !(dbg & 4096) && (f >= 128 || !(dbg & 65536))) {
+        if (wmf_directl_supported(f, ld) && !(dbg & WMF_DBG_HEAVY_REG_RING) && (f >= 128 || !(dbg & WMF_DBG_HEAVY_REG_RING_K64))) {
             (void)wmf_launch_directl(prow, pcount, V, side, indptr, indices, vals, f, ld, g, pl->fallback_rows, pl->fallback_count, st, pdev);
         } else {
             static const char* nm = wmf_kname("solve_directw_kernel<%d, 0, %s>", NFB, BORDER ? "true" : "false");
@@ -326,8 +326,8 @@ static void launch_directw_nfb(const wmf_plan* pl, const float* V, const float* 
         const int64_t nseg = pl->seg_total;
         static const char* nm1 = wmf_kname("solve_directw_kernel<%d, 1, %s>", NFB, BORDER ? "true" : "false");
         static const char* nm2 = wmf_kname("solve_directw_kernel<%d, 2, %s>", NFB, BORDER ? "true" : "false");
-        // (k = 128: the segments through the LDS-DMA kernel as well -- same partial layout; debug flags 4096 / 16777216: here)
-        if (NFB == 8 && wmf_directl_supported(f, ld) && !(dbg & (4096 | 8192 | 16777216))) {
+        // (k = 128: the segments through the LDS-DMA kernel as well -- same partial layout; WMF_DBG_HEAVY_REG_RING / _HEAVY_ONE_WAVE: here)
+        if (NFB == 8 && wmf_directl_supported(f, ld) && !(dbg & (WMF_DBG_HEAVY_REG_RING | WMF_DBG_HEAVY_F32_ACC | WMF_DBG_HEAVY_ONE_WAVE))) {
             (void)wmf_launch_directl_segments(nseg, V, side, indices, vals, f, ld, pl->seg_lo, pl->seg_d, pl->partial, st);
         } else
         WMF_LAUNCH(nm1, (solve_directw_kernel<NFB, 1, BORDER>), dim3((unsigned)(nseg < cap ? nseg : cap)), dim3(64), 0, st, rows,
@@ -350,7 +350,7 @@ static void launch_accumulate_nfb(const float* V, const float* side, const int64
     const int64_t cap = 256 * 4 * DwCfg<NFB>::OCC * 3;
     static const char* nm = wmf_kname("solve_directw_kernel<%d, 1, %s>", NFB, BORDER ? "true" : "false");
     WMF_LAUNCH(nm, (solve_directw_kernel<NFB, 1, BORDER>), dim3((unsigned)(n < cap ? n : cap)), dim3(64), 0, st, nullptr, n, V,
-               side, indptr, indices, vals, f, ld, nullptr, nullptr, nullptr, wmf_debug_flags & ~3, indptr, degrees,
+               side, indptr, indices, vals, f, ld, nullptr, nullptr, nullptr, wmf_debug_flags & ~(WMF_DBG_NO_ELIMINATION | WMF_DBG_NO_ACCUMULATION), indptr, degrees,
                nullptr, partial, slot_stride, slot_offset, (const int32_t*)nullptr);
 }
 template <int NFB, bool BORDER>
@@ -359,7 +359,7 @@ static void launch_eliminate_nfb(float* partial, int64_t n, int slots_per_row, i
     const int64_t cap = 256 * 4 * DwCfg<NFB>::OCC * 3;
     static const char* nm = wmf_kname("solve_directw_kernel<%d, 2, %s>", NFB, BORDER ? "true" : "false");
     WMF_LAUNCH(nm, (solve_directw_kernel<NFB, 2, BORDER>), dim3((unsigned)(n < cap ? n : cap)), dim3(64), 0, st, nullptr, n,
-               nullptr, nullptr, nullptr, nullptr, nullptr, f, ld, g, fb_rows, fail_count, wmf_debug_flags & ~3, nullptr,
+               nullptr, nullptr, nullptr, nullptr, nullptr, f, ld, g, fb_rows, fail_count, wmf_debug_flags & ~(WMF_DBG_NO_ELIMINATION | WMF_DBG_NO_ACCUMULATION), nullptr,
                nullptr, nullptr, partial, slots_per_row, 0, (const int32_t*)nullptr);
 }
 static bool dw_border(int f) { return wmf_dw_border(f); }
@@ -416,14 +416,14 @@ int wmf_launch_eliminate(float* partial, int64_t n, int slots_per_row, int f, in
 }
 
 int wmf_launch_directw(const wmf_plan* pl, const float* V, const float* side, const int64_t* indptr,
-                       const int32_t* indices, const float* vals, int f, int ld, float* g, hipStream_t st) {
+                       const int32_t* indices, const float* vals, int f, int ld, float* g, bool rolled, hipStream_t st) {
     if (pl->count[WMF_BIN_MFMA] <= 0) return 0;
     const int dbg = wmf_debug_flags;
     // k = 16 m with biases: m blocks and a border column.  The row stream must deliver the border feature as its own
     // dword block (lane 0), which it does unless m + 1 is a multiple of 4 (then all blocks are 16-byte pieces).
     if (dw_border(f)) {
         switch (f / 16) {
-#define C_(N) case N: launch_directw_nfb<N, true>(pl, V, side, indptr, indices, vals, f, ld, g, dbg, st); break;
+#define C_(N) case N: launch_directw_nfb<N, true>(pl, V, side, indptr, indices, vals, f, ld, g, dbg, rolled, st); break;
             C_(1) C_(2) C_(4) C_(5) C_(6) C_(8)
 #undef C_
             default: return -1;
@@ -431,7 +431,7 @@ int wmf_launch_directw(const wmf_plan* pl, const float* V, const float* side, co
         return 0;
     }
     switch ((f + 15) / 16) {
-#define C_(N) case N: launch_directw_nfb<N, false>(pl, V, side, indptr, indices, vals, f, ld, g, dbg, st); break;
+#define C_(N) case N: launch_directw_nfb<N, false>(pl, V, side, indptr, indices, vals, f, ld, g, dbg, rolled, st); break;
         C_(1) C_(2) C_(3) C_(4) C_(5) C_(6) C_(7) C_(8) C_(9)
 #undef C_
         default: return -1;

@@ -122,7 +122,7 @@ __device__ __forceinline__ void dw_eliminate(f32x4 (&acc)[NFB * (NFB + 1) / 2], 
     int pmin = 0x7f800000, pmax = 0, spread = 0;                 // wave-uniform: smallest / largest pivot of the tile inverses (bit patterns), largest spread within a tile
     float cacc2 = 0.f, eacc2 = 0.f;                              // BORDER: per-lane parts of the two border sums
     // ---- C: block elimination, everything in registers except the two panel buffers
-    if (!WMF_ABL(dbg, 1)) {
+    if (!WMF_ABL(dbg, WMF_DBG_NO_ELIMINATION)) {
 #pragma unroll
         for (int b = 0; b < NFB; ++b) {
 #pragma unroll
@@ -142,7 +142,7 @@ __device__ __forceinline__ void dw_eliminate(f32x4 (&acc)[NFB * (NFB + 1) / 2], 
                 if constexpr (RELANE && WMF_DW_GJM != 0) {
                     gj_sweep_mfma(X, pmin, std::make_integer_sequence<int, 16>{});
                     X = -X;
-                } else if (!WMF_ABL(dbg, 8)) {
+                } else if (!WMF_ABL(dbg, WMF_DBG_NO_TILE_INVERSE)) {
                     float dsc = 1.f;                                 // un-normalised sweep (wmf_common.h): X = diag(dsc) . tile
                     gj_inv_sweep_lean<(RELANE && WMF_DW_BP != 0)>(X, dsc, pmin, pmax, spread, 4 * r, std::make_integer_sequence<int, 16>{});
                     X *= dsc;
@@ -156,7 +156,7 @@ __device__ __forceinline__ void dw_eliminate(f32x4 (&acc)[NFB * (NFB + 1) / 2], 
             // ids the compiler cannot see through make it compare in place: 20 v_cmp per pivot instead.
             int rp = r, qp = q;
             asm volatile("" : "+v"(rp), "+v"(qp));
-            if (!WMF_ABL(dbg, 8))                                      // timing experiments only: 8 = no tile inverse
+            if (!WMF_ABL(dbg, WMF_DBG_NO_TILE_INVERSE))                                      // timing experiments only: 8 = no tile inverse
                 gj_inv_sweep<GJ_LDS, true, true>(X, baddr, rp, qp, ok, std::make_integer_sequence<int, 16>{});
 #else
             gj_inv_sweep<GJ_LDS, true, true>(X, baddr, r, q, ok, std::make_integer_sequence<int, 16>{});
@@ -293,7 +293,7 @@ __device__ __forceinline__ void dw_eliminate(f32x4 (&acc)[NFB * (NFB + 1) / 2], 
         if (!(piv > 1e-20f)) ok = false;
         tb = eacc * __builtin_amdgcn_rcpf(piv);
     }
-    if (!WMF_ABL(dbg, 1)) {
+    if (!WMF_ABL(dbg, WMF_DBG_NO_ELIMINATION)) {
 #pragma unroll
         for (int p = NFB - 1; p >= 0; --p) {
             relane();

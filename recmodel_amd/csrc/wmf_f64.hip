@@ -492,7 +492,7 @@ __global__ void f64_count_low_kernel(const int64_t* __restrict__ indptr, int64_t
     for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(&ctrl[1], c);
 }
-// ctrl[0] = 1: the low-rank path is on for this half step (enough rows for the whitening pass to pay, debug flag not set)
+// ctrl[0] = 1: the low-rank path is on for this half step (enough rows for the whitening pass to pay, WMF_DBG_F64_NO_LOW_RANK not set)
 // (iter_on: the matrix-free iteration of wmf_iter64.hip reads the whitened factors for rows of every length)
 __global__ void f64_decide_kernel(int32_t* __restrict__ ctrl, int64_t n, int off, int iter_on) {
     ctrl[0] = (!off && n > 0 && (iter_on || (int64_t)ctrl[1] * 4 >= n)) ? 1 : 0;
@@ -943,7 +943,7 @@ static void launch_gram64(const double* Y, int64_t m, int f, int bias, double la
     static const char* nmg = wmf_kname("gram64v2_kernel<%d>", NB);
     const int64_t rpb = (m + nwg - 1) / nwg;
     const int nb16 = (f + 15) / 16, pw = (nb16 * (nb16 + 1) / 2 + 7) / 8, ldy = 16 * nb16 + ((nb16 & 1) ? 0 : 16);
-    if (pw <= 6 && !(wmf_debug_flags & 536870912)) {        // the matrix-core form (f <= 144)
+    if (pw <= 6 && !(wmf_debug_flags & WMF_DBG_F64_VALU)) {        // the matrix-core form (f <= 144)
 #define GM_(PW)                                                                                                            \
     case PW: {                                                                                                             \
         static const char* nm_ = wmf_kname("gram64m_kernel<%d>", PW);                                                      \
@@ -989,11 +989,11 @@ static void launch_transform64(const double* in, int64_t m, int f, const double*
                                const int32_t* ctrl, hipStream_t st, const int32_t* state = nullptr) {
     if (m <= 0) return;
     const int f4 = (f + 3) / 4, FP = 4 * f4;
-    {                                               // the matrix-core form where W fits LDS (debug flag 536870912: never)
+    {                                               // the matrix-core form where W fits LDS (WMF_DBG_F64_VALU, 536870912: never)
         const int nb = (f + 15) / 16;
         const int ldw = 16 * nb + ((nb & 1) ? 0 : 16);          // 16 mod 32
         const size_t lds = (size_t)FP * ldw * 8;
-        if (lds <= 160 * 1024 && f4 <= 36 && !(wmf_debug_flags & 536870912)) {
+        if (lds <= 160 * 1024 && f4 <= 36 && !(wmf_debug_flags & WMF_DBG_F64_VALU)) {
             int64_t grid = ((m + 15) / 16 + 7) / 8;
             if (grid > 256) grid = 256;
 #define TM_(KK, G)                                                                                                                     \
@@ -1059,8 +1059,8 @@ int wmf_launch_half_step_f64(const double* Y, int64_t m, int f, int bias, const 
     if (hipMemsetAsync(fb_count, 0, 256, st) != hipSuccess) return -2;
     if (n > 0 && hipMemsetAsync(state, 0, (size_t)n * 4, st) != hipSuccess) return -2;
     // round 4: rows whose whitened system is close to the identity by a matrix-free Neumann series in float64 (wmf_iter64.hip)
-    // -- first: what it marks solved, the two kernels below skip; debug flags 134217728 (no whitened path) / 268435456 switch it off
-    const bool iter_on = wmf_iter_enabled() && wmf_iter64_dmax(f) > 0 && !(wmf_debug_flags & 134217728);
+    // -- first: what it marks solved, the two kernels below skip; WMF_DBG_F64_NO_LOW_RANK (134217728: no whitened path) / WMF_DBG_NO_ITER (268435456) switch it off
+    const bool iter_on = wmf_iter_enabled() && wmf_iter64_dmax(f) > 0 && !(wmf_debug_flags & WMF_DBG_F64_NO_LOW_RANK);
     switch (f64_nb(f64_blocks(f, false))) {
 #define C_(N) case N: launch_gram64<N>(Y, m, f, bias, lambda, partial, G, nwg, st); break;
         C_(1) C_(2) C_(3) C_(5) C_(9)
@@ -1068,11 +1068,11 @@ int wmf_launch_half_step_f64(const double* Y, int64_t m, int f, int bias, const 
         default: return -1;
     }
     if (n > 0) {
-        // ---- rows with 1 .. 32 entries through the whitened low-rank form, when there are enough of them (debug flag 134217728: never)
+        // ---- rows with 1 .. 32 entries through the whitened low-rank form, when there are enough of them (WMF_DBG_F64_NO_LOW_RANK: never)
         int64_t cgrid = (n + 255) / 256;
         if (cgrid > 1024) cgrid = 1024;
         hipLaunchKernelGGL(f64_count_low_kernel, dim3((unsigned)cgrid), dim3(256), 0, st, indptr, n, ctrl);
-        hipLaunchKernelGGL(f64_decide_kernel, dim3(1), dim3(1), 0, st, ctrl, n, (wmf_debug_flags & 134217728) ? 1 : 0, iter_on ? 1 : 0);
+        hipLaunchKernelGGL(f64_decide_kernel, dim3(1), dim3(1), 0, st, ctrl, n, (wmf_debug_flags & WMF_DBG_F64_NO_LOW_RANK) ? 1 : 0, iter_on ? 1 : 0);
         switch (f64_nb(f64_blocks(f, false))) {
 #define C_(N) case N: launch_factor64<N>(G, f, Rblk, ctrl, st); break;
             C_(1) C_(2) C_(3) C_(5) C_(9)
@@ -1102,7 +1102,7 @@ int wmf_launch_half_step_f64(const double* Y, int64_t m, int f, int bias, const 
         // ---- every other row (all of them when the low-rank path is off): the f x f system directly
         const int nblk = f64_blocks(f, true);
 #define S_(N, T, R) launch_solve64<N, T, R>(Y, f, bias, G, indptr, indices, values, n, X, fb_rows, fb_count, ctrl, st, state)
-        const bool waves = !(wmf_debug_flags & 67108864);       // debug flag 67108864 (timing experiments): workgroup teams at every width
+        const bool waves = !(wmf_debug_flags & WMF_DBG_F64_TEAMS);     // WMF_DBG_F64_TEAMS, 67108864 (timing experiments, lab builds): workgroup teams at every width
         if (!waves && nblk <= 256) S_(1, 256, 16);
         else if (nblk <= 64) S_(1, 64, 8);            // one WAVE per row while a lane holds at most three blocks (f <= 68)
         else if (nblk <= 128) S_(2, 64, 8);

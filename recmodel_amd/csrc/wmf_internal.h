@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/wmf_hip.h"
 
 #define WMF_GRAM_MAX_WAVES 4096
 #define WMF_EVAL_MAX_BLOCKS 2048
@@ -9,7 +10,22 @@
 #define WMF_SEG 2048          /* ... in segments of this many entries */
 #define WMF_WIDE_LU_GRID 64   /* workgroups (and workspace slices) of the pivoted-LU fallback for f > 144 */
 
-extern int wmf_debug_flags;   // kernel-selection switches for timing experiments (tools/kernel_lab.py); 0 in normal use
+// The kernel-selection switches (include/wmf_hip.h, WMF_DBG_*); 0 in normal use.  The shipped library accepts the switches a
+// committed GPU test sets; a lab build (-DWMF_LAB, `make lab`) accepts every one, and only it compiles the kernels that the
+// other switches select: their launch sites sit behind `if constexpr (WMF_LAB_BUILD)`.
+extern int wmf_debug_flags;
+#ifdef WMF_LAB
+constexpr bool WMF_LAB_BUILD = true;
+#else
+constexpr bool WMF_LAB_BUILD = false;
+#endif
+constexpr int WMF_DBG_SHIPPED = WMF_DBG_HEAVY_REG_RING | WMF_DBG_F32_GRAM | WMF_DBG_HEAVY_ONE_WAVE | WMF_DBG_F64_NO_LOW_RANK |
+                                WMF_DBG_NO_ITER | WMF_DBG_F64_VALU;
+constexpr int WMF_DBG_LAB = WMF_DBG_NO_ELIMINATION | WMF_DBG_NO_ACCUMULATION | WMF_DBG_NO_TILE_INVERSE | WMF_DBG_LOW32_GAUSS_JORDAN |
+                            WMF_DBG_NO_BORDER | WMF_DBG_WIDE_EIGHT_WAVES | WMF_DBG_NO_ROW_PAIRS | WMF_DBG_HEAVY_F32_ACC |
+                            WMF_DBG_HEAVY_REG_RING_K64 | WMF_DBG_F32_TRANSFORM | WMF_DBG_LOW_F32_TILES | WMF_DBG_WIDE_F32 |
+                            WMF_DBG_HEAVY_PIVOTED_LU | WMF_DBG_F64_TEAMS | WMF_DBG_NO_ROLLED_LAYOUT;
+constexpr int WMF_DBG_ACCEPTED = WMF_LAB_BUILD ? (WMF_DBG_SHIPPED | WMF_DBG_LAB) : WMF_DBG_SHIPPED;   // what wmf_debug_set_flags takes
 
 // row-degree bins of a plan
 enum { WMF_BIN_LOW16 = 0, WMF_BIN_LOW32 = 1, WMF_BIN_MFMA = 2, WMF_BIN_GENERAL = 3, WMF_NBINS = 4 };
@@ -21,7 +37,6 @@ struct wmf_plan {
     int64_t count8, nnz8;      // rows of the first bin with at most 8 entries (and their entries); they come first in rows[WMF_BIN_LOW16]
     bool bias;                 // created for a biased model: w_eff is allocated (unless split)
     bool split;                // latched at creation: the whitened fixed side comes in the split layout (no w_eff needed)
-    mutable int rolled;        // this solve's V / pairs are in the rolled coordinates with the bias bits (wmf_solve_rows_ex; set per call)
     int64_t nnz[WMF_NBINS];    // stored entries per bin
     int32_t* rows[WMF_NBINS];  // device: row ids of each bin (slices of rows_all)
     int32_t* rows_all;         // device: n row ids grouped by bin
@@ -53,13 +68,14 @@ int wmf_launch_factorize(const double* G_sum, int f, int ld, double lambda, floa
 int wmf_launch_transform(const float* in, int64_t m, int f, int ld, const float* W, int set_col0_one, float* out,
                          float* col0_out, hipStream_t st);
 
+// (rolled: this call's V / pairs are in the rolled coordinates with the bias bits, wmf_solve_rows_ex(WMF_SOLVE_ROLLED))
 int wmf_launch_solve(const wmf_plan* plan, const float* V, const float* bias_fixed, const int64_t* indptr,
                      const int32_t* indices, const float* values, int f, int ld, float* g, int32_t* fail_count,
-                     hipStream_t st);
+                     bool rolled, hipStream_t st);
 static inline int wmf_direct_supported(int f) { return f >= 1 && f <= 144; }   // one wave per row holds the f x f system
-// Widths whose last feature is a border column of an m-block system (f = 16 m + 1 <= 144, m + 1 not a multiple of 4; debug
-// flag 256 switches the border off): k = 16 m with biases.
-static inline bool wmf_dw_border(int f) { return f > 16 && f <= 144 && f % 16 == 1 && (f / 16) % 4 != 3 && !(wmf_debug_flags & 256); }
+// Widths whose last feature is a border column of an m-block system (f = 16 m + 1 <= 144, m + 1 not a multiple of 4;
+// WMF_DBG_NO_BORDER, 256, switches the border off): k = 16 m with biases.
+static inline bool wmf_dw_border(int f) { return f > 16 && f <= 144 && f % 16 == 1 && (f / 16) % 4 != 3 && !(wmf_debug_flags & WMF_DBG_NO_BORDER); }
 // SPLIT LAYOUT of the whitened fixed side of a bias model at those widths (ld = f + 3): the first f - 1 = 16 m features of
 // row i are a packed body row V[i * (f - 1) ..] -- 64 m bytes, whole 128-byte lines when m is even, where an (f + 3)-float
 // row at a 528-byte stride (f = 129) touched five lines for 4.03 lines of data -- and the last feature and the side's bias are
@@ -78,7 +94,7 @@ int wmf_launch_directl(const int32_t* rows, int64_t count, const float* V, const
 int wmf_launch_directl_segments(int64_t nseg, const float* V, const float* side, const int32_t* indices, const float* vals, int f,
                                 int ld, const int64_t* seg_lo, const int32_t* seg_d, float* partial, hipStream_t st);
 int wmf_launch_directw(const wmf_plan* pl, const float* V, const float* side, const int64_t* indptr,
-                       const int32_t* indices, const float* vals, int f, int ld, float* g, hipStream_t st);
+                       const int32_t* indices, const float* vals, int f, int ld, float* g, bool rolled, hipStream_t st);
 int64_t wmf_directw_partial_floats(int f);
 int wmf_launch_accumulate(const float* V, const float* side, const int64_t* indptr, const int32_t* degrees, const int32_t* indices,
                           const float* vals, int64_t n, int f, int ld, float* partial, int slot_stride, int slot_offset,
@@ -102,11 +118,12 @@ int wmf_iter_dmax(int f, int ld, int split);
 int wmf_launch_iter(const int32_t* rows, int64_t count, const float* V, const float* side, const int64_t* indptr,
                     const int32_t* indices, const float* vals, int f, int ld, float* g, int32_t* bounce_rows,
                     int32_t* bounce_count, unsigned long long* stats, const void* info, hipStream_t st, int lsb = 0);
-static inline bool wmf_iter_enabled() { return !(wmf_debug_flags & 268435456); }
+static inline bool wmf_iter_enabled() { return !(wmf_debug_flags & WMF_DBG_NO_ITER); }
 // The rolled whitened coordinates with the bias in the body's last mantissa bits (include/wmf_hip.h, wmf_row_transform modes 3 / 4,
 // wmf_solve_rows_ex): bias models whose packed body is 128 floats (k = 128), transform6_kernel and the iteration kernels only
+// (a lab build's f32 transform_kernel, WMF_DBG_F32_TRANSFORM, cannot write it)
 static inline bool wmf_rolled_layout(int f, int ld) {
-    return f == 129 && wmf_split_layout(f, ld) && !(wmf_debug_flags & 262144) && !(wmf_debug_flags & 1073741824);
+    return f == 129 && wmf_split_layout(f, ld) && !(wmf_debug_flags & (WMF_DBG_F32_TRANSFORM | WMF_DBG_NO_ROLLED_LAYOUT));
 }
 // candidates of this call: none when the iteration is switched off, or when the call's layout (ld, split) is not the one the
 // plan sorted its rows for (a caller with its own leading dimension: the kernel's register slots would not hold the rows)
@@ -154,8 +171,8 @@ int wmf_launch_iter64(const double* V, const double* Y, int f, int bias, const i
                       const double* vals, int64_t n, int low, double* gout, int32_t* state, const int32_t* ctrl, hipStream_t st);
 
 void wmf_set_error(const char* fmt, ...);
-// Ablation switches whose results are WRONG (1 no elimination, 2 no accumulation MFMAs, 8 no tile inverse) are compiled
-// into a -DWMF_LAB build only (tools/build_variant.sh); the shipped library has no such code path.
+// Ablation switches whose results are WRONG (WMF_DBG_NO_ELIMINATION, _NO_ACCUMULATION, _NO_TILE_INVERSE) are compiled
+// into a -DWMF_LAB build only; the shipped library has no such code path.
 #ifdef WMF_LAB
 #define WMF_ABL(dbg, bits) ((dbg) & (bits))
 #else

@@ -741,23 +741,46 @@ __global__ __launch_bounds__(64 * NW, OCC) void solve_iter_kernel(const int32_t*
 #define IT_OCC4S 2            // (three workgroups per CU spill the pairs: a scratch store of a loaded value waits for the load)
 #endif
 static int it_ldv(int f, int ld, bool split) { return split ? f - 1 : ld; }
+
+// Policy of the iteration.  The shipped library holds these values as constants and reads no environment; a lab build
+// (-DWMF_LAB) reads the WMF_ITER_* variables once, and only it compiles the instantiations that they alone reach (rows of
+// ldv <= 64, ldv = 128 in one stage).  The IT_* geometry macros above are for lab variants too.
+//   tau, kappa, kmax: start with the Neumann series while tau <= WMF_ITER_TAU (it converges for tau < 1, at the rate of the row's
+//   LARGEST EIGENVALUE, usually far below tau) and move to the Chebyshev recurrence when it contracts slower than that would;
+//   Chebyshev only while the bound on the condition number is <= WMF_ITER_KAPPA; at most WMF_ITER_KMAX applications of E
+//   eps: relative accuracy of a solved row (WMF_ITER_EPS): 2^-23, one float32 ulp
+//   min_ldv: narrow factors stay with the elimination kernels: at 4 features per lane the sums over the lanes of an entry
+//   cost as much as its multiply-adds, and the f x f elimination is cheap -- measured on MI355X at k = 64 (BASELINE.json
+//   configs[1], item rows of 200 entries, four applications of E): 1.17 ms against 1.05 ms for solve_directl.
+//   WMF_ITER_MIN_LDV = 0 sends them here as well
+//   dma (WMF_ITER_NO_DMA = 1: off), two_stage (WMF_ITER_ONE_STAGE = 1: off): see wmf_launch_iter
+struct ItPolicy { float tau, kappa; int kmax; float eps; int min_ldv; bool dma, two_stage; };
+constexpr ItPolicy IT_DEFAULTS = {0.8f, 4.f, 20, 1.2e-7f, 65, true, true};
+#ifdef WMF_LAB
 static float it_env(const char* name, float dflt) {
     const char* s = getenv(name);
     return s && *s ? (float)atof(s) : dflt;
 }
+static const ItPolicy& it_policy() {
+    static const ItPolicy p = {it_env("WMF_ITER_TAU", IT_DEFAULTS.tau), it_env("WMF_ITER_KAPPA", IT_DEFAULTS.kappa),
+                               (int)it_env("WMF_ITER_KMAX", (float)IT_DEFAULTS.kmax), it_env("WMF_ITER_EPS", IT_DEFAULTS.eps),
+                               (int)it_env("WMF_ITER_MIN_LDV", (float)IT_DEFAULTS.min_ldv), !it_env("WMF_ITER_NO_DMA", 0.f),
+                               !it_env("WMF_ITER_ONE_STAGE", 0.f)};
+    return p;
+}
+#else
+static_assert(IT_NW128 == 2 && IT_DMA == 1, "the IT_* geometry variants need a -DWMF_LAB build");
+static constexpr ItPolicy it_policy() { return IT_DEFAULTS; }
+#endif
 
 // rows of up to this many entries are candidates (0: no kernel for this width)
 int wmf_iter_dmax(int f, int ld, int split) {
     const int ldv = it_ldv(f, ld, split != 0);
     if (split && ldv > 128) return 0;
-    // Narrow factors stay with the elimination kernels by default: at 4 features per lane the sums over the lanes of an entry
-    // cost as much as its multiply-adds, and the f x f elimination is cheap -- measured on MI355X at k = 64 (BASELINE.json
-    // configs[1], item rows of 200 entries, four applications of E): 1.17 ms against 1.05 ms for solve_directl.
-    // WMF_ITER_MIN_LDV = 0 sends them here as well.
-    static const int min_ldv = (int)it_env("WMF_ITER_MIN_LDV", 65.f);
-    if (ldv < min_ldv) return 0;
+    const ItPolicy pol = it_policy();
+    if (ldv < pol.min_ldv) return 0;
     if (IT_NW128 == 2 && ldv == 128) return 8 * 16;
-    if (IT_DMA && (ldv == 64 || ldv == 128) && !it_env("WMF_ITER_NO_DMA", 0.f)) return 16 * 8;
+    if (IT_DMA && (ldv == 64 || ldv == 128) && pol.dma) return 16 * 8;
     if (ldv <= 64) return 16 * (split ? IT_NS64S : IT_NS64);
     if (ldv <= 128) return 16 * (split ? IT_NS128S : IT_NS128);
     if (ldv <= 256) return 32 * 8;
@@ -780,38 +803,33 @@ static void it_launch(const int32_t* rows, int64_t count, const float* V, const 
         (void)hipFuncSetAttribute((const void*)solve_iter_kernel<NW, FPL, NS, SPLIT, FULL, OCC, DMA, LSB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
         attr_set = true;
     }
-    // policy (environment overrides for experiments): start with the Neumann series while tau <= WMF_ITER_TAU (it converges
-    // for tau < 1, at the rate of the row's LARGEST EIGENVALUE, usually far below tau) and move to the Chebyshev recurrence
-    // when it contracts slower than that would; Chebyshev only while the bound on the condition number is <= WMF_ITER_KAPPA;
-    // at most WMF_ITER_KMAX applications of E
-    static const float tau_n = it_env("WMF_ITER_TAU", 0.8f), kap = it_env("WMF_ITER_KAPPA", 4.f);
-    static const int kmax = (int)it_env("WMF_ITER_KMAX", 20.f);
-    static const float eps = it_env("WMF_ITER_EPS", 1.2e-7f);     // relative accuracy of a solved row: 2^-23, one float32 ulp
+    const ItPolicy pol = it_policy();
     const int64_t resident = 256LL * (OCC * 4 / NW);              // workgroups the chip holds
     // four rounds queued (rows differ in length); over a device-side list -- usually empty -- one round: every workgroup of a
     // launch has to be scheduled before it can find that out, 0.10 ms for 2048 workgroups of 72 KB of LDS
     const int64_t cap = count_dev ? resident : resident * 4;
     WMF_LAUNCH(nm, (solve_iter_kernel<NW, FPL, NS, SPLIT, FULL, OCC, DMA, LSB>), dim3((unsigned)(count < cap ? count : cap)), dim3(64 * NW), dyn, st,
-               rows, count, V, side, indptr, indices, vals, f, ld, g, bounce_rows, bounce_count, tau_n, kap, kmax, eps * eps, stats, info, count_dev, bounce_stat);
+               rows, count, V, side, indptr, indices, vals, f, ld, g, bounce_rows, bounce_count, pol.tau, pol.kappa, pol.kmax, pol.eps * pol.eps, stats, info, count_dev, bounce_stat);
 }
 
 // rows[0 .. count): candidates (more than 32 and at most wmf_iter_dmax entries).  side: NULL, or the {last feature, bias}
 // pairs of the split layout (V is then the packed body).  Rows that are not solved here are appended to bounce_rows.
-int wmf_launch_iter(const int32_t* rows, int64_t count, const float* V, const float* side, const int64_t* indptr,
-                    const int32_t* indices, const float* vals, int f, int ld, float* g, int32_t* bounce_rows,
-                    int32_t* bounce_count, unsigned long long* stats, const void* info_v, hipStream_t st, int lsb) {
-    const int4* info = static_cast<const int4*>(info_v);     // NULL, or {first entry lo, hi, row id, entries} of rows[i] (wmf_plan_create)
+// (LAB: a template parameter so that `if constexpr` keeps what only the policy knobs reach out of the shipped build)
+template <bool LAB>
+static int launch_iter(const int32_t* rows, int64_t count, const float* V, const float* side, const int64_t* indptr,
+                       const int32_t* indices, const float* vals, int f, int ld, float* g, int32_t* bounce_rows,
+                       int32_t* bounce_count, unsigned long long* stats, const int4* info, hipStream_t st, int lsb) {
+    // info: NULL, or {first entry lo, hi, row id, entries} of rows[i] (wmf_plan_create)
     if (count <= 0) return 0;
     const bool split = side != nullptr;
     const int ldv = it_ldv(f, ld, split);
-#define IT_GO(NW, FPL, NS, SP, OCC)                                                                                                      \
-    do {                                                                                                                                 \
-        if (ldv == 16 * FPL) it_launch<NW, FPL, NS, SP, true, OCC>(rows, count, V, side, indptr, indices, vals, f, ld, g, bounce_rows, bounce_count, stats, info, st); \
-        else it_launch<NW, FPL, NS, SP, false, OCC>(rows, count, V, side, indptr, indices, vals, f, ld, g, bounce_rows, bounce_count, stats, info, st);            \
-    } while (0)
+    const ItPolicy pol = it_policy();
+#define IT_ONE(NW, FPL, NS, SP, FULL, OCC) \
+    it_launch<NW, FPL, NS, SP, FULL, OCC>(rows, count, V, side, indptr, indices, vals, f, ld, g, bounce_rows, bounce_count, stats, info, st)
+#define IT_GO(NW, FPL, NS, SP, OCC) do { if (ldv == 16 * FPL) IT_ONE(NW, FPL, NS, SP, true, OCC); else IT_ONE(NW, FPL, NS, SP, false, OCC); } while (0)
     if (split && ldv > 128) return -1;                            // (the split layout exists for f <= 144 only)
 #if IT_NW128 == 2
-    if (ldv == 128 && !it_env("WMF_ITER_ONE_STAGE", 0.f)) {
+    if (ldv == 128 && pol.two_stage) {
         // Stage 1: two waves per row -- half the per-row overhead of the four-wave form (exchanges, norms, vector updates are per
         // wave) and four rows in flight per CU: 11.1 against 12.2 ms on the item side of BASELINE.json's configs[2] -- at the price of
         // registers: no room for the Chebyshev recurrence's fourth vector.  What it does not solve (tau above the Neumann limit, a
@@ -831,21 +849,34 @@ int wmf_launch_iter(const int32_t* rows, int64_t count, const float* V, const fl
         return 0;
     }
 #endif
+    if constexpr (LAB) {
+        // what only the knobs reach: ldv <= 64 (WMF_ITER_MIN_LDV) and ldv = 128 in one stage (WMF_ITER_ONE_STAGE, WMF_ITER_NO_DMA)
 #if IT_DMA
-    if ((ldv == 64 || ldv == 128) && !it_env("WMF_ITER_NO_DMA", 0.f)) {
+        if ((ldv == 64 || ldv == 128) && pol.dma) {
 #define IT_GO_DMA(FPL, SP) it_launch<4, FPL, 8, SP, true, 2, true>(rows, count, V, side, indptr, indices, vals, f, ld, g, bounce_rows, bounce_count, stats, info, st)
-        if (ldv == 64) { if (split) IT_GO_DMA(4, true); else IT_GO_DMA(4, false); }
-        else { if (split) IT_GO_DMA(8, true); else IT_GO_DMA(8, false); }
+            if (ldv == 64) { if (split) IT_GO_DMA(4, true); else IT_GO_DMA(4, false); }
+            else { if (split) IT_GO_DMA(8, true); else IT_GO_DMA(8, false); }
 #undef IT_GO_DMA
-        return 0;
-    }
+            return 0;
+        }
 #endif
-    if (ldv <= 64) { if (split) IT_GO(4, 4, IT_NS64S, true, IT_OCC4S); else IT_GO(4, 4, IT_NS64, false, IT_OCC64); }
-    else if (ldv <= 128) { if (split) IT_GO(4, 8, IT_NS128S, true, IT_OCC4S); else IT_GO(4, 8, IT_NS128, false, IT_OCC4); }
+        if (ldv <= 64) { if (split) IT_GO(4, 4, IT_NS64S, true, IT_OCC4S); else IT_GO(4, 4, IT_NS64, false, IT_OCC64); return 0; }
+        if (ldv == 128) { if (split) IT_ONE(4, 8, IT_NS128S, true, true, IT_OCC4S); else IT_ONE(4, 8, IT_NS128, false, true, IT_OCC4); return 0; }
+    }
+    if (ldv <= 64 || ldv == 128) return -1;                       // (wmf_iter_dmax: no candidates at these widths without the knobs)
+    else if (ldv < 128) { if (split) IT_ONE(4, 8, IT_NS128S, true, false, IT_OCC4S); else IT_ONE(4, 8, IT_NS128, false, false, IT_OCC4); }
     else if (ldv <= 192) IT_GO(8, 12, 8, false, 2);
     else if (ldv <= 256) IT_GO(8, 16, 8, false, 2);
     else if (ldv <= 320) IT_GO(8, 20, 6, false, 2);
     else return -1;
 #undef IT_GO
+#undef IT_ONE
     return 0;
+}
+
+int wmf_launch_iter(const int32_t* rows, int64_t count, const float* V, const float* side, const int64_t* indptr,
+                    const int32_t* indices, const float* vals, int f, int ld, float* g, int32_t* bounce_rows,
+                    int32_t* bounce_count, unsigned long long* stats, const void* info, hipStream_t st, int lsb) {
+    return launch_iter<WMF_LAB_BUILD>(rows, count, V, side, indptr, indices, vals, f, ld, g, bounce_rows, bounce_count, stats,
+                                      static_cast<const int4*>(info), st, lsb);
 }

@@ -380,7 +380,7 @@ __device__ __forceinline__ void rs_body(float* __restrict__ sm, const int32_t* _
                 const float* vb = Vs + (c & 1) * (C::RC * C::LDV);
                 const float* wb = wsm + (c & 1) * C::RC;
                 const float* pb = psm + (c & 1) * C::RC;
-                const int nsteps = WMF_ABL(dbg, 2) ? 0 : (nrow + 3) >> 2;  // dbg: timing ablations (wmf_debug_set_flags)
+                const int nsteps = WMF_ABL(dbg, WMF_DBG_NO_ACCUMULATION) ? 0 : (nrow + 3) >> 2;  // dbg: timing ablations (wmf_debug_set_flags)
                 for (int ks = 0; ks < nsteps; ++ks) {
                     const float wq = wb[4 * ks + q], pq = pb[4 * ks + q];
                     const float* vrow = vb + (4 * ks + q) * C::LDV + r;
@@ -498,7 +498,7 @@ __device__ __forceinline__ void rs_body(float* __restrict__ sm, const int32_t* _
             }
             (void)p;
         };
-        if (!WMF_ABL(dbg, 1)) {
+        if (!WMF_ABL(dbg, WMF_DBG_NO_ELIMINATION)) {
 #pragma unroll 1
             for (int p = 0; p < NFB; ++p) {
                 float* P1 = Pan;                                 // originals of block row p
@@ -682,13 +682,16 @@ static void launch_rowsplit_nfb(const wmf_plan* pl, const float* V, const float*
                                 const int32_t* indices, const float* vals, int f, int ld, float* g, hipStream_t st) {
     const int32_t* rows = pl->rows[WMF_BIN_GENERAL];
     const int64_t normal = pl->count[WMF_BIN_GENERAL] - pl->heavy_count;
-    // split-f16 accumulation and elimination (debug flag 2097152: the f32 MFMA kernel it replaces; that one does not split rows)
-    if (wmf_debug_flags & 2097152) {
-        launch_rowsplit_f<NFB, BORDER, false, 0>(rows, pl->count[WMF_BIN_GENERAL], V, biasv, indptr, indices, vals, f, ld, g, pl, st);
-        return;
+    // split-f16 accumulation and elimination (WMF_DBG_WIDE_F32, 2097152, in lab builds: the f32 MFMA kernel it replaces; that one
+    // does not split rows)
+    if constexpr (WMF_LAB_BUILD) {
+        if (wmf_debug_flags & WMF_DBG_WIDE_F32) {
+            launch_rowsplit_f<NFB, BORDER, false, 0>(rows, pl->count[WMF_BIN_GENERAL], V, biasv, indptr, indices, vals, f, ld, g, pl, st);
+            return;
+        }
     }
     // ROUND 4: the first iter_count of the normal rows go to the matrix-free iteration kernel (wmf_iter.hip), which hands back what
-    // it does not solve as a device-side list (as in wmf_directw.hip); debug flag 268435456: off
+    // it does not solve as a device-side list (as in wmf_directw.hip); WMF_DBG_NO_ITER: off
     const int64_t n_iter = biasv ? 0 : wmf_iter_rows(pl, f, ld, false);      // (biasv: always folded into vals by wmf_launch_solve)
     if (n_iter > 0)
         (void)wmf_launch_iter(rows, n_iter, V, nullptr, indptr, indices, vals, f, ld, g, pl->iter_bounce_rows, pl->fallback_count + 1,

@@ -740,11 +740,11 @@ static void launch_low(const wmf_plan* pl, const float* V, const float* biasv, i
                        const int32_t* indices, const float* vals, int ld, int last1, float* g, hipStream_t st) {
     const int64_t c0 = pl->count[WMF_BIN_LOW16], c1 = pl->count[WMF_BIN_LOW32];
     // rows with at most 8 entries come first in the bin and go two per wave (solve_pair_kernel)
-    const int64_t c8 = (wmf_debug_flags & 2048) ? 0 : pl->count8;
+    const int64_t c8 = (wmf_debug_flags & WMF_DBG_NO_ROW_PAIRS) ? 0 : pl->count8;
     // split-f16 S tiles (X6, solve_low_kernel) where the row is whole 32-feature chunks, or those and one more piece
-    // (debug flag 524288: f32 MFMAs everywhere)
+    // (WMF_DBG_LOW_F32_TILES, 524288: f32 MFMAs everywhere)
     constexpr bool X6_OK = (NCH % 2 == 0) || (NCH >= 3);
-    const bool x6 = X6_OK && !(wmf_debug_flags & 524288) && ((NCH % 2 == 0) ? (ld % 32 == 0) : (last1 && ld == 16 * (NCH - 1) + 4));   // (last1: f = ld - 3, one feature in the last piece)
+    const bool x6 = X6_OK && !(wmf_debug_flags & WMF_DBG_LOW_F32_TILES) && ((NCH % 2 == 0) ? (ld % 32 == 0) : (last1 && ld == 16 * (NCH - 1) + 4));   // (last1: f = ld - 3, one feature in the last piece)
     if (bstride == 3 && !(x6 && NCH == 9)) bstride = 2;        // (the bias is rebuilt from the row in the X6 piece order only: elsewhere the pairs are read)
 #define WMF_LOW_LAUNCH(KERNEL, NAME, ROWS, COUNT, GRID)                                                                   \
     do {                                                                                                                  \
@@ -766,9 +766,12 @@ static void launch_low(const wmf_plan* pl, const float* V, const float* biasv, i
         if (!x6) WMF_LOW_LAUNCH((solve_low_kernel<NCH, 1, false, false>), wmf_kname("solve_low_kernel<%d, 1, false, false>", NCH), pl->rows[WMF_BIN_LOW16] + c8, c0 - c8, (c0 - c8 + 3) / 4);
     }
     if (c1 > 0) {
-        if (wmf_debug_flags & 64) {     // plain 32 x 32 Gauss-Jordan, kept for A/B timing
-            WMF_LOW_LAUNCH((solve_low_kernel<NCH, 2, false, false>), wmf_kname("solve_low_kernel<%d, 2, false, false>", NCH), pl->rows[WMF_BIN_LOW32], c1, (c1 + 3) / 4);
-        } else {
+        bool gauss_jordan = false;      // plain 32 x 32 Gauss-Jordan, kept for A/B timing in lab builds (WMF_DBG_LOW32_GAUSS_JORDAN, 64)
+        if constexpr (WMF_LAB_BUILD) {
+            gauss_jordan = (wmf_debug_flags & WMF_DBG_LOW32_GAUSS_JORDAN) != 0;
+            if (gauss_jordan) WMF_LOW_LAUNCH((solve_low_kernel<NCH, 2, false, false>), wmf_kname("solve_low_kernel<%d, 2, false, false>", NCH), pl->rows[WMF_BIN_LOW32], c1, (c1 + 3) / 4);
+        }
+        if (!gauss_jordan) {
             if constexpr (X6_OK) {
                 if (x6) WMF_LOW_LAUNCH((solve_low_kernel<NCH, 2, true, true>), wmf_kname("solve_low_kernel<%d, 2, true, true>", NCH), pl->rows[WMF_BIN_LOW32], c1, (c1 + 3) / 4);
             }
@@ -842,7 +845,7 @@ void wmf_launch_combine_segments(const wmf_plan* pl, int64_t partial_floats, hip
 
 int wmf_launch_solve(const wmf_plan* pl, const float* V, const float* biasv, const int64_t* indptr,
                      const int32_t* indices, const float* vals, int f, int ld, float* g, int32_t* fail_count,
-                     hipStream_t st) {
+                     bool rolled, hipStream_t st) {
     if (hipMemsetAsync(pl->fallback_count, 0, 3 * sizeof(int32_t), st) != hipSuccess) return -2;   // [0] pivoted fallback, [1] rows handed back by wmf_iter.hip, [2] its stage 1's hand-on list
     const int64_t nnz = pl->nnz[0] + pl->nnz[1] + pl->nnz[2] + pl->nnz[3];
     if (nnz == 0)                                                      // nothing stored: every row solves to zero
@@ -851,7 +854,7 @@ int wmf_launch_solve(const wmf_plan* pl, const float* V, const float* biasv, con
     const float* side = nullptr;
     if (biasv && wmf_split_layout(f, ld)) {                            // split layout: V is the packed body, biasv the pairs
         side = biasv;
-        bstride = (pl->rolled && f == 129) ? 3 : 2;                     // (3: wmf_solve_rows_ex(WMF_SOLVE_ROLLED): the low-row kernels rebuild the bias from the row)
+        bstride = (rolled && f == 129) ? 3 : 2;                        // (3: wmf_solve_rows_ex(WMF_SOLVE_ROLLED): the low-row kernels rebuild the bias from the row)
     } else if (biasv) {                                                // other widths: fold the biases into the weights once
         if (!pl->w_eff) return -3;                                     // (plan latched the split layout, this call is not in it)
         wmf_launch_bias_adjust(vals, indices, biasv, nnz, pl->w_eff, st);   // (w_eff: allocated by wmf_plan_create(bias = 1))
@@ -865,20 +868,20 @@ int wmf_launch_solve(const wmf_plan* pl, const float* V, const float* biasv, con
         default: return -1;
     }
     const bool general_ok = f <= 144;
-    if (pl->count[WMF_BIN_MFMA] > 0 && (wmf_debug_flags & 33554432)) {
-        // debug flag 33554432 (accuracy experiments): every row of this bin through the pivoted float32 LU kernel
+    if (pl->count[WMF_BIN_MFMA] > 0 && (wmf_debug_flags & WMF_DBG_HEAVY_PIVOTED_LU)) {
+        // WMF_DBG_HEAVY_PIVOTED_LU, 33554432 (accuracy experiments, lab builds): every row of this bin through the pivoted float32 LU kernel
         if (dispatch_general(pl->rows[WMF_BIN_MFMA], pl->count[WMF_BIN_MFMA], nullptr, 256, V, biasv, bstride, indptr, indices, vals, f, ld,
                              g, fail_count, st)) return -1;
     } else if (pl->count[WMF_BIN_MFMA] > 0) {
         // one wave per row with the whole system in MFMA accumulator registers (wmf_directw.hip, wmf_directl.hip)
-        if (wmf_launch_directw(pl, V, side, indptr, indices, vals, f, ld, g, st)) return -1;
+        if (wmf_launch_directw(pl, V, side, indptr, indices, vals, f, ld, g, rolled, st)) return -1;
     }
     if (pl->count[WMF_BIN_GENERAL] > 0) {
         // f > 144: rows with more than 32 entries go to the workgroup-per-row kernel (wmf_wide.hip)
         if (!wmf_wide_supported(f)) return -1;
-        // f <= 256: four waves per row, tiles owned by block row (wmf_rowsplit.hip); f = 257 .. 272, or debug flag
-        // 1024: the run-time-indexed eight-wave kernel (wmf_wide.hip)
-        if (wmf_rowsplit_supported(f) && !(wmf_debug_flags & 1024)) {
+        // f <= 256: four waves per row, tiles owned by block row (wmf_rowsplit.hip); f = 257 .. 272, or
+        // WMF_DBG_WIDE_EIGHT_WAVES (1024, lab builds): the run-time-indexed eight-wave kernel (wmf_wide.hip)
+        if (wmf_rowsplit_supported(f) && !(wmf_debug_flags & WMF_DBG_WIDE_EIGHT_WAVES)) {
             if (wmf_launch_rowsplit(pl, V, biasv, indptr, indices, vals, f, ld, g, st)) return -1;
         } else {
             // (f = 258 .. 272: no split rows; the iteration kernel first, as in wmf_directw.hip / wmf_rowsplit.hip)

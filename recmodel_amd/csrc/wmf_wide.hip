@@ -133,7 +133,7 @@ __global__ __launch_bounds__(512, 1) void solve_wide_kernel(const int32_t* __res
             __syncthreads();
             if (c + 2 < nchunks) load_chunk(pre, wpre, lo, d, base + 2 * C::RC);
             else if (itn < count) load_chunk(pre, wpre, lon, dn, slot * C::RC);
-            const int nsteps = WMF_ABL(dbg, 2) ? 0 : (nrow + 3) >> 2;           // dbg: timing ablations (wmf_debug_set_flags)
+            const int nsteps = WMF_ABL(dbg, WMF_DBG_NO_ACCUMULATION) ? 0 : (nrow + 3) >> 2;           // dbg: timing ablations (wmf_debug_set_flags)
             for (int s = 0; s < nsteps; ++s) {
                 const float wq = wsm[4 * s + q];
                 const float pb = (r == 0) ? psm[4 * s + q] : 0.f;          // rhs tile: p in column 0
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(512, 1) void solve_wide_kernel(const int32_t* __res
 #pragma unroll
         for (int kq = 0; kq < 4; ++kq) baddr[kq] = (r + 16 * kq) * 4;
 #pragma unroll 1
-        for (int p = 0; p < (WMF_ABL(dbg, 1) ? 0 : NFB); ++p) {
+        for (int p = 0; p < (WMF_ABL(dbg, WMF_DBG_NO_ELIMINATION) ? 0 : NFB); ++p) {
             // (a) the wave that owns tile (p, p) inverts it in registers: a symmetric tile in accumulator layout is
             //     the row-distributed layout of the Gauss-Jordan sweep (wmf_common.h), 16 DPP steps, no other wave waits
             //     on a serial Cholesky.  X goes to T[p] as [row][col] for everybody's A operand.
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(512, 1) void solve_wide_kernel(const int32_t* __res
         // ---- D. g_p = w_p - sum_{j > p} W_pj g_j, column by column: once g_p is final every tile (i, p), i < p, takes
         //      its product out of z_i -- one tile, hence one writer, per block i and step
 #pragma unroll 1
-        for (int p = (WMF_ABL(dbg, 1) ? -1 : NFB - 1); p >= 0; --p) {
+        for (int p = (WMF_ABL(dbg, WMF_DBG_NO_ELIMINATION) ? -1 : NFB - 1); p >= 0; --p) {
             const float gp = zb[16 * p + r];                     // final: all columns j > p have been taken out
 #pragma unroll
             for (int a = 0; a < C::NACC; ++a) {

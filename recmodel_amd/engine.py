@@ -996,8 +996,11 @@ class AlsEngine:
         for c in range(len(self.chunk_bounds[side])):
             self._publish(side, c)
 
-    iter_on = True      # the matrix-free iteration kernel (csrc/wmf_iter.hip) is part of the solve; tools that switch it off with
-                        # wmf_debug_set_flags(268435456) set this to False for bench.py's byte model
+    @property
+    def iter_on(self):
+        """The matrix-free iteration kernel (csrc/wmf_iter.hip) is part of the solve unless WMF_DBG_NO_ITER is set: read from the
+        library, so bench.py's byte model prices the solve that runs."""
+        return not (_lib.load().wmf_debug_get_flags() & _lib.DEBUG_FLAGS["WMF_DBG_NO_ITER"])
 
     def iter_stats(self, side):
         """(rows solved by the matrix-free iteration, rows it handed back to the elimination kernels, applications of the row

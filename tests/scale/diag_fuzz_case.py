@@ -42,7 +42,7 @@ import os
 if os.environ.get("DIAG_FLAGS"):
     from recmodel_amd import _lib
     lib = _lib.load()
-    lib.wmf_debug_set_flags(int(os.environ["DIAG_FLAGS"]))
+    _lib.check(lib.wmf_debug_set_flags(_lib.parse_debug_flags(os.environ["DIAG_FLAGS"])))    # a number or names: NO_ITER|F64_VALU
     got3 = (model.recompute_factors_bias if bias else model.recompute_factors)(Y, C, 0.1).astype(np.float64)
     got4 = (model.recompute_factors_bias if bias else model.recompute_factors)(Y, C, 0.1).astype(np.float64)
     print("with debug flags: run-to-run rows that differ", int((np.abs(got4 - got3).max(axis=1) > 0).sum()))

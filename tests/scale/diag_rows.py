@@ -7,8 +7,8 @@ from oracle import wmf_oracle as orc
 from test_gpu_parity import ragged_matrix, as_f64
 from recmodel_amd import WMF, _lib
 k, bias = int(sys.argv[1]), bool(int(sys.argv[2]))
-flags = int(sys.argv[3]) if len(sys.argv) > 3 else 0
-lib = _lib.load(); lib.wmf_debug_set_flags(flags)
+flags = _lib.parse_debug_flags(sys.argv[3]) if len(sys.argv) > 3 else 0      # a number or names: NO_ITER|HEAVY_REG_RING
+lib = _lib.load(); _lib.check(lib.wmf_debug_set_flags(flags))
 n, m_items = 2500, 600
 C = ragged_matrix(n, m_items, seed=k + bias)
 model = WMF(num_items=m_items, num_users=n, dim=k, gamma=0.1, weighted=True, bias=bias)

@@ -35,8 +35,10 @@ if bias:
 G = Yt.T @ Yt + 0.1 * np.eye(Y.shape[1])
 Linv = np.linalg.inv(np.linalg.cholesky(G))
 out = {}
-for fl, name in ((0, "default"), (4096, "f32 register ring"), (33554432, "pivoted LU")):
-    lib.wmf_debug_set_flags(fl)
+# (the pivoted LU for every row is a lab switch: WMF_HIP_LIB=build/lab/libwmf_hip_lab.so, or the library refuses it here)
+for fl, name in ((0, "default"), (_lib.DEBUG_FLAGS["WMF_DBG_HEAVY_REG_RING"], "f32 register ring"),
+                 (_lib.DEBUG_FLAGS["WMF_DBG_HEAVY_PIVOTED_LU"], "pivoted LU")):
+    _lib.check(lib.wmf_debug_set_flags(fl))
     got = step_g(Y, C, 0.1).astype(np.float64)
     lib.wmf_debug_set_flags(0)
     out[name] = np.linalg.norm(got - want, axis=1) / den

@@ -75,6 +75,103 @@ def test_pure_host_entry_points(lib):
     assert lib.wmf_whitened_row_floats(129, 132, 0) == 132
 
 
+CSRC = os.path.join(ROOT, "recmodel_amd", "csrc")
+
+
+def header_debug_flags():
+    """{name: (value, lab only)} of the WMF_DBG_* enum of include/wmf_hip.h: one constant per line, `lab` the first word of its comment."""
+    rows = re.findall(r"^\s*(WMF_DBG_\w+)\s*=\s*(\d+),?\s*/\*\s*(lab\b)?", open(HEADER).read(), flags=re.M)
+    assert len(rows) == len({name for name, _, _ in rows})
+    return {name: (int(value), bool(lab)) for name, value, lab in rows}
+
+
+def test_debug_flag_table_is_one_table():
+    """The header's enum, the dict of recmodel_amd/_lib.py and the mask the shipped library accepts (wmf_internal.h) name the
+    same switches; every one is a single bit; every switch the shipped library accepts is set by a GPU test."""
+    import glob
+    from recmodel_amd import _lib
+    table = header_debug_flags()
+    assert len(table) >= 21
+    assert {name: value for name, (value, _) in table.items()} == _lib.DEBUG_FLAGS
+    assert all(value & (value - 1) == 0 for value in _lib.DEBUG_FLAGS.values())
+    assert len(set(_lib.DEBUG_FLAGS.values())) == len(_lib.DEBUG_FLAGS) and 512 not in _lib.DEBUG_FLAGS.values()
+    shipped = sorted(name for name, (_, lab) in table.items() if not lab)
+    assert shipped == sorted(_lib.SHIPPED_DEBUG_FLAGS) and len(shipped) == 6
+    internal = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, "wmf_internal.h")).read())
+    masks = {m.group(1): sorted(re.findall(r"WMF_DBG_\w+", m.group(2)))
+             for m in re.finditer(r"constexpr int (WMF_DBG_SHIPPED|WMF_DBG_LAB) =([^;]*);", internal)}
+    assert masks["WMF_DBG_SHIPPED"] == shipped
+    assert masks["WMF_DBG_LAB"] == sorted(name for name, (_, lab) in table.items() if lab)
+    gpu_tests = "".join(open(path).read() for path in glob.glob(os.path.join(ROOT, "tests", "test_gpu_*.py")))
+    for name in shipped:
+        assert re.search(r"\b%s\b" % name, gpu_tests), f"{name} is accepted by the shipped library, but no tests/test_gpu_*.py sets it"
+
+
+def test_no_magic_switch_numbers_in_csrc():
+    """No decimal literal is tested against the switches any more: the names of include/wmf_hip.h only."""
+    for fn in sorted(os.listdir(CSRC)):
+        if not fn.endswith((".hip", ".h")):
+            continue
+        text = open(os.path.join(CSRC, fn)).read()
+        for pattern in (r"(wmf_debug_flags|dbg)\s*&\s*\(?\s*~?\s*\d", r"WMF_ABL\(\w+,\s*\d"):
+            found = re.search(pattern, text)
+            assert not found, f"{fn}: {found.group(0)!r}"
+
+
+def test_shipped_library_accepts_the_tested_switches_only(lib):
+    from recmodel_amd import _lib
+    assert os.path.basename(_lib.LIB_PATH) == "libwmf_hip.so"                    # (not a lab build selected by WMF_HIP_LIB)
+    try:
+        for name, value in _lib.DEBUG_FLAGS.items():
+            if name in _lib.SHIPPED_DEBUG_FLAGS:
+                assert lib.wmf_debug_set_flags(value) == 0, name
+                assert lib.wmf_debug_get_flags() == value
+            else:
+                before = lib.wmf_debug_get_flags()
+                assert lib.wmf_debug_set_flags(value) == _lib.WMF_EINVAL, name
+                assert lib.wmf_debug_set_flags(value | _lib.DEBUG_FLAGS["WMF_DBG_NO_ITER"]) == _lib.WMF_EINVAL, name
+                assert lib.wmf_debug_get_flags() == before                        # a refused call changes nothing
+        for value in (512, 4, 16, 32, 128, 16384, 1 << 20, -1):                  # 512: reserved; the others were never switches
+            assert lib.wmf_debug_set_flags(value) == _lib.WMF_EINVAL, value
+        everything = sum(_lib.DEBUG_FLAGS[name] for name in _lib.SHIPPED_DEBUG_FLAGS)
+        assert lib.wmf_debug_set_flags(everything) == 0 and lib.wmf_debug_get_flags() == everything
+    finally:
+        assert lib.wmf_debug_set_flags(0) == 0
+    assert lib.wmf_debug_get_flags() == 0
+
+
+def test_debug_flag_names_parse():
+    from recmodel_amd import _lib
+    assert _lib.parse_debug_flags("268435456") == _lib.parse_debug_flags("WMF_DBG_NO_ITER") == _lib.parse_debug_flags("NO_ITER") == 268435456
+    assert _lib.parse_debug_flags("NO_ITER|F64_VALU") == 268435456 | 536870912
+    assert _lib.parse_debug_flags("0x1000 | 131072") == 4096 | 131072 and _lib.parse_debug_flags("0") == 0
+    with pytest.raises(ValueError):
+        _lib.parse_debug_flags("NO_SUCH_SWITCH")
+
+
+def test_shipped_library_reads_no_environment(lib):
+    """The policy of the matrix-free iteration (csrc/wmf_iter.hip) is compiled in: the shipped library does not import getenv."""
+    from recmodel_amd import _lib
+    out = subprocess.run(["nm", "-D", "--undefined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    symbols = {line.split()[-1].split("@")[0] for line in out.splitlines() if line.strip()}
+    assert "hipLaunchKernel" in symbols or any(s.startswith("hip") for s in symbols)   # (the listing is not empty)
+    assert "getenv" not in symbols and "secure_getenv" not in symbols
+
+
+def test_iter_on_follows_the_switch(lib):
+    """AlsEngine.iter_on, which the benchmark's byte model reads, is the library's switch and not a constant."""
+    from recmodel_amd import _lib
+    from recmodel_amd.engine import AlsEngine
+    assert isinstance(AlsEngine.__dict__["iter_on"], property)
+    read = AlsEngine.__dict__["iter_on"].fget
+    try:
+        assert read(None) is True
+        assert lib.wmf_debug_set_flags(_lib.DEBUG_FLAGS["WMF_DBG_NO_ITER"]) == 0
+        assert read(None) is False
+    finally:
+        lib.wmf_debug_set_flags(0)
+
+
 def test_argument_validation_without_gpu(lib):
     from recmodel_amd import _lib
     dummy = ctypes.c_void_p(16)

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from conftest import record_error
+from recmodel_amd._lib import DEBUG_FLAGS
 
 pytestmark = pytest.mark.gpu
 
@@ -27,7 +28,7 @@ M_EDGES = (1, 3, 4, 5, 15, 16, 17, 31, 32, 33, 127, 128, 129, 1234)
 WIDTHS = sorted({f for n in range(1, 18) for f in (16 * n - 15, 16 * n - 6, 16 * n) if f <= WMF_MAX_F} | {258, 259, 260})
 SPLIT_WIDTHS = (17, 33, 65, 81, 97, 129)
 assert set(SPLIT_WIDTHS) <= set(WIDTHS) and {(f + 15) // 16 for f in WIDTHS} == set(range(1, 18))
-F32_GRAM = 131072                                                 # wmf_debug_set_flags: the f32-MFMA Gramian for NFB 7 .. 9
+F32_GRAM = DEBUG_FLAGS["WMF_DBG_F32_GRAM"]                        # wmf_debug_set_flags: the f32-MFMA Gramian for NFB 7 .. 9
 
 
 def _big_m(f):

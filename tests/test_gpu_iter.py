@@ -124,7 +124,7 @@ def test_iteration_with_negative_weights():
 
 
 def test_iteration_off_gives_the_same_rows():
-    """Debug flag 268435456 sends every row to the elimination kernels: the two solvers must agree to float32 rounding on rows
+    """WMF_DBG_NO_ITER (268435456) sends every row to the elimination kernels: the two solvers must agree to float32 rounding on rows
     the iteration solves (cfg3-like shape, scaled down)."""
     from recmodel_amd import _lib
     eng, indptr, indices, w, Y = _engine(4000, 300_000, 128, True, 33, 128, 0.5, seed=11)
@@ -132,7 +132,7 @@ def test_iteration_off_gives_the_same_rows():
     a = eng.get_factors("users").copy()
     lib = _lib.load()
     try:
-        lib.wmf_debug_set_flags(268435456)
+        lib.wmf_debug_set_flags(_lib.DEBUG_FLAGS["WMF_DBG_NO_ITER"])
         eng.half_step("users")
     finally:
         lib.wmf_debug_set_flags(0)
@@ -181,8 +181,8 @@ def test_float64_iteration_against_the_float64_oracle(k, bias):
     """The float64 form of the iteration (csrc/wmf_iter64.hip, inside wmf_half_step_f64 -- the reference's cores > 1 variants,
     wmf_model.py:242-309): rows of 1 .. 32 entries (one wave per row) and of 33 .. 256 / 192 / 144 entries (four waves)
     against a LARGE fixed side, so that tr E is small and the series runs; 1e-10 of oracle.solve_row like every float64 test, and
-    the same rows with the iteration switched off (debug flag 268435456: blocked Cholesky / low-rank kernels) agree to 1e-12, and so
-    do the matrix-core forms of the Gramian and the row transform with their VALU forms (debug flag 536870912)."""
+    the same rows with the iteration switched off (WMF_DBG_NO_ITER: blocked Cholesky / low-rank kernels) agree to 1e-12, and so
+    do the matrix-core forms of the Gramian and the row transform with their VALU forms (WMF_DBG_F64_VALU)."""
     from recmodel_amd import _lib
     from recmodel_amd.engine import HipKernels
     f = k + int(bias)
@@ -205,7 +205,7 @@ def test_float64_iteration_against_the_float64_oracle(k, bias):
     fail = torch.zeros(4, dtype=torch.int32, device=dev)
     outs = []
     lib = _lib.load()
-    for flags in (0, 268435456, 536870912):
+    for flags in (0, _lib.DEBUG_FLAGS["WMF_DBG_NO_ITER"], _lib.DEBUG_FLAGS["WMF_DBG_F64_VALU"]):
         out = torch.empty(n_rows, f, dtype=torch.float64, device=dev)
         try:
             lib.wmf_debug_set_flags(flags)

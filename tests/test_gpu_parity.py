@@ -327,7 +327,7 @@ def test_many_heavy_rows_per_wave_at_k128(WMF, bias):
     """More heavy rows than resident waves (8000 against 3072), 33 .. 400 entries each, k = 128: every wave of the LDS-DMA
     kernel walks several rows -- next row's metadata requested during the last group, its first rows during the elimination,
     the metadata buffers rotating across rows -- and must give what the ORACLE gives for every one of the 8000 rows (float64
-    restatement of wmf_model.py:220-239 / :337-350), what the register-ring f32 kernel (debug flag 4096) gives, row by row,
+    restatement of wmf_model.py:220-239 / :337-350), what the register-ring f32 kernel (WMF_DBG_HEAVY_REG_RING) gives, row by row,
     and satisfy the rows' own normal equations in float64."""
     from recmodel_amd import _lib
     lib = _lib.load()
@@ -345,7 +345,7 @@ def test_many_heavy_rows_per_wave_at_k128(WMF, bias):
         Y[:, 0] *= 0.5                                                 # weights stay positive: the SPD kernels are used
     step = model.recompute_factors_bias if bias else model.recompute_factors
     try:
-        lib.wmf_debug_set_flags(4096)
+        lib.wmf_debug_set_flags(_lib.DEBUG_FLAGS["WMF_DBG_HEAVY_REG_RING"])
         ref = step(Y, C, 0.1).astype(np.float64)
     finally:
         lib.wmf_debug_set_flags(0)
@@ -354,7 +354,7 @@ def test_many_heavy_rows_per_wave_at_k128(WMF, bias):
     rel_o, zero_abs = worst_row(got, want)
     assert fro(got, want) <= HALF_FRO and rel_o <= HALF_ROW and zero_abs == 0.0, (fro(got, want), rel_o)
     try:                                                               # the one-wave-per-SIMD variant (16-entry groups)
-        lib.wmf_debug_set_flags(16777216)
+        lib.wmf_debug_set_flags(_lib.DEBUG_FLAGS["WMF_DBG_HEAVY_ONE_WAVE"])
         got8 = step(Y, C, 0.1).astype(np.float64)
     finally:
         lib.wmf_debug_set_flags(0)
@@ -557,8 +557,8 @@ def test_float64_half_step_all_degree_classes(WMF, k, bias):
     from recmodel_amd import _lib
     lib = _lib.load()
     # rows with 1 .. 32 entries through the whitened low-rank form (most rows here, so it is on), then every row through the
-    # direct f x f kernel (debug flag 134217728)
-    for flags in (0, 134217728):
+    # direct f x f kernel (WMF_DBG_F64_NO_LOW_RANK)
+    for flags in (0, _lib.DEBUG_FLAGS["WMF_DBG_F64_NO_LOW_RANK"]):
         try:
             lib.wmf_debug_set_flags(flags)
             got = fn(Y, C, 0.1)

@@ -2,13 +2,16 @@
 some time after the instruction issues; hipcc believes they are written at once.  Between each such read and the
 inline-asm `s_waitcnt lgkmcnt(0)` that retires it nothing may touch those registers (a copy the register allocator
 inserts there would copy stale data).  Parses the gfx950 assembly of the file and reports violations.
-Usage: python tools/check_inflight_regs.py [path/to/wmf_directl.hip] [extra compiler flags ...]
+Usage: python tools/check_inflight_regs.py [path/to/wmf_directl.hip] [--known-bad=REGEX] [extra compiler flags ...]
+--known-bad: kernels whose mangled name matches are scanned and counted, but do not fail the check (the lab build's f32-accumulation
+variants of solve_directl_kernel, which have a statically possible path around a wait: the reason they are not shipped).
 Run by recmodel_amd/csrc/Makefile on the flags of the build itself (a violation fails the build).  Since round 3 the scan
 follows the control flow of every kernel (both successors of a conditional branch), not the text order of the assembly."""
 import re, subprocess, sys, os, tempfile
 
 src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(__file__), "..", "recmodel_amd", "csrc", "wmf_directl.hip")
-extra = sys.argv[2:]
+extra = [a for a in sys.argv[2:] if not a.startswith("--known-bad=")]
+known_bad = [re.compile(a.split("=", 1)[1]) for a in sys.argv[2:] if a.startswith("--known-bad=")]
 out = os.path.join(tempfile.mkdtemp(prefix="wmf_inflight_"), "wmf_directl_check.s")
 subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", *extra, "-S",
                 "--cuda-device-only", "-o", out, src], check=True, stderr=subprocess.DEVNULL)
@@ -90,7 +93,9 @@ def touched_by(code, inflight_regs):
 
 bad_lines = {}
 reads_seen = set()
+tolerated = 0
 for fn in parse_functions(lines):
+    found_before = len(bad_lines)
     ins, labels = fn["ins"], fn["labels"]
     # is instruction i inside an inline-asm region?  (regions do not span branches: computed in text order)
     in_asm_at, flag = [], False
@@ -144,7 +149,13 @@ for fn in parse_functions(lines):
                 if m_br.group(1) == "s_branch":
                     break
             pc += 1
+    if any(p.search(fn["name"]) for p in known_bad) and len(bad_lines) > found_before:
+        mine = [n for n, text in bad_lines.items() if text.startswith(fn["name"] + ":")]
+        print(f"{fn['name']}: {len(mine)} violations in a kernel listed as known bad (not shipped)")
+        tolerated += len(mine)
+        for n in mine:
+            del bad_lines[n]
 for n in sorted(bad_lines):
     print(bad_lines[n])
-print(f"{len(reads_seen)} inline-asm ds_reads checked, {len(bad_lines)} violations")
+print(f"{len(reads_seen)} inline-asm ds_reads checked, {len(bad_lines)} violations" + (f" ({tolerated} more in known-bad kernels)" if tolerated else ""))
 sys.exit(1 if bad_lines else 0)

@@ -1,7 +1,8 @@
 """Full-scale cross-check of the heavy-row kernels (not a test): one half step of a bench configuration's side, solved by
 every variant the debug flags select, ALL rows compared against the first (row-wise relative difference).  Catches what a
 sample of rows cannot: a rare race between consecutive rows of one wave.
-Usage: python tools/compare_heavy_variants.py cfg3 items 0,4096 [repeats]   (8192, the f32-MFMA accumulation, needs a -DWMF_LAB build)"""
+Usage: python tools/compare_heavy_variants.py cfg3 items 0,HEAVY_REG_RING [repeats]   (numbers or names of recmodel_amd/_lib.py DEBUG_FLAGS;
+HEAVY_F32_ACC, the f32-MFMA accumulation, needs the lab build: WMF_HIP_LIB=build/lab/libwmf_hip_lab.so)"""
 import ctypes, sys
 import numpy as np, torch
 sys.path.insert(0, '.')
@@ -10,7 +11,7 @@ from recmodel_amd.engine import AlsEngine, _ptr, _stream
 
 cfg = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
 side = sys.argv[2] if len(sys.argv) > 2 else "items"
-flags = [int(x) for x in (sys.argv[3] if len(sys.argv) > 3 else "0,4096").split(",")]
+flags = [_lib.parse_debug_flags(x) for x in (sys.argv[3] if len(sys.argv) > 3 else "0,HEAVY_REG_RING").split(",")]
 reps = int(sys.argv[4]) if len(sys.argv) > 4 else 2
 lib = _lib.load()
 n_users, n_items, dbar, k, bias = synth.CONFIGS[cfg]
@@ -26,7 +27,7 @@ c = eng.csr[side]
 ref = None
 for fl in flags:
     for rep in range(reps):
-        lib.wmf_debug_set_flags(fl)
+        _lib.check(lib.wmf_debug_set_flags(fl))
         eng.g[side].fill_(7.0)
         _lib.check(lib.wmf_solve_rows(c._plan, _ptr(eng.V[fixed]), _ptr(eng.bias_vec[fixed]) if bias else None, _ptr(c.indptr),
                                       _ptr(c.indices), _ptr(c.values), c.n_rows, eng.f, eng.ld, _ptr(eng.g[side]), _ptr(eng.fail), _stream()))

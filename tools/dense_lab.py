@@ -1,5 +1,6 @@
 """Timing lab for the dense shared-work kernels on a real GPU (not a test): Gramian and row transform of an [m, f] factor
-block.  Usage: python tools/dense_lab.py m k bias reps [flags,...]"""
+block.  Usage: python tools/dense_lab.py m k bias reps [flags,...]
+(flags: numbers or names, e.g. 0,F32_GRAM; recmodel_amd/_lib.py DEBUG_FLAGS)"""
 import sys
 import torch
 sys.path.insert(0, '.')
@@ -10,7 +11,7 @@ m = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
 k = int(sys.argv[2]) if len(sys.argv) > 2 else 128
 bias = int(sys.argv[3]) if len(sys.argv) > 3 else 1
 reps = int(sys.argv[4]) if len(sys.argv) > 4 else 5
-flags = [int(x) for x in (sys.argv[5] if len(sys.argv) > 5 else "0").split(",")]
+flags = [_lib.parse_debug_flags(x) for x in (sys.argv[5] if len(sys.argv) > 5 else "0").split(",")]
 lib = _lib.load()
 K = HipKernels()
 f = k + (2 if bias else 0) - (1 if bias else 0)            # the engine's f: k + 1 with biases
@@ -28,7 +29,7 @@ pairs = torch.empty(m, 2, device=dev) if (bias and ldv != ld) else torch.empty(m
 out2 = torch.empty(m, ld, device=dev)
 Gref = None
 for fl in flags:
-    lib.wmf_debug_set_flags(fl)
+    _lib.check(lib.wmf_debug_set_flags(fl))
     lib.wmf_profile_enable(0)
     K.gram(X, m, f, ld, bias, G, ws)
     K.row_transform(X, m, f, ld, W, bias, V, pairs if bias else None)

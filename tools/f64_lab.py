@@ -9,7 +9,7 @@ from recmodel_amd import _lib
 cfg = sys.argv[1] if len(sys.argv) > 1 else "cfg2"
 lib = _lib.load()
 if len(sys.argv) > 2:
-    lib.wmf_debug_set_flags(int(sys.argv[2]))
+    _lib.check(lib.wmf_debug_set_flags(_lib.parse_debug_flags(sys.argv[2])))       # a number or names: NO_ITER|F64_VALU
 dev = torch.device("cuda:0")
 lib.wmf_profile_reset()
 lib.wmf_profile_enable(1)

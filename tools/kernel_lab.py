@@ -1,6 +1,7 @@
 """Timing lab for the row-solve kernels on a real GPU (not a test): builds a cfg-shaped matrix,
 prepares whitened factors once and times wmf_solve_rows per kernel slot, optionally under the
-ablation flags of wmf_debug_set_flags.  Usage: python tools/kernel_lab.py cfg2 items 0,1,2,4,8"""
+switches of wmf_debug_set_flags (numbers, or names of recmodel_amd/_lib.py DEBUG_FLAGS joined by `|`; a switch marked `lab` in
+include/wmf_hip.h needs WMF_HIP_LIB=build/lab/libwmf_hip_lab.so).  Usage: python tools/kernel_lab.py cfg2 items 0,NO_ITER,HEAVY_REG_RING"""
 import ctypes, sys
 import numpy as np, torch
 sys.path.insert(0, '.')
@@ -13,7 +14,7 @@ ZIPF = float(os.environ.get("LAB_ZIPF", "0"))          # item popularity exponen
 HIST = os.environ.get("LAB_HIST") == "1"               # print the distribution of tr E = sum_e w_e |v_e|^2 over the side's rows
 cfg = sys.argv[1] if len(sys.argv) > 1 else "cfg2"
 side = sys.argv[2] if len(sys.argv) > 2 else "items"
-flags = [int(x) for x in (sys.argv[3] if len(sys.argv) > 3 else "0").split(",")]
+flags = [_lib.parse_debug_flags(x) for x in (sys.argv[3] if len(sys.argv) > 3 else "0").split(",")]
 reps = int(sys.argv[4]) if len(sys.argv) > 4 else 5
 lib = _lib.load()
 n_users, n_items, dbar, k, bias = synth.CONFIGS[cfg]
@@ -54,7 +55,7 @@ if HIST:
               f"  share <= 0.06: {float((t <= 0.06).double().mean()):.4f}, <= 0.5: {float((t <= 0.5).double().mean()):.4f}, <= 3: {float((t <= 3).double().mean()):.4f};"
               f"  negative part max {float(tau_n[sel].max()):.3g}")
 for fl in flags:
-    lib.wmf_debug_set_flags(fl)
+    _lib.check(lib.wmf_debug_set_flags(fl))
     lib.wmf_profile_enable(0)
     for _ in range(2):
         _lib.check(lib.wmf_solve_rows_ex(c._plan, _ptr(eng.V[fixed]), _ptr(eng.bias_vec[fixed]) if bias else None, _ptr(c.indptr),

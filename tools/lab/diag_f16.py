@@ -20,7 +20,7 @@ C64, CT = ns['as_f64'](C), C.T.tocsr()
 for name, (Y, mat) in (("users", (model.items, C)), ("items", (step_o(model.items, C64, 0.1), CT))):
     want = step_o(Y, ns['as_f64'](mat), 0.1, out_dtype="float64")
     deg = np.diff(mat.indptr)
-    for flags in (0, 8192, 4096):
+    for flags in (0, _lib.DEBUG_FLAGS["WMF_DBG_HEAVY_F32_ACC"], _lib.DEBUG_FLAGS["WMF_DBG_HEAVY_REG_RING"]):   # (the lab build)
         lib.wmf_debug_set_flags(flags)
         got = step_g(Y, mat, 0.1).astype(np.float64)
         lib.wmf_debug_set_flags(0)
