@@ -41,6 +41,16 @@ static int check_launch(const char* what) {
     return WMF_OK;
 }
 
+// What a launcher answered (WmfLaunchRc), as the entry point's WMF_E* and message; `layout`: what WMF_L_LAYOUT means there
+static int launch_error(int lrc, const char* what, int f, int ld, const char* layout) {
+    switch (lrc) {
+        case WMF_L_OK: return check_launch(what);
+        case WMF_L_HIP: wmf_set_error("%s: hipMemsetAsync failed", what); return WMF_EHIP;
+        case WMF_L_LAYOUT: wmf_set_error("%s: %s", what, layout); return WMF_EINVAL;
+        default: wmf_set_error("%s: no kernel for f=%d, ld=%d", what, f, ld); return WMF_EINVAL;
+    }
+}
+
 static int check_shape(int f, int ld) {
     if (f < 1 || f > WMF_MAX_F) { wmf_set_error("factor width f=%d outside [1, %d]", f, WMF_MAX_F); return WMF_EINVAL; }
     if (ld < f || (ld & 3)) { wmf_set_error("leading dimension ld=%d must be a multiple of 4 and >= f=%d", ld, f); return WMF_EINVAL; }
@@ -74,6 +84,15 @@ const char* wmf_kname(const char* fmt, ...) {
     static std::set<std::string> names;
     std::lock_guard<std::mutex> lk(mu);
     return names.insert(buf).first->c_str();       // node-based container: the string never moves
+}
+
+WmfKName wmf_kname_pair(const char* fmt, ...) {
+    char buf[176];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    return WmfKName{wmf_kname("%s", buf), wmf_kname("%s [bounced]", buf)};
 }
 
 void wmf_prof_begin(const char* name, hipStream_t st) {
@@ -190,7 +209,7 @@ int wmf_row_transform(const float* in, int64_t m, int f, int ld, const float* W,
     if (!in || !W || !out || m < 0) { wmf_set_error("wmf_row_transform: null pointer or negative m"); return WMF_EINVAL; }
     rc = wmf_launch_transform(in, m, f, ld, W, set_col0_one, out, col0_out, (hipStream_t)stream);
     if (rc) {
-        if (rc == -3) wmf_set_error("wmf_row_transform: f=%d, ld=%d with set_col0_one writes the split layout: col0_out (float[2 m]) is required and out may not alias in", f, ld);
+        if (rc == WMF_L_LAYOUT) wmf_set_error("wmf_row_transform: f=%d, ld=%d with set_col0_one writes the split layout: col0_out (float[2 m]) is required and out may not alias in", f, ld);
         else wmf_set_error("wmf_row_transform: unsupported f=%d", f);
         return WMF_EINVAL;
     }
@@ -378,12 +397,12 @@ int wmf_solve_rows_ex(const wmf_plan* plan, const float* V, const float* bias_fi
     if (bias_fixed && !plan->bias) { wmf_set_error("wmf_solve_rows: bias_fixed given, but the plan was created with bias = 0"); return WMF_EINVAL; }
     if (plan->n != n || plan->f != f) { wmf_set_error("wmf_solve_rows: plan was built for n=%lld f=%d", (long long)plan->n, plan->f); return WMF_EINVAL; }
     if (n == 0) return WMF_OK;
-    const int lrc = wmf_launch_solve(plan, V, bias_fixed, indptr, indices, values, f, ld, g, fail_count,
-                                     (flags & WMF_SOLVE_ROLLED) != 0, (hipStream_t)stream);
-    if (lrc == -2) { wmf_set_error("wmf_solve_rows: hipMemsetAsync failed"); return WMF_EHIP; }
-    if (lrc == -3) { wmf_set_error("wmf_solve_rows: the plan was created for the split layout of the whitened factors, the call is not"); return WMF_EINVAL; }
-    if (lrc) { wmf_set_error("wmf_solve_rows: no kernel for f=%d, ld=%d", f, ld); return WMF_EINVAL; }
-    return check_launch("wmf_solve_rows");
+    RowArgs a = {};                                              // (side, bstride, the bounce list, dbg: wmf_launch_solve)
+    a.V = V; a.biasv = bias_fixed; a.indptr = indptr; a.indices = indices; a.vals = values;
+    a.f = f; a.ld = ld; a.g = g; a.fail_count = fail_count;
+    a.rolled = (flags & WMF_SOLVE_ROLLED) != 0; a.st = (hipStream_t)stream;
+    return launch_error(wmf_launch_solve(plan, a), "wmf_solve_rows", f, ld,
+                        "the plan was created for the split layout of the whitened factors, the call is not");
 }
 
 int64_t wmf_eval_workspace_bytes(void) { return (int64_t)WMF_EVAL_MAX_BLOCKS * 3 * sizeof(double); }
@@ -443,9 +462,10 @@ int wmf_accumulate_rows(const float* V, const float* bias_fixed, const int64_t* 
         wmf_launch_bias_adjust(values, indices, bias_fixed, nnz, w_eff_workspace, st);
         values = w_eff_workspace;
     }
-    {
-        if (wmf_launch_accumulate(V, side, indptr, degrees, indices, values, n, f, ld, partial, slot_stride, slot_offset, st)) { wmf_set_error("wmf_accumulate_rows: no kernel for f=%d", f); return WMF_EINVAL; }
-    }
+    RowArgs a = {};                                              // (nothing is solved or bounced here)
+    a.V = V; a.side = side; a.indptr = indptr; a.indices = indices; a.vals = values; a.f = f; a.ld = ld; a.st = st;
+    a.dbg = wmf_debug_flags & ~(WMF_DBG_NO_ELIMINATION | WMF_DBG_NO_ACCUMULATION);
+    if (wmf_launch_accumulate(a, degrees, n, partial, slot_stride, slot_offset)) { wmf_set_error("wmf_accumulate_rows: no kernel for f=%d", f); return WMF_EINVAL; }
     return check_launch("wmf_accumulate_rows");
 }
 
@@ -456,9 +476,10 @@ int wmf_eliminate_rows(float* partial, int64_t n, int32_t slots_per_row, int f, 
     if (!partial || !g || !fail_count || !scratch || n < 0 || slots_per_row < 1) { wmf_set_error("wmf_eliminate_rows: null pointer or bad size"); return WMF_EINVAL; }
     if (wmf_directw_partial_floats(f) == 0) { wmf_set_error("wmf_eliminate_rows: f=%d not supported (f <= 144)", f); return WMF_EINVAL; }
     if (n == 0) return WMF_OK;
-    {
-        if (wmf_launch_eliminate(partial, n, slots_per_row, f, ld, g, scratch, fail_count, (hipStream_t)stream)) { wmf_set_error("wmf_eliminate_rows: no kernel for f=%d", f); return WMF_EINVAL; }
-    }
+    RowArgs a = {};                                              // (the systems are read from `partial`: no factors, no CSR)
+    a.f = f; a.ld = ld; a.g = g; a.fb_rows = scratch; a.fb_count = fail_count; a.st = (hipStream_t)stream;
+    a.dbg = wmf_debug_flags & ~(WMF_DBG_NO_ELIMINATION | WMF_DBG_NO_ACCUMULATION);
+    if (wmf_launch_eliminate(a, partial, n, slots_per_row)) { wmf_set_error("wmf_eliminate_rows: no kernel for f=%d", f); return WMF_EINVAL; }
     return check_launch("wmf_eliminate_rows");
 }
 

@@ -232,7 +232,7 @@ static int launch_gram_nfb(const float* Y, int64_t m, int f, int ld, int bias, f
         if (!(wmf_debug_flags & WMF_DBG_F32_GRAM)) {          // (WMF_DBG_F32_GRAM, 131072: the f32 MFMA kernel)
             static const char* nm = wmf_kname("gram6_kernel<%d>", NFB);
             WMF_LAUNCH(nm, (gram6_kernel<NFB>), dim3(nwaves), dim3(64), 0, st, Y, m, f, ld, bias, partial, spw);
-            return 0;
+            return WMF_L_OK;
         }
     }
     if constexpr (NFB <= 9) {
@@ -242,7 +242,7 @@ static int launch_gram_nfb(const float* Y, int64_t m, int f, int ld, int bias, f
         static const char* nm = wmf_kname("gram_kernel<%d, 4>", NFB);
         WMF_LAUNCH(nm, (gram_kernel<NFB, 4>), dim3(nwaves), dim3(256), 0, st, Y, m, f, ld, bias, partial, spw);
     }
-    return 0;
+    return WMF_L_OK;
 }
 
 int wmf_gram_max_waves(int f) {            // keep the per-wave partial tiles within 64 MiB
@@ -266,19 +266,14 @@ int wmf_gram_nwaves(int64_t m, int f) {
 
 int wmf_launch_gram(const float* Y, int64_t m, int f, int ld, int bias, double* G_sum, float* partial, double* slices,
                     hipStream_t st) {
-    if (m <= 0) return hipMemsetAsync(G_sum, 0, (size_t)f * f * sizeof(double), st) == hipSuccess ? 0 : -1;
+    if (m <= 0) return hipMemsetAsync(G_sum, 0, (size_t)f * f * sizeof(double), st) == hipSuccess ? WMF_L_OK : WMF_L_NO_KERNEL;   // (reported as "unsupported f", as ever)
     const int nfb = (f + 15) / 16;
     const int nwaves = wmf_gram_nwaves(m, f);
-    switch (nfb) {
-#define C(N) case N: launch_gram_nfb<N>(Y, m, f, ld, bias, partial, nwaves, st); break;
-        C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12) C(13) C(14) C(15) C(16) C(17)
-#undef C
-        default: return -1;
-    }
+    if (const int rc = wmf_dispatch_nfb<1, 17>(nfb, [&](auto n) { return launch_gram_nfb<decltype(n)::value>(Y, m, f, ld, bias, partial, nwaves, st); })) return rc;
     WMF_LAUNCH("gram_reduce1_kernel", gram_reduce1_kernel, dim3((f * f + 255) / 256, WMF_GRAM_SLICES), dim3(256), 0, st, partial,
                nwaves, f, nfb, slices);
     WMF_LAUNCH("gram_reduce2_kernel", gram_reduce2_kernel, dim3((f * f + 255) / 256), dim3(256), 0, st, slices, f, G_sum);
-    return 0;
+    return WMF_L_OK;
 }
 
 // ------------------------------------------------------------------------------------- factorize
@@ -800,14 +795,9 @@ static void launch_transform6(const float* in, int64_t m, int f, int ld, const f
                               float* col0_out, int64_t grid, int64_t nblk, hipStream_t st) {
     constexpr size_t lds = (size_t)3 * 16 * NFB * 176 * 2;
     static_assert(lds <= 158 * 1024, "W planes do not fit LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)transform6_kernel<NFB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
     static const char* nm = wmf_kname("transform6_kernel<%d>", NFB);
-    WMF_LAUNCH(nm, (transform6_kernel<NFB>), dim3((unsigned)grid), dim3(512), lds, st, in, m, f, ld, W, set_col0_one, out,
-               col0_out, nblk);
+    WMF_LAUNCH_LDS(nm, (transform6_kernel<NFB>), lds, dim3((unsigned)grid), dim3(512), lds, st, in, m, f, ld, W, set_col0_one, out,
+                   col0_out, nblk);
 }
 
 template <int NFB, int NB0, int NBW>
@@ -815,19 +805,13 @@ static void launch_transform_slice(const float* in, int64_t m, int f, int ld, co
                                    float* col0_out, int64_t grid, int64_t nblk, hipStream_t st) {
     constexpr size_t lds = (size_t)16 * NFB * (16 * NBW + 4) * 4;
     static_assert(lds <= 150 * 1024, "slice too wide");
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)transform_kernel<NFB, true, NB0, NBW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
-        attr_set = true;
-    }
     static const char* nm = wmf_kname("transform_kernel<%d, true, %d, %d>", NFB, NB0, NBW);
-    WMF_LAUNCH(nm, (transform_kernel<NFB, true, NB0, NBW>), dim3((unsigned)grid), dim3(512), lds, st, in, m, f, ld, W,
-               set_col0_one, out, col0_out, nblk);
+    WMF_LAUNCH_LDS(nm, (transform_kernel<NFB, true, NB0, NBW>), lds, dim3((unsigned)grid), dim3(512), lds, st, in, m, f, ld, W,
+                   set_col0_one, out, col0_out, nblk);
 }
 
 template <int NFB>
-static void launch_transform_nfb(const float* in, int64_t m, int f, int ld, const float* W, int set_col0_one, float* out,
+static int launch_transform_nfb(const float* in, int64_t m, int f, int ld, const float* W, int set_col0_one, float* out,
                                  float* col0_out, hipStream_t st) {
     constexpr int KP = 16 * NFB, LDW = KP + 4;
     constexpr size_t lds = (size_t)KP * LDW * 4;
@@ -841,7 +825,7 @@ static void launch_transform_nfb(const float* in, int64_t m, int f, int ld, cons
     if constexpr (WIDE) {
         if (!WMF_LAB_BUILD || !(wmf_debug_flags & WMF_DBG_F32_TRANSFORM)) {
             launch_transform6<NFB>(in, m, f, ld, W, set_col0_one, out, col0_out, grid, nblk, st);
-            return;
+            return WMF_L_OK;
         }
     }
     if constexpr (WIDE && !WMF_LAB_BUILD) {
@@ -865,25 +849,20 @@ static void launch_transform_nfb(const float* in, int64_t m, int f, int ld, cons
         WMF_LAUNCH(nm, (transform_kernel<NFB, false>), dim3((unsigned)grid), dim3(512), 0, st, in, m, f, ld, W,
                    set_col0_one, out, col0_out, nblk);
     }
+    return WMF_L_OK;
 }
 
 int wmf_launch_transform(const float* in, int64_t m, int f, int ld, const float* W, int set_col0_one, float* out,
                          float* col0_out, hipStream_t st) {
-    if (m <= 0) return 0;
+    if (m <= 0) return WMF_L_OK;
     const int nfb = (f + 15) / 16;
     // set_col0_one == 2 inside the kernels: the split layout (wmf_internal.h) -- `out` is the packed body, col0_out the pairs;
     // 3 / 4 (callers' values, wmf_rolled_layout_supported): the rolled coordinates, transform6_kernel only
     if (set_col0_one == 3 || set_col0_one == 4) {
-        if (!wmf_rolled_layout(f, ld)) return -1;
+        if (!wmf_rolled_layout(f, ld)) return WMF_L_NO_KERNEL;
     } else {
         set_col0_one = set_col0_one ? (wmf_split_layout(f, ld) ? 2 : 1) : 0;
     }
-    if ((set_col0_one == 2 || set_col0_one == 3) && (!col0_out || in == out)) return -3;
-    switch (nfb) {
-#define C(N) case N: launch_transform_nfb<N>(in, m, f, ld, W, set_col0_one, out, col0_out, st); break;
-        C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12) C(13) C(14) C(15) C(16) C(17)
-#undef C
-        default: return -1;
-    }
-    return 0;
+    if ((set_col0_one == 2 || set_col0_one == 3) && (!col0_out || in == out)) return WMF_L_LAYOUT;
+    return wmf_dispatch_nfb<1, 17>(nfb, [&](auto n) { return launch_transform_nfb<decltype(n)::value>(in, m, f, ld, W, set_col0_one, out, col0_out, st); });
 }

@@ -567,35 +567,36 @@ int wmf_directl_supported(int f, int ld) {
     return (f == 128 && ld == 128) || (f == 129 && ld == 132) || (f == 64 && ld == 64) || (f == 65 && ld == 68);
 }
 
-// the launch over the rows the iteration kernel bounced is a separate line of the per-kernel timing table
-static const char* dl_name(const char* base, bool bounced) { return bounced ? wmf_kname("%s [bounced]", base) : base; }
+// One launch of solve_directl_kernel<NFB, BORDER, X6, GE, MODE> over a list, at most `cap` workgroups (resident waves, three rounds
+// queued).  MODE 1: the list counts segments, seg_lo / seg_d / partial are theirs.
+template <int NFB, bool BORDER, bool X6, int GE, int MODE>
+static int launch_directl_k(const RowArgs& a, RowList l, int64_t cap, const int64_t* seg_lo, const int32_t* seg_d, float* partial) {
+    static const WmfKName nm = wmf_kname_pair("solve_directl_kernel<%d, %s, %s, %d, %d>", NFB, wmf_tf(BORDER), wmf_tf(X6), GE, MODE);
+    WMF_LAUNCH(nm.of(l), (solve_directl_kernel<NFB, BORDER, X6, GE, MODE>), dim3((unsigned)(l.count < cap ? l.count : cap)), dim3(64),
+               DL_LDSB(NFB, GE), a.st, l.rows, l.count, a.V, a.side, a.indptr, a.indices, a.vals, a.f, a.ld, a.g, a.fb_rows, a.fb_count, a.dbg,
+               seg_lo, seg_d, partial, l.count_dev);
+    return WMF_L_OK;
+}
 
-int wmf_launch_directl(const int32_t* rows, int64_t count, const float* V, const float* side, const int64_t* indptr,
-                       const int32_t* indices, const float* vals, int f, int ld, float* g, int32_t* fb_rows, int32_t* fb_count,
-                       hipStream_t st, const int32_t* count_dev) {
-    // (count_dev: NULL, or the device-side number of rows -- count is then the capacity of the list and sizes the grid)
-    if (count <= 0) return 0;
-    if (!wmf_directl_supported(f, ld)) return -1;
-    const int nfb = f / 16;                                      // 4 or 8 (the bias column is a border)
+int wmf_launch_directl(const RowArgs& a, RowList l) {
+    if (l.count <= 0) return WMF_L_OK;
+    if (!wmf_directl_supported(a.f, a.ld)) return WMF_L_NO_KERNEL;
+    const int nfb = a.f / 16;                                    // 4 or 8 (the bias column is a border)
+    const bool border = a.f % 16 != 0;
     const int64_t cap = 256 * 4 * (nfb <= 4 ? 2 : 1) * 3;        // resident waves, three rounds queued
-    const dim3 grid((unsigned)(count < cap ? count : cap));
-    const int dbg = wmf_debug_flags;
-#ifdef WMF_LAB
-    const bool x6 = !(dbg & WMF_DBG_HEAVY_F32_ACC);             // (8192, lab builds only): f32 MFMA accumulation
-#else
-    constexpr bool x6 = true;                                   // (the f32-MFMA accumulation variants are compiled into -DWMF_LAB builds only)
-#endif
-#define DL_LAUNCH(N, B, X) WMF_LAUNCH(dl_name("solve_directl_kernel<" #N ", " #B ", " #X ", 16, 0>", count_dev != nullptr), (solve_directl_kernel<N, B, X>), grid, dim3(64), \
-                                      DL_LDSB(N, 16), st, rows, count, V, side, indptr, indices, vals, f, ld, g, fb_rows, fb_count, dbg, \
-                                      (const int64_t*)nullptr, (const int32_t*)nullptr, (float*)nullptr, count_dev)
-#ifdef WMF_LAB
-#define DL_PICK(N) do { if (f % 16) { if (x6) DL_LAUNCH(N, true, true); else DL_LAUNCH(N, true, false); } \
-                        else        { if (x6) DL_LAUNCH(N, false, true); else DL_LAUNCH(N, false, false); } } while (0)
-#else
-#define DL_PICK(N) do { if (f % 16) DL_LAUNCH(N, true, true); else DL_LAUNCH(N, false, true); } while (0)
-#endif
-    if (nfb == 4) DL_PICK(4);
-    else if (x6 && !(dbg & WMF_DBG_HEAVY_ONE_WAVE)) {
+    // (WMF_DBG_HEAVY_F32_ACC, 8192: f32 MFMA accumulation; those variants are compiled into -DWMF_LAB builds only, with 16-entry groups)
+    const bool x6 = !WMF_LAB_BUILD || !(a.dbg & WMF_DBG_HEAVY_F32_ACC);
+    auto pick = [&](auto n, auto ge, int64_t cap_) {
+        constexpr int N = decltype(n)::value, GE = decltype(ge)::value;
+        if constexpr (WMF_LAB_BUILD && GE == 16) {
+            if (!x6) return border ? launch_directl_k<N, true, false, GE, 0>(a, l, cap_, nullptr, nullptr, nullptr)
+                                   : launch_directl_k<N, false, false, GE, 0>(a, l, cap_, nullptr, nullptr, nullptr);
+        }
+        return border ? launch_directl_k<N, true, true, GE, 0>(a, l, cap_, nullptr, nullptr, nullptr)
+                      : launch_directl_k<N, false, true, GE, 0>(a, l, cap_, nullptr, nullptr, nullptr);
+    };
+    if (nfb == 4) return pick(wmf_int<4>{}, wmf_int<16>{}, cap);
+    if (x6 && !(a.dbg & WMF_DBG_HEAVY_ONE_WAVE)) {
         // k = 128: 8-entry groups (16 KB ring, 16-entry chunks with 16x16x16 MFMAs, w_p in LDS by inline asm, lane coordinates
         // re-formed at every pivot), TWO waves per SIMD on 256 registers each (249 used, no scratch).  The second wave
         // overlaps what one wave cannot -- rocprofv3 --pmc at cfg3: VALU active 80 % + MFMA busy 38 % of the SIMD cycles,
@@ -603,32 +604,19 @@ int wmf_launch_directl(const int32_t* rows, int64_t count, const float* V, const
         // add up -- for 19.9 against 21.2 ms.  On the way there: every scratch reload is a VMEM operation that returns in
         // order, i.e. behind every LDS-DMA of the ring (27.3 ms with reloads of spilled lane constants inside the chunk loop,
         // 21.0 with none there, 19.9 with none at all); hipcc puts s_waitcnt vmcnt(0) in front of every LDS access it can see.
-        const dim3 grid2((unsigned)(count < 2 * cap ? count : 2 * cap));
-        if (f % 16) WMF_LAUNCH(dl_name("solve_directl_kernel<8, true, true, 8, 0>", count_dev != nullptr), (solve_directl_kernel<8, true, true, 8>), grid2, dim3(64), DL_LDSB(8, 8), st,
-                               rows, count, V, side, indptr, indices, vals, f, ld, g, fb_rows, fb_count, dbg, (const int64_t*)nullptr,
-                               (const int32_t*)nullptr, (float*)nullptr, count_dev);
-        else WMF_LAUNCH(dl_name("solve_directl_kernel<8, false, true, 8, 0>", count_dev != nullptr), (solve_directl_kernel<8, false, true, 8>), grid2, dim3(64), DL_LDSB(8, 8), st,
-                        rows, count, V, side, indptr, indices, vals, f, ld, g, fb_rows, fb_count, dbg, (const int64_t*)nullptr,
-                        (const int32_t*)nullptr, (float*)nullptr, count_dev);
-    } else DL_PICK(8);
-#undef DL_PICK
-#undef DL_LAUNCH
-    return 0;
+        return pick(wmf_int<8>{}, wmf_int<8>{}, 2 * cap);
+    }
+    return pick(wmf_int<8>{}, wmf_int<16>{}, cap);
 }
 
 // the segments of rows with more than WMF_HEAVY_T entries at k = 128 (+- biases): partial systems by the two-waves kernel
-int wmf_launch_directl_segments(int64_t nseg, const float* V, const float* side, const int32_t* indices, const float* vals, int f,
-                                int ld, const int64_t* seg_lo, const int32_t* seg_d, float* partial, hipStream_t st) {
-    if (nseg <= 0) return 0;
-    if (!((f == 128 && ld == 128) || (f == 129 && ld == 132))) return -1;
+int wmf_launch_directl_segments(const wmf_plan* pl, const RowArgs& a) {
+    if (pl->seg_total <= 0) return WMF_L_OK;
+    if (!((a.f == 128 && a.ld == 128) || (a.f == 129 && a.ld == 132))) return WMF_L_NO_KERNEL;
+    RowArgs s = a;                                               // (segments: no row pointer, no solution, nothing bounced)
+    s.indptr = nullptr; s.g = nullptr; s.fb_rows = nullptr; s.fb_count = nullptr;
+    const RowList segs{nullptr, pl->seg_total, nullptr};
     const int64_t cap = 256 * 4 * 2 * 3;
-    const dim3 grid((unsigned)(nseg < cap ? nseg : cap));
-    const int dbg = wmf_debug_flags;
-    if (f % 16) WMF_LAUNCH("solve_directl_kernel<8, true, true, 8, 1>", (solve_directl_kernel<8, true, true, 8, 1>), grid, dim3(64), DL_LDSB(8, 8), st,
-                           (const int32_t*)nullptr, nseg, V, side, (const int64_t*)nullptr, indices, vals, f, ld, (float*)nullptr,
-                           (int32_t*)nullptr, (int32_t*)nullptr, dbg, seg_lo, seg_d, partial, (const int32_t*)nullptr);
-    else WMF_LAUNCH("solve_directl_kernel<8, false, true, 8, 1>", (solve_directl_kernel<8, false, true, 8, 1>), grid, dim3(64), DL_LDSB(8, 8), st,
-                    (const int32_t*)nullptr, nseg, V, side, (const int64_t*)nullptr, indices, vals, f, ld, (float*)nullptr,
-                    (int32_t*)nullptr, (int32_t*)nullptr, dbg, seg_lo, seg_d, partial, (const int32_t*)nullptr);
-    return 0;
+    return a.f % 16 ? launch_directl_k<8, true, true, 8, 1>(s, segs, cap, pl->seg_lo, pl->seg_d, pl->partial)
+                    : launch_directl_k<8, false, true, 8, 1>(s, segs, cap, pl->seg_lo, pl->seg_d, pl->partial);
 }

@@ -285,156 +285,70 @@ __global__ __launch_bounds__(64, DwCfg<NFB>::OCC) void solve_directw_kernel(cons
     }
 }
 
+// One launch of solve_directw_kernel<NFB, MODE, BORDER> over a list: resident waves, three rounds queued.  seg_lo / seg_d /
+// seg_first / partial / slot_a / slot_b: the kernel's segment arguments (MODE 1 writes partial systems, MODE 2 reads them).
+template <int NFB, int MODE, bool BORDER>
+static int launch_directw_mode(const RowArgs& a, RowList l, const int64_t* seg_lo, const int32_t* seg_d, const int32_t* seg_first,
+                               float* partial, int slot_a, int slot_b) {
+    const int64_t cap = 256 * 4 * DwCfg<NFB>::OCC * 3;
+    static const WmfKName nm = wmf_kname_pair("solve_directw_kernel<%d, %d, %s>", NFB, MODE, wmf_tf(BORDER));
+    WMF_LAUNCH(nm.of(l), (solve_directw_kernel<NFB, MODE, BORDER>), dim3((unsigned)(l.count < cap ? l.count : cap)), dim3(64), 0, a.st,
+               l.rows, l.count, a.V, a.side, a.indptr, a.indices, a.vals, a.f, a.ld, a.g, a.fb_rows, a.fb_count, a.dbg, seg_lo, seg_d,
+               seg_first, partial, slot_a, slot_b, l.count_dev);
+    return WMF_L_OK;
+}
+
 template <int NFB, bool BORDER>
-static void launch_directw_nfb(const wmf_plan* pl, const float* V, const float* side, const int64_t* indptr,
-                               const int32_t* indices, const float* vals, int f, int ld, float* g, int dbg, bool rolled, hipStream_t st) {
-    constexpr int waves_per_cu = 4 * DwCfg<NFB>::OCC;
-    const int64_t cap = 256 * waves_per_cu * 3;                  // resident waves, three rounds queued
-    const int32_t* rows = pl->rows[WMF_BIN_MFMA];
-    const int64_t normal = pl->count[WMF_BIN_MFMA] - pl->heavy_count;
-    // ROUND 4: the first iter_count of the normal rows (at most wmf_iter_dmax entries each, wmf_plan_create) go to the
-    // matrix-free iteration kernel (wmf_iter.hip); what it cannot solve to float32 accuracy in a few applications of the
-    // row's operator comes back as a device-side list and is eliminated below like every other row.  WMF_DBG_NO_ITER (268435456)
-    // switches the iteration off (everything eliminated, as in round 3).
-    const int64_t n_iter = wmf_iter_rows(pl, f, ld, side != nullptr);
-    if (n_iter > 0)
-        (void)wmf_launch_iter(rows, n_iter, V, side, indptr, indices, vals, f, ld, g, pl->iter_bounce_rows, pl->fallback_count + 1,
-                              pl->iter_stats, pl->iter_info, st, (side && rolled) ? 1 : 0);
-    // two launches of the elimination kernel: the rows that were never candidates (count on the host), then the bounced ones
-    // (count on the device; the grid is sized for the list's capacity and exits at once when the list is empty)
-    for (int pass = 0; pass < 2; ++pass) {
-        const int32_t* prow = pass ? pl->iter_bounce_rows : rows + n_iter;
-        const int64_t pcount = pass ? n_iter : normal - n_iter;
-        const int32_t* pdev = pass ? pl->fallback_count + 1 : nullptr;
-        if (pcount <= 0) continue;
-        // k = 128 with or without biases: the LDS-DMA ring kernel (wmf_directl.hip); WMF_DBG_HEAVY_REG_RING (4096) keeps the register ring
-        // and k = 64 since round 2: with the split-f16 accumulation AND elimination the LDS-DMA kernel, two waves per SIMD there,
-        // takes 0.97 ms for cfg2's item side where the f32 register-ring kernel takes 1.39 (round 1, bf16 x 3 accumulation
-        // and f32 elimination: 1.34 against 1.30; WMF_DBG_HEAVY_REG_RING_K64, 65536, keeps the register ring at k = 64 in lab builds)
-        // (side: NULL, or the {last feature, bias} pairs of the split layout, V then being the packed body)
-        if (wmf_directl_supported(f, ld) && !(dbg & WMF_DBG_HEAVY_REG_RING) && (f >= 128 || !(dbg & WMF_DBG_HEAVY_REG_RING_K64))) {
-            (void)wmf_launch_directl(prow, pcount, V, side, indptr, indices, vals, f, ld, g, pl->fallback_rows, pl->fallback_count, st, pdev);
-        } else {
-            static const char* nm = wmf_kname("solve_directw_kernel<%d, 0, %s>", NFB, BORDER ? "true" : "false");
-            static const char* nmb = wmf_kname("solve_directw_kernel<%d, 0, %s> [bounced]", NFB, BORDER ? "true" : "false");
-            WMF_LAUNCH(pass ? nmb : nm, (solve_directw_kernel<NFB, 0, BORDER>), dim3((unsigned)(pcount < cap ? pcount : cap)), dim3(64), 0, st,
-                       prow, pcount, V, side, indptr, indices, vals, f, ld, g, pl->fallback_rows, pl->fallback_count, dbg,
-                       nullptr, nullptr, nullptr, nullptr, 1, 0, pdev);
+static int launch_directw_nfb(const wmf_plan* pl, const RowArgs& a) {
+    const int f = a.f, ld = a.ld, dbg = a.dbg;
+    return wmf_schedule_bin(pl, WMF_BIN_MFMA, a, pl->heavy_count, WMF_DW_PARTIAL(NFB, BORDER), [&](int mode, RowList l) -> int {
+        if (mode == 0) {
+            // k = 128 with or without biases: the LDS-DMA ring kernel (wmf_directl.hip); WMF_DBG_HEAVY_REG_RING (4096) keeps the register ring
+            // and k = 64 since round 2: with the split-f16 accumulation AND elimination the LDS-DMA kernel, two waves per SIMD there,
+            // takes 0.97 ms for cfg2's item side where the f32 register-ring kernel takes 1.39 (round 1, bf16 x 3 accumulation
+            // and f32 elimination: 1.34 against 1.30; WMF_DBG_HEAVY_REG_RING_K64, 65536, keeps the register ring at k = 64 in lab builds)
+            if (wmf_directl_supported(f, ld) && !(dbg & WMF_DBG_HEAVY_REG_RING) && (f >= 128 || !(dbg & WMF_DBG_HEAVY_REG_RING_K64)))
+                return wmf_launch_directl(a, l);
+            return launch_directw_mode<NFB, 0, BORDER>(a, l, nullptr, nullptr, nullptr, nullptr, 1, 0);
         }
-    }
-    if (pl->heavy_count > 0) {
-        const int64_t nseg = pl->seg_total;
-        static const char* nm1 = wmf_kname("solve_directw_kernel<%d, 1, %s>", NFB, BORDER ? "true" : "false");
-        static const char* nm2 = wmf_kname("solve_directw_kernel<%d, 2, %s>", NFB, BORDER ? "true" : "false");
-        // (k = 128: the segments through the LDS-DMA kernel as well -- same partial layout; WMF_DBG_HEAVY_REG_RING / _HEAVY_ONE_WAVE: here)
-        if (NFB == 8 && wmf_directl_supported(f, ld) && !(dbg & (WMF_DBG_HEAVY_REG_RING | WMF_DBG_HEAVY_F32_ACC | WMF_DBG_HEAVY_ONE_WAVE))) {
-            (void)wmf_launch_directl_segments(nseg, V, side, indices, vals, f, ld, pl->seg_lo, pl->seg_d, pl->partial, st);
-        } else
-        WMF_LAUNCH(nm1, (solve_directw_kernel<NFB, 1, BORDER>), dim3((unsigned)(nseg < cap ? nseg : cap)), dim3(64), 0, st, rows,
-                   nseg, V, side, indptr, indices, vals, f, ld, g, pl->fallback_rows, pl->fallback_count, dbg, pl->seg_lo,
-                   pl->seg_d, pl->seg_first, pl->partial, 1, 0, (const int32_t*)nullptr);
-        const int64_t nh = pl->heavy_count;
-        wmf_launch_combine_segments(pl, WMF_DW_PARTIAL(NFB, BORDER), st);
-        WMF_LAUNCH(nm2, (solve_directw_kernel<NFB, 2, BORDER>), dim3((unsigned)(nh < cap ? nh : cap)), dim3(64), 0, st,
-                   rows + normal, nh, V, side, indptr, indices, vals, f, ld, g, pl->fallback_rows, pl->fallback_count, dbg,
-                   pl->seg_lo, pl->seg_d, pl->seg_first, pl->partial, 0, 0, (const int32_t*)nullptr);
-    }
+        if (mode == 1) {
+            // (k = 128: the segments through the LDS-DMA kernel as well -- same partial layout; WMF_DBG_HEAVY_REG_RING / _HEAVY_ONE_WAVE: here)
+            if (NFB == 8 && wmf_directl_supported(f, ld) && !(dbg & (WMF_DBG_HEAVY_REG_RING | WMF_DBG_HEAVY_F32_ACC | WMF_DBG_HEAVY_ONE_WAVE)))
+                return wmf_launch_directl_segments(pl, a);
+            return launch_directw_mode<NFB, 1, BORDER>(a, l, pl->seg_lo, pl->seg_d, pl->seg_first, pl->partial, 1, 0);
+        }
+        return launch_directw_mode<NFB, 2, BORDER>(a, l, pl->seg_lo, pl->seg_d, pl->seg_first, pl->partial, 0, 0);
+    });
+}
+
+int64_t wmf_directw_partial_floats(int f) {
+    if (f < 1 || f > 144) return 0;
+    const int64_t nfb = wmf_dw_border(f) ? f / 16 : (f + 15) / 16;
+    return nfb * (nfb - 1) / 2 * 256 + nfb * WMF_DW_TRI + (nfb + (wmf_dw_border(f) ? nfb + 2 : 0)) * 64;
 }
 
 // Partial systems for the reduce-scatter exchange (engine.py, "reduce mode"): MODE 1 over every row of a CSR (one
 // segment per row, slot = row) and MODE 2 over a buffer of summed partial systems (one slot per row, row = slot).
-template <int NFB, bool BORDER>
-static void launch_accumulate_nfb(const float* V, const float* side, const int64_t* indptr, const int32_t* degrees, const int32_t* indices,
-                                  const float* vals, int64_t n, int f, int ld, float* partial, int slot_stride, int slot_offset,
-                                  hipStream_t st) {
-    const int64_t cap = 256 * 4 * DwCfg<NFB>::OCC * 3;
-    static const char* nm = wmf_kname("solve_directw_kernel<%d, 1, %s>", NFB, BORDER ? "true" : "false");
-    WMF_LAUNCH(nm, (solve_directw_kernel<NFB, 1, BORDER>), dim3((unsigned)(n < cap ? n : cap)), dim3(64), 0, st, nullptr, n, V,
-               side, indptr, indices, vals, f, ld, nullptr, nullptr, nullptr, wmf_debug_flags & ~(WMF_DBG_NO_ELIMINATION | WMF_DBG_NO_ACCUMULATION), indptr, degrees,
-               nullptr, partial, slot_stride, slot_offset, (const int32_t*)nullptr);
-}
-template <int NFB, bool BORDER>
-static void launch_eliminate_nfb(float* partial, int64_t n, int slots_per_row, int f, int ld, float* g, int32_t* fb_rows,
-                                 int32_t* fail_count, hipStream_t st) {
-    const int64_t cap = 256 * 4 * DwCfg<NFB>::OCC * 3;
-    static const char* nm = wmf_kname("solve_directw_kernel<%d, 2, %s>", NFB, BORDER ? "true" : "false");
-    WMF_LAUNCH(nm, (solve_directw_kernel<NFB, 2, BORDER>), dim3((unsigned)(n < cap ? n : cap)), dim3(64), 0, st, nullptr, n,
-               nullptr, nullptr, nullptr, nullptr, nullptr, f, ld, g, fb_rows, fail_count, wmf_debug_flags & ~(WMF_DBG_NO_ELIMINATION | WMF_DBG_NO_ACCUMULATION), nullptr,
-               nullptr, nullptr, partial, slots_per_row, 0, (const int32_t*)nullptr);
-}
-static bool dw_border(int f) { return wmf_dw_border(f); }
-
-int64_t wmf_directw_partial_floats(int f) {
-    if (f < 1 || f > 144) return 0;
-    const int64_t nfb = dw_border(f) ? f / 16 : (f + 15) / 16;
-    return nfb * (nfb - 1) / 2 * 256 + nfb * WMF_DW_TRI + (nfb + (dw_border(f) ? nfb + 2 : 0)) * 64;
+int wmf_launch_accumulate(const RowArgs& a, const int32_t* degrees, int64_t n, float* partial, int slot_stride, int slot_offset) {
+    if (n <= 0) return WMF_L_OK;
+    if (a.f > 144) return WMF_L_NO_KERNEL;
+    return wmf_dispatch_dw(a.f, wmf_dw_border(a.f), [&](auto nfb, auto border) {
+        return launch_directw_mode<decltype(nfb)::value, 1, decltype(border)::value>(a, RowList{nullptr, n, nullptr}, a.indptr, degrees, nullptr, partial,
+                                                                                     slot_stride, slot_offset);
+    });
 }
 
-int wmf_launch_accumulate(const float* V, const float* side, const int64_t* indptr, const int32_t* degrees, const int32_t* indices,
-                          const float* vals, int64_t n, int f, int ld, float* partial, int slot_stride, int slot_offset,
-                          hipStream_t st) {
-    if (n <= 0) return 0;
-    if (f > 144) return -1;
-    if (dw_border(f)) {
-        switch (f / 16) {
-#define C_(N) case N: launch_accumulate_nfb<N, true>(V, side, indptr, degrees, indices, vals, n, f, ld, partial, slot_stride, slot_offset, st); break;
-            C_(1) C_(2) C_(4) C_(5) C_(6) C_(8)
-#undef C_
-            default: return -1;
-        }
-        return 0;
-    }
-    switch ((f + 15) / 16) {
-#define C_(N) case N: launch_accumulate_nfb<N, false>(V, nullptr, indptr, degrees, indices, vals, n, f, ld, partial, slot_stride, slot_offset, st); break;
-        C_(1) C_(2) C_(3) C_(4) C_(5) C_(6) C_(7) C_(8) C_(9)
-#undef C_
-        default: return -1;
-    }
-    return 0;
+int wmf_launch_eliminate(const RowArgs& a, float* partial, int64_t n, int slots_per_row) {
+    if (n <= 0) return WMF_L_OK;
+    if (a.f > 144) return WMF_L_NO_KERNEL;
+    return wmf_dispatch_dw(a.f, wmf_dw_border(a.f), [&](auto nfb, auto border) {
+        return launch_directw_mode<decltype(nfb)::value, 2, decltype(border)::value>(a, RowList{nullptr, n, nullptr}, nullptr, nullptr, nullptr, partial,
+                                                                                     slots_per_row, 0);
+    });
 }
 
-int wmf_launch_eliminate(float* partial, int64_t n, int slots_per_row, int f, int ld, float* g, int32_t* fb_rows,
-                         int32_t* fail_count, hipStream_t st) {
-    if (n <= 0) return 0;
-    if (f > 144) return -1;
-    if (dw_border(f)) {
-        switch (f / 16) {
-#define C_(N) case N: launch_eliminate_nfb<N, true>(partial, n, slots_per_row, f, ld, g, fb_rows, fail_count, st); break;
-            C_(1) C_(2) C_(4) C_(5) C_(6) C_(8)
-#undef C_
-            default: return -1;
-        }
-        return 0;
-    }
-    switch ((f + 15) / 16) {
-#define C_(N) case N: launch_eliminate_nfb<N, false>(partial, n, slots_per_row, f, ld, g, fb_rows, fail_count, st); break;
-        C_(1) C_(2) C_(3) C_(4) C_(5) C_(6) C_(7) C_(8) C_(9)
-#undef C_
-        default: return -1;
-    }
-    return 0;
-}
-
-int wmf_launch_directw(const wmf_plan* pl, const float* V, const float* side, const int64_t* indptr,
-                       const int32_t* indices, const float* vals, int f, int ld, float* g, bool rolled, hipStream_t st) {
-    if (pl->count[WMF_BIN_MFMA] <= 0) return 0;
-    const int dbg = wmf_debug_flags;
-    // k = 16 m with biases: m blocks and a border column.  The row stream must deliver the border feature as its own
-    // dword block (lane 0), which it does unless m + 1 is a multiple of 4 (then all blocks are 16-byte pieces).
-    if (dw_border(f)) {
-        switch (f / 16) {
-#define C_(N) case N: launch_directw_nfb<N, true>(pl, V, side, indptr, indices, vals, f, ld, g, dbg, rolled, st); break;
-            C_(1) C_(2) C_(4) C_(5) C_(6) C_(8)
-#undef C_
-            default: return -1;
-        }
-        return 0;
-    }
-    switch ((f + 15) / 16) {
-#define C_(N) case N: launch_directw_nfb<N, false>(pl, V, side, indptr, indices, vals, f, ld, g, dbg, rolled, st); break;
-        C_(1) C_(2) C_(3) C_(4) C_(5) C_(6) C_(7) C_(8) C_(9)
-#undef C_
-        default: return -1;
-    }
-    return 0;
+int wmf_launch_directw(const wmf_plan* pl, const RowArgs& a) {
+    if (pl->count[WMF_BIN_MFMA] <= 0) return WMF_L_OK;
+    // k = 16 m with biases: m blocks and a border column (wmf_dispatch_dw)
+    return wmf_dispatch_dw(a.f, wmf_dw_border(a.f), [&](auto nfb, auto border) { return launch_directw_nfb<decltype(nfb)::value, decltype(border)::value>(pl, a); });
 }

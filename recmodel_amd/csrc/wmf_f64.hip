@@ -922,66 +922,75 @@ static int gram64_blocks(int64_t m) {
 static int solve64_blocks(int64_t n) { return (int)(n < 1 ? 1 : (n > 4096 ? 4096 : n)); }
 #define WMF_F64_LU_GRID 256
 
-// workspace: [gram partials nwg x blocks x 16][G f x f][LU slices WMF_F64_LU_GRID x (f x f + f)] doubles [64 int32: fallback count,
-// control words][fallback rows n int32][R blocks f4 x f4 x 16][R^-1 FP x FP][R^-T FP x FP][V m x f][g n x f] doubles
-static int64_t f64_al(int64_t bytes) { return (bytes + 255) / 256 * 256; }
-int64_t wmf_f64_ws_bytes(int f, int64_t m, int64_t n) {
-    const int64_t ff = (int64_t)f * f, f4 = (f + 3) / 4, FP = 4 * f4;
-    return f64_al(8 * ((int64_t)gram64_blocks(m) * f64_blocks(f, false) * 16 + ff + (int64_t)WMF_F64_LU_GRID * (ff + f))) + f64_al(4 * (n + 64)) +
-           f64_al(8 * f4 * f4 * 16) + 2 * f64_al(8 * FP * FP) + f64_al(8 * m * f) + f64_al(8 * (n > 0 ? n : 1) * f) + f64_al(4 * (n > 0 ? n : 1)) + 256;
-}
+// The workspace of a float64 half step, laid out once: byte offsets of its parts, each a multiple of 256, and the size.
+// [gram partials nwg x blocks x 16][G f x f][LU slices WMF_F64_LU_GRID x (f x f + f)] doubles [64 int32: fallback count, control
+// words][fallback rows n int32][R blocks f4 x f4 x 16][R^-1 FP x FP][R^-T FP x FP][V m x f][g n x f] doubles [state n int32]
+struct F64Workspace {
+    int64_t partial, G, slices, fb_count, Rblk, Rinv, RinvT, V, gbuf, state, bytes;
+    F64Workspace(int f, int64_t m, int64_t n) {
+        const int64_t ff = (int64_t)f * f, f4 = (f + 3) / 4, FP = 4 * f4, n1 = n > 0 ? n : 1;
+        int64_t at = 0;
+        auto take = [&at](int64_t b) { const int64_t off = at; at += (b + 255) / 256 * 256; return off; };
+        partial = 0;
+        G = 8 * (int64_t)gram64_blocks(m) * f64_blocks(f, false) * 16;            // (the three double arrays are one aligned part)
+        slices = G + 8 * ff;
+        take(slices + 8 * (int64_t)WMF_F64_LU_GRID * (ff + f));
+        fb_count = take(4 * (n + 64));                                            // [16 ..): control words, [64 ..): fallback rows
+        Rblk = take(8 * f4 * f4 * 16);
+        Rinv = take(8 * FP * FP);
+        RinvT = take(8 * FP * FP);
+        V = take(8 * m * f);
+        gbuf = take(8 * n1 * f);
+        state = take(4 * n1);
+        bytes = at + 256;
+    }
+};
+int64_t wmf_f64_ws_bytes(int f, int64_t m, int64_t n) { return F64Workspace(f, m, n).bytes; }
 
 template <int NB>
-static void launch_gram64(const double* Y, int64_t m, int f, int bias, double lambda, double* partial, double* G, int nwg, hipStream_t st) {
+static int launch_gram64(const double* Y, int64_t m, int f, int bias, double lambda, double* partial, double* G, int nwg, hipStream_t st) {
     const int f4 = (f + 3) / 4, FP = 4 * f4;
     const size_t lds_g = (size_t)(F64_R * FP + F64_R) * 8;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gram64v2_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        attr_set = true;
-    }
+    WMF_LDS_CEILING((gram64v2_kernel<NB>), 64 * 1024);      // (at the first Gramian of this width, whichever form it takes)
     static const char* nmg = wmf_kname("gram64v2_kernel<%d>", NB);
     const int64_t rpb = (m + nwg - 1) / nwg;
     const int nb16 = (f + 15) / 16, pw = (nb16 * (nb16 + 1) / 2 + 7) / 8, ldy = 16 * nb16 + ((nb16 & 1) ? 0 : 16);
     if (pw <= 6 && !(wmf_debug_flags & WMF_DBG_F64_VALU)) {        // the matrix-core form (f <= 144)
-#define GM_(PW)                                                                                                            \
-    case PW: {                                                                                                             \
-        static const char* nm_ = wmf_kname("gram64m_kernel<%d>", PW);                                                      \
-        WMF_LAUNCH(nm_, (gram64m_kernel<PW>), dim3(nwg), dim3(512), (size_t)2 * 16 * ldy * 8, st, Y, m, f, bias, partial, rpb, nb16, ldy); \
-    } break;
-        switch (pw) { GM_(1) GM_(2) GM_(3) GM_(4) GM_(5) GM_(6) }
-#undef GM_
+        (void)wmf_dispatch_nfb<1, 6>(pw, [&](auto n) {
+            constexpr int PW = decltype(n)::value;
+            static const char* nm = wmf_kname("gram64m_kernel<%d>", PW);
+            WMF_LAUNCH(nm, (gram64m_kernel<PW>), dim3(nwg), dim3(512), (size_t)2 * 16 * ldy * 8, st, Y, m, f, bias, partial, rpb, nb16, ldy);
+            return WMF_L_OK;
+        });
     } else
     WMF_LAUNCH(nmg, (gram64v2_kernel<NB>), dim3(nwg), dim3(256), lds_g, st, Y, m, f, bias, partial, rpb);
     const int nel = f64_blocks(f, false) * 16;
     WMF_LAUNCH("gram64v2_reduce_kernel", gram64v2_reduce_kernel, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, st, partial, nwg, f,
                lambda, G);
+    return WMF_L_OK;
 }
 
 template <int NB, int TEAM, int R>
-static void launch_solve64(const double* Y, int f, int bias, const double* G, const int64_t* indptr, const int32_t* indices,
+static int launch_solve64(const double* Y, int f, int bias, const double* G, const int64_t* indptr, const int32_t* indices,
                            const double* values, int64_t n, double* X, int32_t* fb_rows, int32_t* fb_count, const int32_t* ctrl, hipStream_t st,
                            const int32_t* state) {
     const int team_doubles = (int)((solve64v2_team_doubles(f, R) + 1) & ~(size_t)1);           // 16-byte aligned slices
     const size_t lds = (size_t)team_doubles * 8 * (256 / TEAM);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)solve64v2_kernel<NB, TEAM, R>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        attr_set = true;
-    }
     static const char* nms = wmf_kname("solve64v2_kernel<%d, %d, %d>", NB, TEAM, R);
     const int64_t teams = 256 / TEAM;
     int64_t grid = (n + teams - 1) / teams;
     if (grid > 4096) grid = 4096;
-    WMF_LAUNCH(nms, (solve64v2_kernel<NB, TEAM, R>), dim3((unsigned)grid), dim3(256), lds, st, Y, f, bias, G, indptr, indices, values, n,
-               X, fb_rows, fb_count, team_doubles, ctrl, state);
+    WMF_LAUNCH_LDS(nms, (solve64v2_kernel<NB, TEAM, R>), 64 * 1024, dim3((unsigned)grid), dim3(256), lds, st, Y, f, bias, G, indptr, indices,
+                   values, n, X, fb_rows, fb_count, team_doubles, ctrl, state);
+    return WMF_L_OK;
 }
 
 template <int NB>
-static void launch_factor64(const double* G, int f, double* Rblk, int32_t* ctrl, hipStream_t st) {
+static int launch_factor64(const double* G, int f, double* Rblk, int32_t* ctrl, hipStream_t st) {
     const int f4 = (f + 3) / 4;
     static const char* nm = wmf_kname("factor64_kernel<%d>", NB);
     WMF_LAUNCH(nm, (factor64_kernel<NB>), dim3(1), dim3(256), (size_t)(2 * (f4 + 1) * 16 + 32 + 8) * 8, st, G, f, Rblk, ctrl);
+    return WMF_L_OK;
 }
 
 template <int NB>
@@ -996,128 +1005,99 @@ static void launch_transform64(const double* in, int64_t m, int f, const double*
         if (lds <= 160 * 1024 && f4 <= 36 && !(wmf_debug_flags & WMF_DBG_F64_VALU)) {
             int64_t grid = ((m + 15) / 16 + 7) / 8;
             if (grid > 256) grid = 256;
-#define TM_(KK, G)                                                                                                                     \
-    do {                                                                                                                               \
-        static bool set_ = false;                                                                                                      \
-        if (!set_) {                                                                                                                   \
-            (void)hipFuncSetAttribute((const void*)transform64m_kernel<KK, G>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            set_ = true;                                                                                                               \
-        }                                                                                                                              \
-        static const char* nm_ = wmf_kname("transform64m_kernel<%d, %d>", KK, G);                                                      \
-        WMF_LAUNCH(nm_, (transform64m_kernel<KK, G>), dim3((unsigned)grid), dim3(512), lds, st, in, m, f, W, set_col0_one, out, indptr, \
-                   ctrl, state, ldw, nb);                                                                                              \
-    } while (0)
-            if (f4 <= 16) TM_(16, 2);
-            else if (f4 == 17) TM_(17, 3);
-            else if (f4 <= 20) TM_(20, 3);
-            else if (f4 <= 24) TM_(24, 3);
-            else if (f4 <= 28) TM_(28, 3);
-            else if (f4 <= 32) TM_(32, 3);
-            else if (f4 == 33) TM_(33, 3);
-            else TM_(36, 3);
-#undef TM_
+            auto tm = [&](auto kk, auto gg) {
+                constexpr int KK = decltype(kk)::value, G = decltype(gg)::value;
+                static const char* nm = wmf_kname("transform64m_kernel<%d, %d>", KK, G);
+                WMF_LAUNCH_LDS(nm, (transform64m_kernel<KK, G>), 160 * 1024, dim3((unsigned)grid), dim3(512), lds, st, in, m, f, W, set_col0_one,
+                               out, indptr, ctrl, state, ldw, nb);
+            };
+            if (f4 <= 16) tm(wmf_int<16>{}, wmf_int<2>{});
+            else if (f4 == 17) tm(wmf_int<17>{}, wmf_int<3>{});
+            else if (f4 <= 20) tm(wmf_int<20>{}, wmf_int<3>{});
+            else if (f4 <= 24) tm(wmf_int<24>{}, wmf_int<3>{});
+            else if (f4 <= 28) tm(wmf_int<28>{}, wmf_int<3>{});
+            else if (f4 <= 32) tm(wmf_int<32>{}, wmf_int<3>{});
+            else if (f4 == 33) tm(wmf_int<33>{}, wmf_int<3>{});
+            else tm(wmf_int<36>{}, wmf_int<3>{});
             return;
         }
-    }
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)transform64_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        attr_set = true;
     }
     int64_t grid = (m + 63) / 64;                   // at least four 16-row passes per workgroup
     if (grid > 2048) grid = 2048;
     const int64_t rpb = ((m + grid - 1) / grid + 15) / 16 * 16;
     static const char* nm = wmf_kname("transform64_kernel<%d>", NB);
-    WMF_LAUNCH(nm, (transform64_kernel<NB>), dim3((unsigned)((m + rpb - 1) / rpb)), dim3(256), (size_t)16 * (FP + 1) * 8, st, in, m, f, W,
-               set_col0_one, out, indptr, ctrl, rpb, state);
+    WMF_LAUNCH_LDS(nm, (transform64_kernel<NB>), 64 * 1024, dim3((unsigned)((m + rpb - 1) / rpb)), dim3(256), (size_t)16 * (FP + 1) * 8, st, in,
+                   m, f, W, set_col0_one, out, indptr, ctrl, rpb, state);
 }
 
 int wmf_launch_half_step_f64(const double* Y, int64_t m, int f, int bias, const int64_t* indptr, const int32_t* indices,
                              const double* values, int64_t n, double lambda, double* X, void* ws, int32_t* fail, hipStream_t st) {
-    const int64_t ff = (int64_t)f * f, f4 = (f + 3) / 4, FP = 4 * f4;
+    const int64_t f4 = (f + 3) / 4, FP = 4 * f4;
     const int nwg = gram64_blocks(m);
+    const F64Workspace w(f, m, n);
     char* base = static_cast<char*>(ws);
-    double* partial = reinterpret_cast<double*>(base);
-    double* G = partial + (int64_t)nwg * f64_blocks(f, false) * 16;
-    double* slices = G + ff;
-    base += f64_al(8 * ((int64_t)nwg * f64_blocks(f, false) * 16 + ff + (int64_t)WMF_F64_LU_GRID * (ff + f)));
-    int32_t* fb_count = reinterpret_cast<int32_t*>(base);
+    double* partial = reinterpret_cast<double*>(base + w.partial);
+    double* G = reinterpret_cast<double*>(base + w.G);
+    double* slices = reinterpret_cast<double*>(base + w.slices);
+    int32_t* fb_count = reinterpret_cast<int32_t*>(base + w.fb_count);
     int32_t* ctrl = fb_count + 16;                  // [0] low-rank path on, [1] rows with 1 .. F64_LR_D entries
     int32_t* fb_rows = fb_count + 64;
-    base += f64_al(4 * (n + 64));
-    double* Rblk = reinterpret_cast<double*>(base);
-    base += f64_al(8 * f4 * f4 * 16);
-    double* Rinv = reinterpret_cast<double*>(base);
-    base += f64_al(8 * FP * FP);
-    double* RinvT = reinterpret_cast<double*>(base);
-    base += f64_al(8 * FP * FP);
-    double* V = reinterpret_cast<double*>(base);
-    base += f64_al(8 * m * f);
-    double* gbuf = reinterpret_cast<double*>(base);
-    base += f64_al(8 * (n > 0 ? n : 1) * f);
-    int32_t* state = reinterpret_cast<int32_t*>(base);          // [n] 1: the row was solved by the matrix-free iteration (wmf_iter64.hip)
-    if (hipMemsetAsync(fb_count, 0, 256, st) != hipSuccess) return -2;
-    if (n > 0 && hipMemsetAsync(state, 0, (size_t)n * 4, st) != hipSuccess) return -2;
+    double* Rblk = reinterpret_cast<double*>(base + w.Rblk);
+    double* Rinv = reinterpret_cast<double*>(base + w.Rinv);
+    double* RinvT = reinterpret_cast<double*>(base + w.RinvT);
+    double* V = reinterpret_cast<double*>(base + w.V);
+    double* gbuf = reinterpret_cast<double*>(base + w.gbuf);
+    int32_t* state = reinterpret_cast<int32_t*>(base + w.state);   // [n] 1: the row was solved by the matrix-free iteration (wmf_iter64.hip)
+    if (hipMemsetAsync(fb_count, 0, 256, st) != hipSuccess) return WMF_L_HIP;
+    if (n > 0 && hipMemsetAsync(state, 0, (size_t)n * 4, st) != hipSuccess) return WMF_L_HIP;
     // round 4: rows whose whitened system is close to the identity by a matrix-free Neumann series in float64 (wmf_iter64.hip)
     // -- first: what it marks solved, the two kernels below skip; WMF_DBG_F64_NO_LOW_RANK (134217728: no whitened path) / WMF_DBG_NO_ITER (268435456) switch it off
     const bool iter_on = wmf_iter_enabled() && wmf_iter64_dmax(f) > 0 && !(wmf_debug_flags & WMF_DBG_F64_NO_LOW_RANK);
-    switch (f64_nb(f64_blocks(f, false))) {
-#define C_(N) case N: launch_gram64<N>(Y, m, f, bias, lambda, partial, G, nwg, st); break;
-        C_(1) C_(2) C_(3) C_(5) C_(9)
-#undef C_
-        default: return -1;
-    }
+    const int nb = f64_nb(f64_blocks(f, false));      // 1, 2, 3, 5 or 9
+    if (const int rc = wmf_dispatch_list<1, 2, 3, 5, 9>(nb, [&](auto k) { return launch_gram64<decltype(k)::value>(Y, m, f, bias, lambda, partial, G, nwg, st); })) return rc;
     if (n > 0) {
         // ---- rows with 1 .. 32 entries through the whitened low-rank form, when there are enough of them (WMF_DBG_F64_NO_LOW_RANK: never)
         int64_t cgrid = (n + 255) / 256;
         if (cgrid > 1024) cgrid = 1024;
         hipLaunchKernelGGL(f64_count_low_kernel, dim3((unsigned)cgrid), dim3(256), 0, st, indptr, n, ctrl);
         hipLaunchKernelGGL(f64_decide_kernel, dim3(1), dim3(1), 0, st, ctrl, n, (wmf_debug_flags & WMF_DBG_F64_NO_LOW_RANK) ? 1 : 0, iter_on ? 1 : 0);
-        switch (f64_nb(f64_blocks(f, false))) {
-#define C_(N) case N: launch_factor64<N>(G, f, Rblk, ctrl, st); break;
-            C_(1) C_(2) C_(3) C_(5) C_(9)
-#undef C_
-            default: return -1;
-        }
+        if (const int rc = wmf_dispatch_list<1, 2, 3, 5, 9>(nb, [&](auto k) { return launch_factor64<decltype(k)::value>(G, f, Rblk, ctrl, st); })) return rc;
         WMF_LAUNCH("rinv64_kernel", rinv64_kernel, dim3((unsigned)((FP + 63) / 64)), dim3(64), 0, st, Rblk, f, Rinv, RinvT, ctrl);
         if (4 * f4 <= 256) launch_transform64<1>(Y, m, f, Rinv, bias, V, nullptr, ctrl, st);
         else launch_transform64<2>(Y, m, f, Rinv, bias, V, nullptr, ctrl, st);
         if (iter_on) {
-            if (wmf_launch_iter64(V, Y, f, bias, indptr, indices, values, n, 1, gbuf, state, ctrl, st)) return -1;
-            if (wmf_launch_iter64(V, Y, f, bias, indptr, indices, values, n, 0, gbuf, state, ctrl, st)) return -1;
+            if (wmf_launch_iter64(V, Y, f, bias, indptr, indices, values, n, 1, gbuf, state, ctrl, st)) return WMF_L_NO_KERNEL;
+            if (wmf_launch_iter64(V, Y, f, bias, indptr, indices, values, n, 0, gbuf, state, ctrl, st)) return WMF_L_NO_KERNEL;
         }
         {
-            static bool attr_set = false;
-            if (!attr_set) {
-                (void)hipFuncSetAttribute((const void*)solve64lr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-                attr_set = true;
-            }
             int64_t grid = (n + 3) / 4;
             if (grid > 4096) grid = 4096;
-            WMF_LAUNCH("solve64lr_kernel", solve64lr_kernel, dim3((unsigned)grid), dim3(256), (size_t)4 * F64_LR_TEAM_DOUBLES * 8, st, V, Y, f, bias,
-                       indptr, indices, values, n, gbuf, fb_rows, fb_count, ctrl, state);
+            WMF_LAUNCH_LDS("solve64lr_kernel", solve64lr_kernel, 64 * 1024, dim3((unsigned)grid), dim3(256), (size_t)4 * F64_LR_TEAM_DOUBLES * 8, st,
+                           V, Y, f, bias, indptr, indices, values, n, gbuf, fb_rows, fb_count, ctrl, state);
         }
         if (4 * f4 <= 256) launch_transform64<1>(gbuf, n, f, RinvT, 0, X, indptr, ctrl, st, state);
         else launch_transform64<2>(gbuf, n, f, RinvT, 0, X, indptr, ctrl, st, state);
         // ---- every other row (all of them when the low-rank path is off): the f x f system directly
         const int nblk = f64_blocks(f, true);
-#define S_(N, T, R) launch_solve64<N, T, R>(Y, f, bias, G, indptr, indices, values, n, X, fb_rows, fb_count, ctrl, st, state)
+        auto solve = [&](auto nbk, auto team, auto r) {
+            launch_solve64<decltype(nbk)::value, decltype(team)::value, decltype(r)::value>(Y, f, bias, G, indptr, indices, values, n, X, fb_rows,
+                                                                                          fb_count, ctrl, st, state);
+        };
         const bool waves = !(wmf_debug_flags & WMF_DBG_F64_TEAMS);     // WMF_DBG_F64_TEAMS, 67108864 (timing experiments, lab builds): workgroup teams at every width
-        if (!waves && nblk <= 256) S_(1, 256, 16);
-        else if (nblk <= 64) S_(1, 64, 8);            // one WAVE per row while a lane holds at most three blocks (f <= 68)
-        else if (nblk <= 128) S_(2, 64, 8);
-        else if (nblk <= 192) S_(3, 64, 8);
-        else if (nblk <= 256) S_(1, 256, 16);         // one workgroup per row beyond
-        else if (nblk <= 512) S_(2, 256, 16);
-        else if (nblk <= 768) S_(3, 256, 16);
-        else if (nblk <= 1280) S_(5, 256, 16);
-        else S_(9, 256, 16);
-#undef S_
+        if (!waves && nblk <= 256) solve(wmf_int<1>{}, wmf_int<256>{}, wmf_int<16>{});
+        else if (nblk <= 64) solve(wmf_int<1>{}, wmf_int<64>{}, wmf_int<8>{});            // one WAVE per row while a lane holds at most three blocks (f <= 68)
+        else if (nblk <= 128) solve(wmf_int<2>{}, wmf_int<64>{}, wmf_int<8>{});
+        else if (nblk <= 192) solve(wmf_int<3>{}, wmf_int<64>{}, wmf_int<8>{});
+        else if (nblk <= 256) solve(wmf_int<1>{}, wmf_int<256>{}, wmf_int<16>{});         // one workgroup per row beyond
+        else if (nblk <= 512) solve(wmf_int<2>{}, wmf_int<256>{}, wmf_int<16>{});
+        else if (nblk <= 768) solve(wmf_int<3>{}, wmf_int<256>{}, wmf_int<16>{});
+        else if (nblk <= 1280) solve(wmf_int<5>{}, wmf_int<256>{}, wmf_int<16>{});
+        else solve(wmf_int<9>{}, wmf_int<256>{}, wmf_int<16>{});
         // rows neither kernel could take (negative weights, not positive definite; count on the device; none as a rule)
         WMF_LAUNCH("solve64_lu_kernel", solve64_lu_kernel, dim3(WMF_F64_LU_GRID), dim3(256), 0, st, Y, f, bias, G, indptr, indices,
                    values, fb_rows, fb_count, X, slices, fail);
     }
-    return 0;
+    return WMF_L_OK;
 }
 
 int wmf_launch_confidence_f64(double* values, int64_t nnz, double alpha, double beta, int mode, hipStream_t st) {
@@ -1125,5 +1105,5 @@ int wmf_launch_confidence_f64(double* values, int64_t nnz, double alpha, double 
     int64_t grid = (nnz + 255) / 256;
     if (grid > 4096) grid = 4096;
     WMF_LAUNCH("confidence64_kernel", confidence64_kernel, dim3((unsigned)grid), dim3(256), 0, st, values, nnz, alpha, beta, mode);
-    return 0;
+    return WMF_L_OK;
 }

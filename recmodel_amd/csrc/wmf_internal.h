@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
+#include <utility>
 #include "../../include/wmf_hip.h"
 
 #define WMF_GRAM_MAX_WAVES 4096
@@ -68,10 +70,49 @@ int wmf_launch_factorize(const double* G_sum, int f, int ld, double lambda, floa
 int wmf_launch_transform(const float* in, int64_t m, int f, int ld, const float* W, int set_col0_one, float* out,
                          float* col0_out, hipStream_t st);
 
-// (rolled: this call's V / pairs are in the rolled coordinates with the bias bits, wmf_solve_rows_ex(WMF_SOLVE_ROLLED))
-int wmf_launch_solve(const wmf_plan* plan, const float* V, const float* bias_fixed, const int64_t* indptr,
-                     const int32_t* indices, const float* values, int f, int ld, float* g, int32_t* fail_count,
-                     bool rolled, hipStream_t st);
+// ---- how a launch is routed ("How a launch is routed") --------------------------------------------------------------
+// What a launcher answers; wmf_api.hip (launch_error) turns it into WMF_E* and the message.
+enum WmfLaunchRc { WMF_L_OK = 0, WMF_L_NO_KERNEL = -1, WMF_L_HIP = -2, WMF_L_LAYOUT = -3 };
+
+// What is the same for every launch of one wmf_solve_rows call.  Host only: a launch site unpacks it into the kernel's positional
+// arguments.  side: NULL, or the {last feature, bias} pairs of the split layout (V is then the packed body); biasv / bstride: what
+// the low-row and pivoted kernels read the biases from (the pairs again, or NULL once the biases are folded into vals);
+// fb_rows / fb_count: the list of rows bounced to the pivoted kernel; dbg: wmf_debug_flags, read once per call;
+// rolled: V / the pairs are in the rolled coordinates with the bias bits (wmf_solve_rows_ex(WMF_SOLVE_ROLLED))
+struct RowArgs {
+    const float* V; const float* side; const float* biasv; int bstride;
+    const int64_t* indptr; const int32_t* indices; const float* vals;
+    int f, ld; float* g; int32_t* fb_rows; int32_t* fb_count; int32_t* fail_count;
+    int dbg; bool rolled; hipStream_t st;
+};
+// rows[0 .. count); count_dev: NULL, or the device-side number of rows -- count is then the capacity of the list and sizes the grid
+// (the bounce list of wmf_iter.hip)
+struct RowList { const int32_t* rows; int64_t count; const int32_t* count_dev; };
+
+// A run-time block count as a template argument: fn(wmf_int<N>{}) for the N of the list that equals n (fn answers a WmfLaunchRc),
+// WMF_L_NO_KERNEL when none does.  Exactly the listed N are instantiated.
+template <int N>
+using wmf_int = std::integral_constant<int, N>;
+template <int... NS, class Fn>
+static inline int wmf_dispatch_list(int n, Fn&& fn) {
+    int rc = WMF_L_NO_KERNEL;
+    (void)(... || (n == NS ? ((rc = fn(wmf_int<NS>{})), true) : false));   // (a left fold: the kernels are instantiated, and so emitted, in the order of the list)
+    return rc;
+}
+template <int LO, class Fn, int... IS>
+static inline int wmf_dispatch_seq(int n, Fn&& fn, std::integer_sequence<int, IS...>) { return wmf_dispatch_list<(LO + IS)...>(n, fn); }
+template <int LO, int HI, class Fn>                              // LO <= n <= HI
+static inline int wmf_dispatch_nfb(int n, Fn&& fn) { return wmf_dispatch_seq<LO>(n, fn, std::make_integer_sequence<int, HI - LO + 1>{}); }
+// ... and the one-wave-per-row kernels' pair (wmf_directw.hip): m blocks and a border column where wmf_dw_border(f), m = 1, 2, 4, 5,
+// 6, 8 -- the row stream delivers the border feature as its own dword block unless m + 1 is a multiple of 4 --, plain blocks elsewhere;
+// fn(N, std::bool_constant<BORDER>{})
+template <class Fn>
+static inline int wmf_dispatch_dw(int f, bool border, Fn&& fn) {
+    if (border) return wmf_dispatch_list<1, 2, 4, 5, 6, 8>(f / 16, [&](auto n) { return fn(n, std::true_type{}); });
+    return wmf_dispatch_nfb<1, 9>((f + 15) / 16, [&](auto n) { return fn(n, std::false_type{}); });
+}
+
+int wmf_launch_solve(const wmf_plan* plan, const RowArgs& a);
 static inline int wmf_direct_supported(int f) { return f >= 1 && f <= 144; }   // one wave per row holds the f x f system
 // Widths whose last feature is a border column of an m-block system (f = 16 m + 1 <= 144, m + 1 not a multiple of 4;
 // WMF_DBG_NO_BORDER, 256, switches the border off): k = 16 m with biases.
@@ -86,21 +127,15 @@ static inline bool wmf_dw_border(int f) { return f > 16 && f <= 144 && f % 16 ==
 static inline bool wmf_split_layout(int f, int ld) { return wmf_dw_border(f) && ld == f + 3; }
 // wmf_directl.hip: normal heavy rows at f = 128 / 129 through an LDS-DMA row ring
 int wmf_directl_supported(int f, int ld);
-// (side: NULL, or the {last feature, bias} pairs of the split layout; V is then the packed body)
-// (count_dev: NULL, or the device-side number of rows; count is then the capacity of the list -- the bounce list of wmf_iter.hip)
-int wmf_launch_directl(const int32_t* rows, int64_t count, const float* V, const float* side, const int64_t* indptr,
-                       const int32_t* indices, const float* vals, int f, int ld, float* g, int32_t* fb_rows, int32_t* fb_count,
-                       hipStream_t st, const int32_t* count_dev = nullptr);
-int wmf_launch_directl_segments(int64_t nseg, const float* V, const float* side, const int32_t* indices, const float* vals, int f,
-                                int ld, const int64_t* seg_lo, const int32_t* seg_d, float* partial, hipStream_t st);
-int wmf_launch_directw(const wmf_plan* pl, const float* V, const float* side, const int64_t* indptr,
-                       const int32_t* indices, const float* vals, int f, int ld, float* g, bool rolled, hipStream_t st);
+int wmf_launch_directl(const RowArgs& a, RowList l);
+// (the segments of the plan's split rows, partial systems into pl->partial)
+int wmf_launch_directl_segments(const wmf_plan* pl, const RowArgs& a);
+int wmf_launch_directw(const wmf_plan* pl, const RowArgs& a);
 int64_t wmf_directw_partial_floats(int f);
-int wmf_launch_accumulate(const float* V, const float* side, const int64_t* indptr, const int32_t* degrees, const int32_t* indices,
-                          const float* vals, int64_t n, int f, int ld, float* partial, int slot_stride, int slot_offset,
-                          hipStream_t st);
-int wmf_launch_eliminate(float* partial, int64_t n, int slots_per_row, int f, int ld, float* g, int32_t* fb_rows,
-                         int32_t* fail_count, hipStream_t st);
+// reduce mode: partial systems of the n rows of a CSR (degrees[r] entries from indptr[r]) into slot r * slot_stride + slot_offset;
+// elimination of n summed systems of slots_per_row slots each.  Of `a` they read what their kernels take.
+int wmf_launch_accumulate(const RowArgs& a, const int32_t* degrees, int64_t n, float* partial, int slot_stride, int slot_offset);
+int wmf_launch_eliminate(const RowArgs& a, float* partial, int64_t n, int slots_per_row);
 void wmf_launch_bias_adjust(const float* vals, const int32_t* indices, const float* biasv, int64_t nnz, float* w_eff,
                             hipStream_t st);
 // wmf_csr.hip: COO -> CSR, stable in (row, column)
@@ -109,15 +144,12 @@ int wmf_launch_coo_to_csr(const int64_t* rows, const int64_t* cols, const float*
                           int64_t* indptr, int32_t* indices, float* values, int32_t* bad_flag, void* ws, int64_t ws_bytes,
                           hipStream_t st);
 int wmf_wide_supported(int f);
-int wmf_launch_wide(const int32_t* rows, int64_t count, const float* V, const float* biasv, const int64_t* indptr,
-                    const int32_t* indices, const float* vals, int f, int ld, float* g, int32_t* fb_rows,
-                    int32_t* fb_count, hipStream_t st, const int32_t* count_dev = nullptr);
+int wmf_launch_wide(const RowArgs& a, RowList l);
 // wmf_iter.hip: rows with 33 .. wmf_iter_dmax entries whose whitened system is close to the identity, by a matrix-free
 // Neumann / Chebyshev iteration; the rows it does not solve are appended to bounce_rows (count on the device)
 int wmf_iter_dmax(int f, int ld, int split);
-int wmf_launch_iter(const int32_t* rows, int64_t count, const float* V, const float* side, const int64_t* indptr,
-                    const int32_t* indices, const float* vals, int f, int ld, float* g, int32_t* bounce_rows,
-                    int32_t* bounce_count, unsigned long long* stats, const void* info, hipStream_t st, int lsb = 0);
+// (l: candidates, the first rows of the plan's bin; the plan holds the bounce list, its counters and the candidates' records)
+int wmf_launch_iter(const wmf_plan* pl, const RowArgs& a, RowList l);
 static inline bool wmf_iter_enabled() { return !(wmf_debug_flags & WMF_DBG_NO_ITER); }
 // The rolled whitened coordinates with the bias in the body's last mantissa bits (include/wmf_hip.h, wmf_row_transform modes 3 / 4,
 // wmf_solve_rows_ex): bias models whose packed body is 128 floats (k = 128), transform6_kernel and the iteration kernels only
@@ -131,15 +163,40 @@ static inline int64_t wmf_iter_rows(const wmf_plan* pl, int f, int ld, bool spli
     return (wmf_iter_enabled() && pl->iter_count > 0 && wmf_iter_dmax(f, ld, split ? 1 : 0) >= pl->iter_dmax) ? pl->iter_count : 0;
 }
 int wmf_rowsplit_supported(int f);
-int wmf_launch_rowsplit(const wmf_plan* pl, const float* V, const float* biasv, const int64_t* indptr,
-                        const int32_t* indices, const float* vals, int f, int ld, float* g, hipStream_t st);
+int wmf_launch_rowsplit(const wmf_plan* pl, const RowArgs& a);
 int64_t wmf_rowsplit_partial_floats(int f);      // floats of one segment's partial system
 // partial systems of the segments of every split row summed, in segment order, into the row's first slot (wmf_solve.hip)
 void wmf_launch_combine_segments(const wmf_plan* pl, int64_t partial_floats, hipStream_t st);
+// The schedule of the plan's bin of rows with more than 32 entries, once for every kernel family that solves it (directw with
+// its directl choice, rowsplit, wide): the iteration's candidates; the rows that were never candidates (count on the host); the
+// rows it bounced (count on the device: the grid is sized for the list's capacity and exits at once when the list is empty);
+// then the `heavy` last rows of the bin as segments -> combine -> eliminate.  launch(mode, list) runs the family's kernel:
+// mode 0 solves the rows of the list, 1 writes the partial systems of the plan's segments (the list counts them), 2 eliminates
+// the heavy rows; partial_floats is the size of one segment's partial system.
+template <class Launch>
+static inline int wmf_schedule_bin(const wmf_plan* pl, int bin, const RowArgs& a, int64_t heavy, int64_t partial_floats, Launch&& launch) {
+    const int32_t* rows = pl->rows[bin];
+    const int64_t normal = pl->count[bin] - heavy;
+    // ROUND 4: the first iter_count of the normal rows (at most wmf_iter_dmax entries each, wmf_plan_create) go to the
+    // matrix-free iteration kernel (wmf_iter.hip); what it cannot solve to float32 accuracy in a few applications of the
+    // row's operator comes back as a device-side list and is eliminated like every other row.  WMF_DBG_NO_ITER (268435456)
+    // switches the iteration off (everything eliminated, as in round 3).
+    // (f > 144: the kernels of that bin know no split layout, and biasv is always folded into vals by wmf_launch_solve)
+    const int64_t n_iter = bin == WMF_BIN_GENERAL ? (a.biasv ? 0 : wmf_iter_rows(pl, a.f, a.ld, false)) : wmf_iter_rows(pl, a.f, a.ld, a.side != nullptr);
+    int rc = WMF_L_OK;
+    if (n_iter > 0 && (rc = wmf_launch_iter(pl, a, RowList{rows, n_iter, nullptr}))) return rc;
+    if (normal > n_iter && (rc = launch(0, RowList{rows + n_iter, normal - n_iter, nullptr}))) return rc;
+    if (n_iter > 0 && (rc = launch(0, RowList{pl->iter_bounce_rows, n_iter, pl->fallback_count + 1}))) return rc;
+    if (heavy > 0) {
+        if ((rc = launch(1, RowList{rows, pl->seg_total, nullptr}))) return rc;
+        wmf_launch_combine_segments(pl, partial_floats, a.st);
+        rc = launch(2, RowList{rows + normal, heavy, nullptr});
+    }
+    return rc;
+}
 size_t wmf_wide_lu_workspace_bytes(int f);
-int wmf_launch_wide_lu(const int32_t* rows, const int32_t* count_ptr, const float* V, const float* biasv,
-                       const int64_t* indptr, const int32_t* indices, const float* vals, int f, int ld, float* g,
-                       int32_t* fail_count, float* work, hipStream_t st);
+// (the rows of the bounce list a.fb_rows / a.fb_count)
+int wmf_launch_wide_lu(const RowArgs& a, float* work);
 int wmf_launch_spmm(const float* V, const int64_t* indptr, const int32_t* indices, const float* values, int64_t n,
                     int ld, float* g, hipStream_t st);
 int wmf_launch_eval(const float* users, const float* items, int f, int ld, int bias, const int64_t* indptr,
@@ -183,6 +240,13 @@ void wmf_set_error(const char* fmt, ...);
 // including the template arguments ("solve_low_kernel<9, 1, false, false>"), so that bench.py's table and a
 // rocprofv3 --kernel-trace --stats summary of the same run can be matched line by line.
 const char* wmf_kname(const char* fmt, ...);     // interned: the pointer stays valid for the life of the library
+// a kernel's name and the name of its launch over a device-counted list of bounced rows (a separate line of the timing table)
+struct WmfKName {
+    const char* plain; const char* bounced;
+    const char* of(const RowList& l) const { return l.count_dev ? bounced : plain; }
+};
+WmfKName wmf_kname_pair(const char* fmt, ...);   // {name, name + " [bounced]"}, interned
+static inline const char* wmf_tf(bool b) { return b ? "true" : "false"; }   // a bool template argument as rocprofv3 prints it
 void wmf_prof_begin(const char* name, hipStream_t st);
 void wmf_prof_end(hipStream_t st);
 struct WmfProfScope {
@@ -194,4 +258,20 @@ struct WmfProfScope {
     do {                                                                             \
         WmfProfScope wmf_ps_(NAME, ST);                                              \
         hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, ST, __VA_ARGS__);               \
+    } while (0)
+// The ceiling of a kernel's dynamic LDS, raised once per kernel, at the first pass over the statement (a function-local static's
+// initialiser: thread-safe), and WMF_LAUNCH behind it.
+static inline bool wmf_lds_ceiling(const void* kernel, size_t bytes) {
+    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    return true;
+}
+#define WMF_LDS_CEILING(KERNEL, BYTES)                                                        \
+    do {                                                                                      \
+        static const bool wmf_lc_ = wmf_lds_ceiling((const void*)KERNEL, BYTES);              \
+        (void)wmf_lc_;                                                                        \
+    } while (0)
+#define WMF_LAUNCH_LDS(NAME, KERNEL, CEILING, GRID, BLOCK, LDS, ST, ...)                      \
+    do {                                                                                      \
+        WMF_LDS_CEILING(KERNEL, CEILING);                                                     \
+        WMF_LAUNCH(NAME, KERNEL, GRID, BLOCK, LDS, ST, __VA_ARGS__);                          \
     } while (0)

@@ -788,46 +788,50 @@ int wmf_iter_dmax(int f, int ld, int split) {
     return 0;
 }
 
+// One launch of the iteration kernel over a list of candidates: what it does not solve is appended to bounce_rows / counted in
+// bounce_count (and in the statistics' slot bounce_stat).  info: NULL, or {first entry lo, hi, row id, entries} of l.rows[i]
+// (wmf_plan_create)
 template <int NW, int FPL, int NS, bool SPLIT, bool FULL, int OCC, bool DMA = false, bool LSB = false>
-static void it_launch(const int32_t* rows, int64_t count, const float* V, const float* side, const int64_t* indptr,
-                      const int32_t* indices, const float* vals, int f, int ld, float* g, int32_t* bounce_rows,
-                      int32_t* bounce_count, unsigned long long* stats, const int4* info, hipStream_t st,
-                      const int32_t* count_dev = nullptr, int bounce_stat = IT_STAT_BOUNCED) {
-    static const char* nm = wmf_kname("solve_iter_kernel<%d, %d, %d, %s, %s, %d, %s, %s>", NW, FPL, NS, SPLIT ? "true" : "false",
-                                      FULL ? "true" : "false", OCC, DMA ? "true" : "false", LSB ? "true" : "false");      // (as rocprofv3 prints it)
+static int it_launch(const wmf_plan* pl, const RowArgs& a, RowList l, int32_t* bounce_rows, int32_t* bounce_count, const int4* info,
+                     int bounce_stat = IT_STAT_BOUNCED) {
+    static const char* nm = wmf_kname("solve_iter_kernel<%d, %d, %d, %s, %s, %d, %s, %s>", NW, FPL, NS, wmf_tf(SPLIT), wmf_tf(FULL), OCC,
+                                      wmf_tf(DMA), wmf_tf(LSB));      // (as rocprofv3 prints it)
     using L = ItLds<NW, FPL>;
     // (DMA variant: exchange buffers, the ring of the next row's gathered rows, its weights and border / bias values)
     constexpr size_t dyn = DMA ? (size_t)L::EXCH * 4 + (size_t)NW * NS * (FPL / 4) * 1024 + NW * 768 : 0;
-    static bool attr_set = false;
-    if (DMA && !attr_set) {
-        (void)hipFuncSetAttribute((const void*)solve_iter_kernel<NW, FPL, NS, SPLIT, FULL, OCC, DMA, LSB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-        attr_set = true;
-    }
+    if constexpr (DMA) WMF_LDS_CEILING((solve_iter_kernel<NW, FPL, NS, SPLIT, FULL, OCC, DMA, LSB>), dyn);
     const ItPolicy pol = it_policy();
     const int64_t resident = 256LL * (OCC * 4 / NW);              // workgroups the chip holds
     // four rounds queued (rows differ in length); over a device-side list -- usually empty -- one round: every workgroup of a
     // launch has to be scheduled before it can find that out, 0.10 ms for 2048 workgroups of 72 KB of LDS
-    const int64_t cap = count_dev ? resident : resident * 4;
-    WMF_LAUNCH(nm, (solve_iter_kernel<NW, FPL, NS, SPLIT, FULL, OCC, DMA, LSB>), dim3((unsigned)(count < cap ? count : cap)), dim3(64 * NW), dyn, st,
-               rows, count, V, side, indptr, indices, vals, f, ld, g, bounce_rows, bounce_count, pol.tau, pol.kappa, pol.kmax, pol.eps * pol.eps, stats, info, count_dev, bounce_stat);
+    const int64_t cap = l.count_dev ? resident : resident * 4;
+    WMF_LAUNCH(nm, (solve_iter_kernel<NW, FPL, NS, SPLIT, FULL, OCC, DMA, LSB>), dim3((unsigned)(l.count < cap ? l.count : cap)), dim3(64 * NW), dyn, a.st,
+               l.rows, l.count, a.V, a.side, a.indptr, a.indices, a.vals, a.f, a.ld, a.g, bounce_rows, bounce_count, pol.tau, pol.kappa, pol.kmax,
+               pol.eps * pol.eps, pl->iter_stats, info, l.count_dev, bounce_stat);
+    return WMF_L_OK;
 }
 
-// rows[0 .. count): candidates (more than 32 and at most wmf_iter_dmax entries).  side: NULL, or the {last feature, bias}
-// pairs of the split layout (V is then the packed body).  Rows that are not solved here are appended to bounce_rows.
+// FULL (the row's features fill the lanes' pieces) where ldv = 16 FPL
+template <int NW, int FPL, int NS, bool SPLIT, int OCC>
+static int it_go(const wmf_plan* pl, const RowArgs& a, RowList l, int32_t* bounce_rows, int32_t* bounce_count, const int4* info, int ldv) {
+    return ldv == 16 * FPL ? it_launch<NW, FPL, NS, SPLIT, true, OCC>(pl, a, l, bounce_rows, bounce_count, info)
+                           : it_launch<NW, FPL, NS, SPLIT, false, OCC>(pl, a, l, bounce_rows, bounce_count, info);
+}
+
+// l: candidates (more than 32 and at most wmf_iter_dmax entries).  a.side: NULL, or the {last feature, bias} pairs of the split
+// layout (V is then the packed body).  Rows that are not solved here are appended to the plan's iter_bounce_rows, counted in
+// fallback_count[1].
 // (LAB: a template parameter so that `if constexpr` keeps what only the policy knobs reach out of the shipped build)
 template <bool LAB>
-static int launch_iter(const int32_t* rows, int64_t count, const float* V, const float* side, const int64_t* indptr,
-                       const int32_t* indices, const float* vals, int f, int ld, float* g, int32_t* bounce_rows,
-                       int32_t* bounce_count, unsigned long long* stats, const int4* info, hipStream_t st, int lsb) {
-    // info: NULL, or {first entry lo, hi, row id, entries} of rows[i] (wmf_plan_create)
-    if (count <= 0) return 0;
-    const bool split = side != nullptr;
-    const int ldv = it_ldv(f, ld, split);
+static int launch_iter(const wmf_plan* pl, const RowArgs& a, RowList l) {
+    if (l.count <= 0) return WMF_L_OK;
+    const bool split = a.side != nullptr;
+    const int ldv = it_ldv(a.f, a.ld, split);
     const ItPolicy pol = it_policy();
-#define IT_ONE(NW, FPL, NS, SP, FULL, OCC) \
-    it_launch<NW, FPL, NS, SP, FULL, OCC>(rows, count, V, side, indptr, indices, vals, f, ld, g, bounce_rows, bounce_count, stats, info, st)
-#define IT_GO(NW, FPL, NS, SP, OCC) do { if (ldv == 16 * FPL) IT_ONE(NW, FPL, NS, SP, true, OCC); else IT_ONE(NW, FPL, NS, SP, false, OCC); } while (0)
-    if (split && ldv > 128) return -1;                            // (the split layout exists for f <= 144 only)
+    int32_t* bounce_rows = pl->iter_bounce_rows;
+    int32_t* bounce_count = pl->fallback_count + 1;
+    const int4* info = reinterpret_cast<const int4*>(pl->iter_info);
+    if (split && ldv > 128) return WMF_L_NO_KERNEL;               // (the split layout exists for f <= 144 only)
 #if IT_NW128 == 2
     if (ldv == 128 && pol.two_stage) {
         // Stage 1: two waves per row -- half the per-row overhead of the four-wave form (exchanges, norms, vector updates are per
@@ -836,47 +840,42 @@ static int launch_iter(const int32_t* rows, int64_t count, const float* V, const
         // series that contracts slowly, no convergence) goes to the SECOND HALF of bounce_rows, counted in bounce_count[1].
         // Stage 2: the four-wave LDS-DMA kernel over that list (count on the device; an empty list costs a few microseconds); what
         // IT hands back is the final list, bounce_rows[0 ..) / bounce_count[0], for the elimination kernels.
-        int32_t* handed = bounce_rows + count;
-        if (split && lsb) {            // (the rolled coordinates with the bias in the rows' own bits: nothing fetched from the pairs)
-            it_launch<2, 8, 16, true, true, 2, false, true>(rows, count, V, side, indptr, indices, vals, f, ld, g, handed, bounce_count + 1, stats, info, st, nullptr, IT_STAT_STAGE1);
-            it_launch<4, 8, 8, true, true, 2, true, true>(handed, count, V, side, indptr, indices, vals, f, ld, g, bounce_rows, bounce_count, stats, nullptr, st, bounce_count + 1);
-            return 0;
+        int32_t* handed = bounce_rows + l.count;
+        const RowList stage2{handed, l.count, bounce_count + 1};
+        if (split && a.rolled) {       // (the rolled coordinates with the bias in the rows' own bits: nothing fetched from the pairs)
+            it_launch<2, 8, 16, true, true, 2, false, true>(pl, a, l, handed, bounce_count + 1, info, IT_STAT_STAGE1);
+            return it_launch<4, 8, 8, true, true, 2, true, true>(pl, a, stage2, bounce_rows, bounce_count, nullptr);
         }
-        if (split) it_launch<2, 8, 16, true, true, 2>(rows, count, V, side, indptr, indices, vals, f, ld, g, handed, bounce_count + 1, stats, info, st, nullptr, IT_STAT_STAGE1);
-        else it_launch<2, 8, 16, false, true, 2>(rows, count, V, side, indptr, indices, vals, f, ld, g, handed, bounce_count + 1, stats, info, st, nullptr, IT_STAT_STAGE1);
-        if (split) it_launch<4, 8, 8, true, true, 2, true>(handed, count, V, side, indptr, indices, vals, f, ld, g, bounce_rows, bounce_count, stats, nullptr, st, bounce_count + 1);
-        else it_launch<4, 8, 8, false, true, 2, true>(handed, count, V, side, indptr, indices, vals, f, ld, g, bounce_rows, bounce_count, stats, nullptr, st, bounce_count + 1);
-        return 0;
+        if (split) {
+            it_launch<2, 8, 16, true, true, 2>(pl, a, l, handed, bounce_count + 1, info, IT_STAT_STAGE1);
+            return it_launch<4, 8, 8, true, true, 2, true>(pl, a, stage2, bounce_rows, bounce_count, nullptr);
+        }
+        it_launch<2, 8, 16, false, true, 2>(pl, a, l, handed, bounce_count + 1, info, IT_STAT_STAGE1);
+        return it_launch<4, 8, 8, false, true, 2, true>(pl, a, stage2, bounce_rows, bounce_count, nullptr);
     }
 #endif
     if constexpr (LAB) {
         // what only the knobs reach: ldv <= 64 (WMF_ITER_MIN_LDV) and ldv = 128 in one stage (WMF_ITER_ONE_STAGE, WMF_ITER_NO_DMA)
 #if IT_DMA
         if ((ldv == 64 || ldv == 128) && pol.dma) {
-#define IT_GO_DMA(FPL, SP) it_launch<4, FPL, 8, SP, true, 2, true>(rows, count, V, side, indptr, indices, vals, f, ld, g, bounce_rows, bounce_count, stats, info, st)
-            if (ldv == 64) { if (split) IT_GO_DMA(4, true); else IT_GO_DMA(4, false); }
-            else { if (split) IT_GO_DMA(8, true); else IT_GO_DMA(8, false); }
-#undef IT_GO_DMA
-            return 0;
+            if (ldv == 64) return split ? it_launch<4, 4, 8, true, true, 2, true>(pl, a, l, bounce_rows, bounce_count, info)
+                                        : it_launch<4, 4, 8, false, true, 2, true>(pl, a, l, bounce_rows, bounce_count, info);
+            return split ? it_launch<4, 8, 8, true, true, 2, true>(pl, a, l, bounce_rows, bounce_count, info)
+                         : it_launch<4, 8, 8, false, true, 2, true>(pl, a, l, bounce_rows, bounce_count, info);
         }
 #endif
-        if (ldv <= 64) { if (split) IT_GO(4, 4, IT_NS64S, true, IT_OCC4S); else IT_GO(4, 4, IT_NS64, false, IT_OCC64); return 0; }
-        if (ldv == 128) { if (split) IT_ONE(4, 8, IT_NS128S, true, true, IT_OCC4S); else IT_ONE(4, 8, IT_NS128, false, true, IT_OCC4); return 0; }
+        if (ldv <= 64) return split ? it_go<4, 4, IT_NS64S, true, IT_OCC4S>(pl, a, l, bounce_rows, bounce_count, info, ldv)
+                                    : it_go<4, 4, IT_NS64, false, IT_OCC64>(pl, a, l, bounce_rows, bounce_count, info, ldv);
+        if (ldv == 128) return split ? it_launch<4, 8, IT_NS128S, true, true, IT_OCC4S>(pl, a, l, bounce_rows, bounce_count, info)
+                                     : it_launch<4, 8, IT_NS128, false, true, IT_OCC4>(pl, a, l, bounce_rows, bounce_count, info);
     }
-    if (ldv <= 64 || ldv == 128) return -1;                       // (wmf_iter_dmax: no candidates at these widths without the knobs)
-    else if (ldv < 128) { if (split) IT_ONE(4, 8, IT_NS128S, true, false, IT_OCC4S); else IT_ONE(4, 8, IT_NS128, false, false, IT_OCC4); }
-    else if (ldv <= 192) IT_GO(8, 12, 8, false, 2);
-    else if (ldv <= 256) IT_GO(8, 16, 8, false, 2);
-    else if (ldv <= 320) IT_GO(8, 20, 6, false, 2);
-    else return -1;
-#undef IT_GO
-#undef IT_ONE
-    return 0;
+    if (ldv <= 64 || ldv == 128) return WMF_L_NO_KERNEL;          // (wmf_iter_dmax: no candidates at these widths without the knobs)
+    if (ldv < 128) return split ? it_launch<4, 8, IT_NS128S, true, false, IT_OCC4S>(pl, a, l, bounce_rows, bounce_count, info)
+                                : it_launch<4, 8, IT_NS128, false, false, IT_OCC4>(pl, a, l, bounce_rows, bounce_count, info);
+    if (ldv <= 192) return it_go<8, 12, 8, false, 2>(pl, a, l, bounce_rows, bounce_count, info, ldv);
+    if (ldv <= 256) return it_go<8, 16, 8, false, 2>(pl, a, l, bounce_rows, bounce_count, info, ldv);
+    if (ldv <= 320) return it_go<8, 20, 6, false, 2>(pl, a, l, bounce_rows, bounce_count, info, ldv);
+    return WMF_L_NO_KERNEL;
 }
 
-int wmf_launch_iter(const int32_t* rows, int64_t count, const float* V, const float* side, const int64_t* indptr,
-                    const int32_t* indices, const float* vals, int f, int ld, float* g, int32_t* bounce_rows,
-                    int32_t* bounce_count, unsigned long long* stats, const void* info, hipStream_t st, int lsb) {
-    return launch_iter<WMF_LAB_BUILD>(rows, count, V, side, indptr, indices, vals, f, ld, g, bounce_rows, bounce_count, stats,
-                                      static_cast<const int4*>(info), st, lsb);
-}
+int wmf_launch_iter(const wmf_plan* pl, const RowArgs& a, RowList l) { return launch_iter<WMF_LAB_BUILD>(pl, a, l); }

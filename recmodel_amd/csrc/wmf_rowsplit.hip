@@ -642,9 +642,7 @@ __global__ __launch_bounds__(256, F16A ? RS_OCC16 : 2) void solve_rowsplit_kerne
 }
 
 template <int NFB, bool BORDER, bool F16A, int MODE>
-static void launch_rowsplit_f(const int32_t* rows, int64_t count, const float* V, const float* biasv, const int64_t* indptr,
-                              const int32_t* indices, const float* vals, int f, int ld, float* g, const wmf_plan* pl, hipStream_t st,
-                              const int32_t* count_dev = nullptr) {
+static int launch_rowsplit_f(const wmf_plan* pl, const RowArgs& a, RowList l) {
     using C = RsCfg<NFB, BORDER, F16A>;
     constexpr size_t lds = (size_t)C::TOTAL * 4;
     // ROUND-3 FINDING, ROUND-4 RESOLUTION.  The BORDER kernels with 13 .. 15 blocks (f = 209, 225, 241) gave
@@ -660,49 +658,29 @@ static void launch_rowsplit_f(const int32_t* rows, int64_t count, const float* V
     constexpr bool ALONE = false;
 #endif
     constexpr size_t lds_launch = ALONE && lds < (size_t)82 * 1024 ? (size_t)82 * 1024 : lds;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)solve_rowsplit_kernel<NFB, BORDER, F16A, MODE>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_launch);
-        attr_set = true;
-    }
     int64_t grid = 256 * 2 * 2;                                  // two resident workgroups per CU, two rounds
-    if (grid > count) grid = count;
-    static const char* nm = wmf_kname("solve_rowsplit_kernel<%d, %s, %s, %d>", NFB, BORDER ? "true" : "false",
-                                      F16A ? "true" : "false", MODE);
-    static const char* nmb = wmf_kname("solve_rowsplit_kernel<%d, %s, %s, %d> [bounced]", NFB, BORDER ? "true" : "false",
-                                       F16A ? "true" : "false", MODE);
-    WMF_LAUNCH(count_dev ? nmb : nm, (solve_rowsplit_kernel<NFB, BORDER, F16A, MODE>), dim3((unsigned)grid), dim3(C::NTHR), lds_launch, st, rows, count, V,
-               biasv, indptr, indices, vals, f, ld, g, pl->fallback_rows, pl->fallback_count,
-               wmf_debug_flags, pl->seg_lo, pl->seg_d, pl->seg_first, pl->partial, count_dev);
+    if (grid > l.count) grid = l.count;
+    static const WmfKName nm = wmf_kname_pair("solve_rowsplit_kernel<%d, %s, %s, %d>", NFB, wmf_tf(BORDER), wmf_tf(F16A), MODE);
+    WMF_LAUNCH_LDS(nm.of(l), (solve_rowsplit_kernel<NFB, BORDER, F16A, MODE>), lds_launch, dim3((unsigned)grid), dim3(C::NTHR), lds_launch, a.st,
+                   l.rows, l.count, a.V, a.biasv, a.indptr, a.indices, a.vals, a.f, a.ld, a.g, a.fb_rows, a.fb_count, a.dbg, pl->seg_lo, pl->seg_d,
+                   pl->seg_first, pl->partial, l.count_dev);
+    return WMF_L_OK;
 }
 
 template <int NFB, bool BORDER>
-static void launch_rowsplit_nfb(const wmf_plan* pl, const float* V, const float* biasv, const int64_t* indptr,
-                                const int32_t* indices, const float* vals, int f, int ld, float* g, hipStream_t st) {
-    const int32_t* rows = pl->rows[WMF_BIN_GENERAL];
-    const int64_t normal = pl->count[WMF_BIN_GENERAL] - pl->heavy_count;
+static int launch_rowsplit_nfb(const wmf_plan* pl, const RowArgs& a) {
     // split-f16 accumulation and elimination (WMF_DBG_WIDE_F32, 2097152, in lab builds: the f32 MFMA kernel it replaces; that one
     // does not split rows)
     if constexpr (WMF_LAB_BUILD) {
-        if (wmf_debug_flags & WMF_DBG_WIDE_F32) {
-            launch_rowsplit_f<NFB, BORDER, false, 0>(rows, pl->count[WMF_BIN_GENERAL], V, biasv, indptr, indices, vals, f, ld, g, pl, st);
-            return;
-        }
+        if (a.dbg & WMF_DBG_WIDE_F32)
+            return launch_rowsplit_f<NFB, BORDER, false, 0>(pl, a, RowList{pl->rows[WMF_BIN_GENERAL], pl->count[WMF_BIN_GENERAL], nullptr});
     }
-    // ROUND 4: the first iter_count of the normal rows go to the matrix-free iteration kernel (wmf_iter.hip), which hands back what
-    // it does not solve as a device-side list (as in wmf_directw.hip); WMF_DBG_NO_ITER: off
-    const int64_t n_iter = biasv ? 0 : wmf_iter_rows(pl, f, ld, false);      // (biasv: always folded into vals by wmf_launch_solve)
-    if (n_iter > 0)
-        (void)wmf_launch_iter(rows, n_iter, V, nullptr, indptr, indices, vals, f, ld, g, pl->iter_bounce_rows, pl->fallback_count + 1,
-                              pl->iter_stats, pl->iter_info, st);
-    if (normal > n_iter) launch_rowsplit_f<NFB, BORDER, true, 0>(rows + n_iter, normal - n_iter, V, biasv, indptr, indices, vals, f, ld, g, pl, st);
-    if (n_iter > 0) launch_rowsplit_f<NFB, BORDER, true, 0>(pl->iter_bounce_rows, n_iter, V, biasv, indptr, indices, vals, f, ld, g, pl, st, pl->fallback_count + 1);
-    if (pl->heavy_count > 0) {          // rows with more than WMF_HEAVY_T entries: segments by separate workgroups, then one combine each
-        launch_rowsplit_f<NFB, BORDER, true, 1>(rows, pl->seg_total, V, biasv, indptr, indices, vals, f, ld, g, pl, st);
-        wmf_launch_combine_segments(pl, RS_PARTIAL(NFB, BORDER), st);
-        launch_rowsplit_f<NFB, BORDER, true, 2>(rows + normal, pl->heavy_count, V, biasv, indptr, indices, vals, f, ld, g, pl, st);
-    }
+    // rows with more than WMF_HEAVY_T entries: segments by separate workgroups, then one combine each
+    return wmf_schedule_bin(pl, WMF_BIN_GENERAL, a, pl->heavy_count, RS_PARTIAL(NFB, BORDER), [&](int mode, RowList l) {
+        return mode == 0 ? launch_rowsplit_f<NFB, BORDER, true, 0>(pl, a, l)
+             : mode == 1 ? launch_rowsplit_f<NFB, BORDER, true, 1>(pl, a, l)
+                         : launch_rowsplit_f<NFB, BORDER, true, 2>(pl, a, l);
+    });
 }
 
 int64_t wmf_rowsplit_partial_floats(int f) {
@@ -714,23 +692,9 @@ int64_t wmf_rowsplit_partial_floats(int f) {
 // 144 < f <= 256, and f = 16 m + 1 up to 257 (k = 16 m with biases: m blocks and a border column)
 int wmf_rowsplit_supported(int f) { return f > 144 && (f <= 256 || f == 257); }
 
-int wmf_launch_rowsplit(const wmf_plan* pl, const float* V, const float* biasv, const int64_t* indptr,
-                        const int32_t* indices, const float* vals, int f, int ld, float* g, hipStream_t st) {
-    if (pl->count[WMF_BIN_GENERAL] <= 0) return 0;
-    if (f % 16 == 1 && f / 16 >= 10) {
-        switch (f / 16) {
-#define C_(N) case N: launch_rowsplit_nfb<N, true>(pl, V, biasv, indptr, indices, vals, f, ld, g, st); break;
-            C_(10) C_(11) C_(12) C_(13) C_(14) C_(15) C_(16)
-#undef C_
-            default: return -1;
-        }
-        return 0;
-    }
-    switch ((f + 15) / 16) {
-#define C_(N) case N: launch_rowsplit_nfb<N, false>(pl, V, biasv, indptr, indices, vals, f, ld, g, st); break;
-        C_(10) C_(11) C_(12) C_(13) C_(14) C_(15) C_(16)
-#undef C_
-        default: return -1;
-    }
-    return 0;
+int wmf_launch_rowsplit(const wmf_plan* pl, const RowArgs& a) {
+    if (pl->count[WMF_BIN_GENERAL] <= 0) return WMF_L_OK;
+    if (a.f % 16 == 1 && a.f / 16 >= 10)
+        return wmf_dispatch_nfb<10, 16>(a.f / 16, [&](auto n) { return launch_rowsplit_nfb<decltype(n)::value, true>(pl, a); });
+    return wmf_dispatch_nfb<10, 16>((a.f + 15) / 16, [&](auto n) { return launch_rowsplit_nfb<decltype(n)::value, false>(pl, a); });
 }

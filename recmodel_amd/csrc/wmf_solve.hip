@@ -735,79 +735,75 @@ void wmf_launch_bias_adjust(const float* vals, const int32_t* indices, const flo
 }
 
 // ------------------------------------------------------------------------------------- launchers
+template <int NCH, bool X6>
+static const char* pair_name() {
+    static const char* nm = wmf_kname("solve_pair_kernel<%d, %s>", NCH, wmf_tf(X6));
+    return nm;
+}
+template <int NCH, int NT, bool TI, bool X6>
+static const char* low_name() {
+    static const char* nm = wmf_kname("solve_low_kernel<%d, %d, %s, %s>", NCH, NT, wmf_tf(TI), wmf_tf(X6));
+    return nm;
+}
+
 template <int NCH>
-static void launch_low(const wmf_plan* pl, const float* V, const float* biasv, int bstride, const int64_t* indptr,
-                       const int32_t* indices, const float* vals, int ld, int last1, float* g, hipStream_t st) {
+static int launch_low(const wmf_plan* pl, const RowArgs& a) {
+    const int ld = a.ld;
+    const int last1 = (a.f % 4 == 1 && ld == a.f + 3 && (ld / 4) % 4 == 1) ? 1 : 0;   // the lanes' last slot holds that one piece only
     const int64_t c0 = pl->count[WMF_BIN_LOW16], c1 = pl->count[WMF_BIN_LOW32];
     // rows with at most 8 entries come first in the bin and go two per wave (solve_pair_kernel)
-    const int64_t c8 = (wmf_debug_flags & WMF_DBG_NO_ROW_PAIRS) ? 0 : pl->count8;
+    const int64_t c8 = (a.dbg & WMF_DBG_NO_ROW_PAIRS) ? 0 : pl->count8;
     // split-f16 S tiles (X6, solve_low_kernel) where the row is whole 32-feature chunks, or those and one more piece
     // (WMF_DBG_LOW_F32_TILES, 524288: f32 MFMAs everywhere)
     constexpr bool X6_OK = (NCH % 2 == 0) || (NCH >= 3);
-    const bool x6 = X6_OK && !(wmf_debug_flags & WMF_DBG_LOW_F32_TILES) && ((NCH % 2 == 0) ? (ld % 32 == 0) : (last1 && ld == 16 * (NCH - 1) + 4));   // (last1: f = ld - 3, one feature in the last piece)
-    if (bstride == 3 && !(x6 && NCH == 9)) bstride = 2;        // (the bias is rebuilt from the row in the X6 piece order only: elsewhere the pairs are read)
-#define WMF_LOW_LAUNCH(KERNEL, NAME, ROWS, COUNT, GRID)                                                                   \
-    do {                                                                                                                  \
-        static const char* nm_ = NAME;                                                                                     \
-        WmfProfScope ps_(nm_, st);                                                                                         \
-        hipLaunchKernelGGL(KERNEL, dim3((unsigned)(GRID)), dim3(256), 0, st, ROWS, COUNT, V, biasv, indptr, indices, vals,  \
-                           ld, last1, g, pl->fallback_rows, pl->fallback_count, bstride);                                   \
-    } while (0)
+    const bool x6 = X6_OK && !(a.dbg & WMF_DBG_LOW_F32_TILES) && ((NCH % 2 == 0) ? (ld % 32 == 0) : (last1 && ld == 16 * (NCH - 1) + 4));   // (last1: f = ld - 3, one feature in the last piece)
+    const int bstride = (a.bstride == 3 && !(x6 && NCH == 9)) ? 2 : a.bstride;   // (the bias is rebuilt from the row in the X6 piece order only: elsewhere the pairs are read)
+    auto launch = [&](auto kernel, const char* name, const int32_t* rows, int64_t count, int64_t grid) {
+        WMF_LAUNCH(name, kernel, dim3((unsigned)grid), dim3(256), 0, a.st, rows, count, a.V, a.biasv, a.indptr, a.indices, a.vals, ld, last1,
+                   a.g, a.fb_rows, a.fb_count, bstride);
+    };
+    const int32_t* rows16 = pl->rows[WMF_BIN_LOW16];
     if (c8 > 0) {
         if constexpr (X6_OK) {
-            if (x6) WMF_LOW_LAUNCH((solve_pair_kernel<NCH, true>), wmf_kname("solve_pair_kernel<%d, true>", NCH), pl->rows[WMF_BIN_LOW16], c8, ((c8 + 1) / 2 + 3) / 4);
+            if (x6) launch(solve_pair_kernel<NCH, true>, pair_name<NCH, true>(), rows16, c8, ((c8 + 1) / 2 + 3) / 4);
         }
-        if (!x6) WMF_LOW_LAUNCH((solve_pair_kernel<NCH, false>), wmf_kname("solve_pair_kernel<%d, false>", NCH), pl->rows[WMF_BIN_LOW16], c8, ((c8 + 1) / 2 + 3) / 4);
+        if (!x6) launch(solve_pair_kernel<NCH, false>, pair_name<NCH, false>(), rows16, c8, ((c8 + 1) / 2 + 3) / 4);
     }
     if (c0 - c8 > 0) {
         if constexpr (X6_OK) {
-            if (x6) WMF_LOW_LAUNCH((solve_low_kernel<NCH, 1, false, true>), wmf_kname("solve_low_kernel<%d, 1, false, true>", NCH), pl->rows[WMF_BIN_LOW16] + c8, c0 - c8, (c0 - c8 + 3) / 4);
+            if (x6) launch(solve_low_kernel<NCH, 1, false, true>, low_name<NCH, 1, false, true>(), rows16 + c8, c0 - c8, (c0 - c8 + 3) / 4);
         }
-        if (!x6) WMF_LOW_LAUNCH((solve_low_kernel<NCH, 1, false, false>), wmf_kname("solve_low_kernel<%d, 1, false, false>", NCH), pl->rows[WMF_BIN_LOW16] + c8, c0 - c8, (c0 - c8 + 3) / 4);
+        if (!x6) launch(solve_low_kernel<NCH, 1, false, false>, low_name<NCH, 1, false, false>(), rows16 + c8, c0 - c8, (c0 - c8 + 3) / 4);
     }
     if (c1 > 0) {
+        const int32_t* rows32 = pl->rows[WMF_BIN_LOW32];
         bool gauss_jordan = false;      // plain 32 x 32 Gauss-Jordan, kept for A/B timing in lab builds (WMF_DBG_LOW32_GAUSS_JORDAN, 64)
         if constexpr (WMF_LAB_BUILD) {
-            gauss_jordan = (wmf_debug_flags & WMF_DBG_LOW32_GAUSS_JORDAN) != 0;
-            if (gauss_jordan) WMF_LOW_LAUNCH((solve_low_kernel<NCH, 2, false, false>), wmf_kname("solve_low_kernel<%d, 2, false, false>", NCH), pl->rows[WMF_BIN_LOW32], c1, (c1 + 3) / 4);
+            gauss_jordan = (a.dbg & WMF_DBG_LOW32_GAUSS_JORDAN) != 0;
+            if (gauss_jordan) launch(solve_low_kernel<NCH, 2, false, false>, low_name<NCH, 2, false, false>(), rows32, c1, (c1 + 3) / 4);
         }
         if (!gauss_jordan) {
             if constexpr (X6_OK) {
-                if (x6) WMF_LOW_LAUNCH((solve_low_kernel<NCH, 2, true, true>), wmf_kname("solve_low_kernel<%d, 2, true, true>", NCH), pl->rows[WMF_BIN_LOW32], c1, (c1 + 3) / 4);
+                if (x6) launch(solve_low_kernel<NCH, 2, true, true>, low_name<NCH, 2, true, true>(), rows32, c1, (c1 + 3) / 4);
             }
-            if (!x6) WMF_LOW_LAUNCH((solve_low_kernel<NCH, 2, true, false>), wmf_kname("solve_low_kernel<%d, 2, true, false>", NCH), pl->rows[WMF_BIN_LOW32], c1, (c1 + 3) / 4);
+            if (!x6) launch(solve_low_kernel<NCH, 2, true, false>, low_name<NCH, 2, true, false>(), rows32, c1, (c1 + 3) / 4);
         }
     }
-#undef WMF_LOW_LAUNCH
+    return WMF_L_OK;
 }
 
+// the pivoted float32 LU kernel over a list of rows (count_dev: the bounce list of the other kernels)
 template <int NFB>
-static void launch_general(const int32_t* rows, int64_t count, const int32_t* count_ptr, int grid, const float* V,
-                           const float* biasv, int bstride, const int64_t* indptr, const int32_t* indices, const float* vals, int f,
-                           int ld, float* g, int32_t* fail_count, hipStream_t st) {
+static int launch_general(const RowArgs& a, RowList l) {
     constexpr int FP = 16 * NFB;
     constexpr size_t lds = ((size_t)16 * (FP + 4) + 16 + FP + 8 + (size_t)FP * (FP + 1)) * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)solve_general_kernel<NFB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
-        attr_set = true;
-    }
     static const char* nm = wmf_kname("solve_general_kernel<%d>", NFB);
-    WMF_LAUNCH(nm, (solve_general_kernel<NFB>), dim3(grid), dim3(256), lds, st, rows, count, count_ptr, V, biasv,
-               indptr, indices, vals, f, ld, g, fail_count, bstride);
+    WMF_LAUNCH_LDS(nm, (solve_general_kernel<NFB>), lds, dim3(256), dim3(256), lds, a.st, l.rows, l.count, l.count_dev, a.V, a.biasv,
+                   a.indptr, a.indices, a.vals, a.f, a.ld, a.g, a.fail_count, a.bstride);
+    return WMF_L_OK;
 }
-
-static int dispatch_general(const int32_t* rows, int64_t count, const int32_t* count_ptr, int grid, const float* V,
-                            const float* biasv, int bstride, const int64_t* indptr, const int32_t* indices, const float* vals, int f,
-                            int ld, float* g, int32_t* fail_count, hipStream_t st) {
-    switch ((f + 15) / 16) {
-#define C(N) case N: launch_general<N>(rows, count, count_ptr, grid, V, biasv, bstride, indptr, indices, vals, f, ld, g, fail_count, st); break;
-        C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9)
-#undef C
-        default: return -1;
-    }
-    return 0;
+static int dispatch_general(const RowArgs& a, RowList l) {
+    return wmf_dispatch_nfb<1, 9>((a.f + 15) / 16, [&](auto n) { return launch_general<decltype(n)::value>(a, l); });
 }
 
 // ---- split rows: the partial systems of a row's segments summed into the row's first slot.  One thread per float4 of the
@@ -843,68 +839,47 @@ void wmf_launch_combine_segments(const wmf_plan* pl, int64_t partial_floats, hip
                pl->partial, pl->seg_first, pl->heavy_count, pf4);
 }
 
-int wmf_launch_solve(const wmf_plan* pl, const float* V, const float* biasv, const int64_t* indptr,
-                     const int32_t* indices, const float* vals, int f, int ld, float* g, int32_t* fail_count,
-                     bool rolled, hipStream_t st) {
-    if (hipMemsetAsync(pl->fallback_count, 0, 3 * sizeof(int32_t), st) != hipSuccess) return -2;   // [0] pivoted fallback, [1] rows handed back by wmf_iter.hip, [2] its stage 1's hand-on list
+int wmf_launch_solve(const wmf_plan* pl, const RowArgs& call) {
+    RowArgs a = call;                                                  // (V, biasv, indptr, indices, vals, f, ld, g, fail_count, rolled, st: the caller's)
+    a.dbg = wmf_debug_flags;
+    a.fb_rows = pl->fallback_rows;
+    a.fb_count = pl->fallback_count;
+    const int f = a.f, ld = a.ld;
+    if (hipMemsetAsync(pl->fallback_count, 0, 3 * sizeof(int32_t), a.st) != hipSuccess) return WMF_L_HIP;   // [0] pivoted fallback, [1] rows handed back by wmf_iter.hip, [2] its stage 1's hand-on list
     const int64_t nnz = pl->nnz[0] + pl->nnz[1] + pl->nnz[2] + pl->nnz[3];
     if (nnz == 0)                                                      // nothing stored: every row solves to zero
-        return hipMemsetAsync(g, 0, (size_t)pl->n * ld * sizeof(float), st) == hipSuccess ? 0 : -2;
-    int bstride = 1;
-    const float* side = nullptr;
-    if (biasv && wmf_split_layout(f, ld)) {                            // split layout: V is the packed body, biasv the pairs
-        side = biasv;
-        bstride = (rolled && f == 129) ? 3 : 2;                        // (3: wmf_solve_rows_ex(WMF_SOLVE_ROLLED): the low-row kernels rebuild the bias from the row)
-    } else if (biasv) {                                                // other widths: fold the biases into the weights once
-        if (!pl->w_eff) return -3;                                     // (plan latched the split layout, this call is not in it)
-        wmf_launch_bias_adjust(vals, indices, biasv, nnz, pl->w_eff, st);   // (w_eff: allocated by wmf_plan_create(bias = 1))
-        vals = pl->w_eff;
-        biasv = nullptr;
+        return hipMemsetAsync(a.g, 0, (size_t)pl->n * ld * sizeof(float), a.st) == hipSuccess ? WMF_L_OK : WMF_L_HIP;
+    a.bstride = 1;
+    a.side = nullptr;
+    if (a.biasv && wmf_split_layout(f, ld)) {                          // split layout: V is the packed body, biasv the pairs
+        a.side = a.biasv;
+        a.bstride = (a.rolled && f == 129) ? 3 : 2;                    // (3: wmf_solve_rows_ex(WMF_SOLVE_ROLLED): the low-row kernels rebuild the bias from the row)
+    } else if (a.biasv) {                                              // other widths: fold the biases into the weights once
+        if (!pl->w_eff) return WMF_L_LAYOUT;                           // (plan latched the split layout, this call is not in it)
+        wmf_launch_bias_adjust(a.vals, a.indices, a.biasv, nnz, pl->w_eff, a.st);   // (w_eff: allocated by wmf_plan_create(bias = 1))
+        a.vals = pl->w_eff;
+        a.biasv = nullptr;
     }
-    switch ((ld + 15) / 16) {
-#define C(N) case N: launch_low<N>(pl, V, biasv, bstride, indptr, indices, vals, ld, (f % 4 == 1 && ld == f + 3 && (ld / 4) % 4 == 1) ? 1 : 0, g, st); break;   /* the lanes' last slot holds that one piece only */
-        C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12) C(13) C(14) C(15) C(16) C(17)
-#undef C
-        default: return -1;
-    }
-    const bool general_ok = f <= 144;
-    if (pl->count[WMF_BIN_MFMA] > 0 && (wmf_debug_flags & WMF_DBG_HEAVY_PIVOTED_LU)) {
+    int rc = wmf_dispatch_nfb<1, 17>((ld + 15) / 16, [&](auto n) { return launch_low<decltype(n)::value>(pl, a); });
+    if (rc) return rc;
+    if (pl->count[WMF_BIN_MFMA] > 0 && (a.dbg & WMF_DBG_HEAVY_PIVOTED_LU)) {
         // WMF_DBG_HEAVY_PIVOTED_LU, 33554432 (accuracy experiments, lab builds): every row of this bin through the pivoted float32 LU kernel
-        if (dispatch_general(pl->rows[WMF_BIN_MFMA], pl->count[WMF_BIN_MFMA], nullptr, 256, V, biasv, bstride, indptr, indices, vals, f, ld,
-                             g, fail_count, st)) return -1;
+        rc = dispatch_general(a, RowList{pl->rows[WMF_BIN_MFMA], pl->count[WMF_BIN_MFMA], nullptr});
     } else if (pl->count[WMF_BIN_MFMA] > 0) {
         // one wave per row with the whole system in MFMA accumulator registers (wmf_directw.hip, wmf_directl.hip)
-        if (wmf_launch_directw(pl, V, side, indptr, indices, vals, f, ld, g, rolled, st)) return -1;
+        rc = wmf_launch_directw(pl, a);
     }
+    if (rc) return rc;
     if (pl->count[WMF_BIN_GENERAL] > 0) {
         // f > 144: rows with more than 32 entries go to the workgroup-per-row kernel (wmf_wide.hip)
-        if (!wmf_wide_supported(f)) return -1;
+        if (!wmf_wide_supported(f)) return WMF_L_NO_KERNEL;
         // f <= 256: four waves per row, tiles owned by block row (wmf_rowsplit.hip); f = 257 .. 272, or
-        // WMF_DBG_WIDE_EIGHT_WAVES (1024, lab builds): the run-time-indexed eight-wave kernel (wmf_wide.hip)
-        if (wmf_rowsplit_supported(f) && !(wmf_debug_flags & WMF_DBG_WIDE_EIGHT_WAVES)) {
-            if (wmf_launch_rowsplit(pl, V, biasv, indptr, indices, vals, f, ld, g, st)) return -1;
-        } else {
-            // (f = 258 .. 272: no split rows; the iteration kernel first, as in wmf_directw.hip / wmf_rowsplit.hip)
-            const int32_t* rows = pl->rows[WMF_BIN_GENERAL];
-            const int64_t all = pl->count[WMF_BIN_GENERAL];
-            const int64_t n_iter = biasv ? 0 : wmf_iter_rows(pl, f, ld, false);
-            if (n_iter > 0 && wmf_launch_iter(rows, n_iter, V, nullptr, indptr, indices, vals, f, ld, g, pl->iter_bounce_rows,
-                                              pl->fallback_count + 1, pl->iter_stats, pl->iter_info, st)) return -1;
-            if (all > n_iter && wmf_launch_wide(rows + n_iter, all - n_iter, V, biasv, indptr, indices, vals, f, ld, g,
-                                                pl->fallback_rows, pl->fallback_count, st)) return -1;
-            if (n_iter > 0 && wmf_launch_wide(pl->iter_bounce_rows, n_iter, V, biasv, indptr, indices, vals, f, ld, g,
-                                              pl->fallback_rows, pl->fallback_count, st, pl->fallback_count + 1)) return -1;
-        }
+        // WMF_DBG_WIDE_EIGHT_WAVES (1024, lab builds): the run-time-indexed eight-wave kernel (wmf_wide.hip), which splits no rows
+        if (wmf_rowsplit_supported(f) && !(a.dbg & WMF_DBG_WIDE_EIGHT_WAVES)) rc = wmf_launch_rowsplit(pl, a);
+        else rc = wmf_schedule_bin(pl, WMF_BIN_GENERAL, a, 0, 0, [&](int, RowList l) { return wmf_launch_wide(a, l); });
+        if (rc) return rc;
     }
-    {
-        // rows bounced by the other kernels (negative weights / not positive definite); count is on the device
-        if (general_ok) {
-            if (dispatch_general(pl->fallback_rows, 0, pl->fallback_count, 256, V, biasv, bstride, indptr, indices, vals, f, ld, g,
-                                 fail_count, st)) return -1;
-        } else {
-            if (wmf_launch_wide_lu(pl->fallback_rows, pl->fallback_count, V, biasv, indptr, indices, vals, f, ld, g, fail_count,
-                                   pl->wide_ws, st)) return -1;
-        }
-    }
-    return 0;
+    // rows bounced by the other kernels (negative weights / not positive definite); count is on the device
+    if (f <= 144) return dispatch_general(a, RowList{a.fb_rows, 0, a.fb_count});
+    return wmf_launch_wide_lu(a, pl->wide_ws);
 }

@@ -358,46 +358,29 @@ __global__ __launch_bounds__(256) void solve_wide_lu_kernel(const int32_t* __res
 }
 
 template <int NFB>
-static void launch_wide_nfb(const int32_t* rows, int64_t count, const float* V, const float* biasv, const int64_t* indptr,
-                            const int32_t* indices, const float* vals, int f, int ld, float* g, int32_t* fb_rows,
-                            int32_t* fb_count, hipStream_t st, const int32_t* count_dev) {
+static int launch_wide_nfb(const RowArgs& a, RowList l) {
     using C = WideCfg<NFB>;
     constexpr size_t lds = (size_t)C::TOTAL * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)solve_wide_kernel<NFB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
     int64_t grid = 256 * 2;                                      // one resident workgroup per CU (LDS), two rounds
-    if (grid > count) grid = count;
-    static const char* nm = wmf_kname("solve_wide_kernel<%d>", NFB);
-    static const char* nmb = wmf_kname("solve_wide_kernel<%d> [bounced]", NFB);
-    WMF_LAUNCH(count_dev ? nmb : nm, (solve_wide_kernel<NFB>), dim3((unsigned)grid), dim3(C::NTHR), lds, st, rows, count, V, biasv, indptr,
-               indices, vals, f, ld, g, fb_rows, fb_count, wmf_debug_flags, count_dev);
+    if (grid > l.count) grid = l.count;
+    static const WmfKName nm = wmf_kname_pair("solve_wide_kernel<%d>", NFB);
+    WMF_LAUNCH_LDS(nm.of(l), (solve_wide_kernel<NFB>), lds, dim3((unsigned)grid), dim3(C::NTHR), lds, a.st, l.rows, l.count, a.V, a.biasv,
+                   a.indptr, a.indices, a.vals, a.f, a.ld, a.g, a.fb_rows, a.fb_count, a.dbg, l.count_dev);
+    return WMF_L_OK;
 }
 
 int wmf_wide_supported(int f) { return f > 144 && f <= 272; }
 
-int wmf_launch_wide(const int32_t* rows, int64_t count, const float* V, const float* biasv, const int64_t* indptr,
-                    const int32_t* indices, const float* vals, int f, int ld, float* g, int32_t* fb_rows,
-                    int32_t* fb_count, hipStream_t st, const int32_t* count_dev) {
-    if (count <= 0) return 0;
-    switch ((f + 15) / 16) {
-#define C_(N) case N: launch_wide_nfb<N>(rows, count, V, biasv, indptr, indices, vals, f, ld, g, fb_rows, fb_count, st, count_dev); break;
-        C_(10) C_(11) C_(12) C_(13) C_(14) C_(15) C_(16) C_(17)
-#undef C_
-        default: return -1;
-    }
-    return 0;
+int wmf_launch_wide(const RowArgs& a, RowList l) {
+    if (l.count <= 0) return WMF_L_OK;
+    return wmf_dispatch_nfb<10, 17>((a.f + 15) / 16, [&](auto n) { return launch_wide_nfb<decltype(n)::value>(a, l); });
 }
 
 size_t wmf_wide_lu_workspace_bytes(int f) { return (size_t)WMF_WIDE_LU_GRID * f * (f + 1) * sizeof(float); }
 
-int wmf_launch_wide_lu(const int32_t* rows, const int32_t* count_ptr, const float* V, const float* biasv,
-                       const int64_t* indptr, const int32_t* indices, const float* vals, int f, int ld, float* g,
-                       int32_t* fail_count, float* work, hipStream_t st) {
-    if (f > 272 || ld > 276) return -1;
-    WMF_LAUNCH("solve_wide_lu_kernel", solve_wide_lu_kernel, dim3(WMF_WIDE_LU_GRID), dim3(256), 0, st, rows, count_ptr, V, biasv,
-               indptr, indices, vals, f, ld, g, fail_count, work);
-    return 0;
+int wmf_launch_wide_lu(const RowArgs& a, float* work) {
+    if (a.f > 272 || a.ld > 276) return WMF_L_NO_KERNEL;
+    WMF_LAUNCH("solve_wide_lu_kernel", solve_wide_lu_kernel, dim3(WMF_WIDE_LU_GRID), dim3(256), 0, a.st, a.fb_rows, a.fb_count, a.V, a.biasv,
+               a.indptr, a.indices, a.vals, a.f, a.ld, a.g, a.fail_count, work);
+    return WMF_L_OK;
 }

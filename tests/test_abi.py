@@ -75,6 +75,25 @@ def test_pure_host_entry_points(lib):
     assert lib.wmf_whitened_row_floats(129, 132, 0) == 132
 
 
+def test_float64_workspace_layout_is_unchanged(lib):
+    """wmf_half_step_f64_workspace_bytes is host arithmetic over the one layout that wmf_launch_half_step_f64 carves as well
+    (F64Workspace, csrc/wmf_f64.hip).  The table was recorded from the library before that layout was written once: the sum of
+    its aligned parts must not move."""
+    shapes = ((0, 0), (1, 1), (1000, 37), (100003, 250001))
+    recorded = {
+        1: [6144, 6656, 15360, 4856320],
+        16: [567552, 568064, 704256, 47867392],
+        17: [642048, 642560, 789248, 50991616],
+        65: [8952320, 8953344, 9550336, 200591872],
+        129: [34970624, 34972160, 36255744, 426179072],
+        144: [43513088, 43514624, 44962560, 481963520],
+        145: [44142592, 44144128, 45614848, 487240192],
+        257: [138223616, 138226176, 141177856, 966908416],
+    }
+    for f, want in recorded.items():
+        assert [lib.wmf_half_step_f64_workspace_bytes(f, m, n) for m, n in shapes] == want, f
+
+
 CSRC = os.path.join(ROOT, "recmodel_amd", "csrc")
 
 
