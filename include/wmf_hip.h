@@ -166,7 +166,8 @@ int wmf_eval_sqerr(const float* users, const float* items, int f, int ld, int bi
                    int64_t n, double* out3, void* workspace, void* stream);
 
 /* out[p] = predict(users_idx[p], items_idx[p])   wmf_model.py:205-211.
- * n_u == 1 or n_i == 1 broadcasts that index (the reference's one-user / one-item form). */
+ * n_u == 1 or n_i == 1 broadcasts that index (the reference's one-user / one-item form).
+ * An empty side (n_u == 0 or n_i == 0, the other 0 or 1) has no pairs: WMF_OK, nothing is read or written. */
 int wmf_predict_pairs(const float* users, const float* items, int f, int ld, int bias,
                       const int32_t* users_idx, int64_t n_u, const int32_t* items_idx, int64_t n_i,
                       float* out, void* stream);

@@ -425,6 +425,7 @@ int wmf_predict_pairs(const float* users, const float* items, int f, int ld, int
         wmf_set_error("users and items need to have the same length or only one user / item needs to be provided.");
         return WMF_EINVAL;
     }
+    if (n_u <= 0 || n_i <= 0) return WMF_OK;                      // an empty side against one index: no pair, nothing read or written
     wmf_launch_predict(users, items, f, ld, bias, users_idx, n_u, items_idx, n_i, out, (hipStream_t)stream);
     return check_launch("wmf_predict_pairs");
 }
