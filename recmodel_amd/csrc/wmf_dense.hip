@@ -7,6 +7,7 @@
 #include "wmf_common.h"
 #include "wmf_internal.h"
 
+#include <type_traits>
 #include <utility>
 
 // ------------------------------------------------------------------------------------------ gram
@@ -88,10 +89,23 @@ __device__ __forceinline__ void gram_body(const float* __restrict__ Y, int64_t m
 // (lo.hi, mid.mid, hi.lo, mid.hi, hi.mid, hi.hi; the dropped products are below 2^-24 of the term): the accuracy of the
 // f32 path at 6 x 16 instead of 8 x 32 MFMA cycles per tile and 32 rows.
 typedef __bf16 gram_bf16x8 __attribute__((ext_vector_type(8)));
+// The next chunk of a wave is requested while this one is worked on, in two groups: its first feature blocks ahead of this
+// chunk's split, the others ahead of its MFMAs.  A chunk is 8 NFB (72) loads and vmcnt counts 63: requested together ahead of
+// the split, the split's waits for THIS chunk could only be written as counts that also retire most of the next one, and the
+// MFMAs ran with nothing in flight.  Loads return in order and nothing before the last MFMA of a trip reads the next chunk, so
+// no wait of a trip asks for one of its loads; they are collected after the MFMAs, when `nxt` becomes `cur` (scheduling fences
+// keep the four phases apart: hipcc would otherwise hoist the copies, and their waits, into the split).  The wave's last chunk
+// is peeled: the loads inside the loop are unconditional (a conditional request makes the waits of the split cover the path
+// without it: all landed), and a chunk that has a successor in its wave is full (c0 + 32 <= c0 + stride < m) -- it is split as
+// loaded, its bias column is the constant one; only the peeled chunk, among them the one ragged chunk of the matrix, carries
+// the row masks (x * 1.0f is x: the results are the same bits).
+// (Two named register sets with the loop unrolled by two, which would drop the copies, spill: the VALU addresses 256 of the 512
+// registers, and two raw chunks + the parts + their addresses need 270 of them; measured figures in DESIGN.md section 9.)
 template <int NFB>
 __device__ __forceinline__ void gram_body6(const float* __restrict__ Y, int64_t m, int f, int ld, int bias,
                                            float* __restrict__ partial, int64_t step_lo, int64_t step_hi) {
     constexpr int NT = NFB * (NFB + 1) / 2;
+    constexpr int NG1 = (5 * NFB + 4) / 9;                                      // feature blocks of the first group: 5 of 9, 4 of 8 and 7
     const int lane = threadIdx.x;
     const int r = lane & 15, q = lane >> 4;
     f32x4 acc[NT];
@@ -99,38 +113,40 @@ __device__ __forceinline__ void gram_body6(const float* __restrict__ Y, int64_t 
     for (int i = 0; i < NT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int last_col = min(16 * (NFB - 1) + r, ld - 1);
     const float col_mask_last = (16 * (NFB - 1) + r < f) ? 1.f : 0.f;
+    const bool bias_lane = bias && r == 0;
     // chunks of 32 rows dealt round-robin over the waves (step_lo = this wave, step_hi = the number of waves): at any moment the
     // resident waves read one contiguous stretch of the matrix
-    const int64_t row_lo = 32 * step_lo, row_hi = m, stride = 32 * step_hi;
-    float cur[8][NFB], nxt[8][NFB];
-    auto load_chunk = [&](int64_t c0, float (&fr)[8][NFB]) {
+    const int64_t stride = 32 * step_hi;
+    auto load_blocks = [&](int64_t c0, float (&fr)[8][NFB], int fb_lo, int fb_hi) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int64_t row = min(c0 + 8 * q + j, m - 1);                     // clamped: masked at use
             const float* yrow = Y + row * (int64_t)ld;
 #pragma unroll
-            for (int fb = 0; fb < NFB - 1; ++fb) fr[j][fb] = yrow[16 * fb + r];
-            fr[j][NFB - 1] = yrow[last_col];
+            for (int fb = 0; fb < NFB; ++fb)
+                if (fb >= fb_lo && fb < fb_hi) fr[j][fb] = yrow[fb == NFB - 1 ? last_col : 16 * fb + r];
         }
     };
-    if (row_lo < row_hi) load_chunk(row_lo, cur);
-    for (int64_t c0 = row_lo; c0 < row_hi; c0 += stride) {
-        if (c0 + stride < row_hi) load_chunk(c0 + stride, nxt);
-        gram_bf16x8 hi[NFB], mid[NFB], lo[NFB];
+    auto split = [&](int64_t c0, const float (&fr)[8][NFB], auto masked, gram_bf16x8 (&hi)[NFB], gram_bf16x8 (&mid)[NFB],
+                     gram_bf16x8 (&lo)[NFB]) {
+        // block by block, as the two load groups arrive; the eight raw values of a block die as its twelve part registers fill
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float rmask = (c0 + 8 * q + j < row_hi) ? 1.f : 0.f;
+        for (int fb = 0; fb < NFB; ++fb) {
 #pragma unroll
-            for (int fb = 0; fb < NFB; ++fb) {
-                float x = cur[j][fb] * rmask;
+            for (int j = 0; j < 8; ++j) {
+                const float rmask = (!decltype(masked)::value || c0 + 8 * q + j < m) ? 1.f : 0.f;
+                float x = fr[j][fb];
+                if (decltype(masked)::value) x *= rmask;
                 if (fb == NFB - 1) x *= col_mask_last;
-                if (fb == 0 && bias && r == 0) x = rmask;                       // column 0 reads as 1 (wmf_model.py:331)
+                if (fb == 0 && bias_lane) x = rmask;                            // column 0 reads as 1 (wmf_model.py:331)
                 const __bf16 h = (__bf16)x;
                 const float r1 = x - (float)h;
                 const __bf16 md = (__bf16)r1;
                 hi[fb][j] = h; mid[fb][j] = md; lo[fb][j] = (__bf16)(r1 - (float)md);
             }
         }
+    };
+    auto products = [&](const gram_bf16x8 (&hi)[NFB], const gram_bf16x8 (&mid)[NFB], const gram_bf16x8 (&lo)[NFB]) {
         // product-major within a block row: consecutive MFMAs write different accumulators (six in a row on one tile wait
         // for each other's result)
         int t0 = 0;
@@ -150,10 +166,29 @@ __device__ __forceinline__ void gram_body6(const float* __restrict__ Y, int64_t 
             for (int bj = bi; bj < NFB; ++bj) acc[t0 + bj - bi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hi[bi], hi[bj], acc[t0 + bj - bi], 0, 0, 0);
             t0 += NFB - bi;
         }
+    };
+    float cur[8][NFB], nxt[8][NFB];
+    int64_t c0 = 32 * step_lo;
+    if (c0 < m) {
+        load_blocks(c0, cur, 0, NFB);
+        for (; c0 + stride < m; c0 += stride) {
+            gram_bf16x8 hi[NFB], mid[NFB], lo[NFB];
+            load_blocks(c0 + stride, nxt, 0, NG1);
+            __builtin_amdgcn_sched_barrier(0);
+            split(c0, cur, std::false_type{}, hi, mid, lo);
+            __builtin_amdgcn_sched_barrier(0);
+            load_blocks(c0 + stride, nxt, NG1, NFB);
+            __builtin_amdgcn_sched_barrier(0);
+            products(hi, mid, lo);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int j = 0; j < 8; ++j)
+            for (int j = 0; j < 8; ++j)
 #pragma unroll
-            for (int fb = 0; fb < NFB; ++fb) cur[j][fb] = nxt[j][fb];
+                for (int fb = 0; fb < NFB; ++fb) cur[j][fb] = nxt[j][fb];
+        }
+        gram_bf16x8 hi[NFB], mid[NFB], lo[NFB];
+        split(c0, cur, std::true_type{}, hi, mid, lo);
+        products(hi, mid, lo);
     }
     float* out = partial + (int64_t)blockIdx.x * NT * 256;                     // partial layout: [wave][tile][reg][lane]
 #pragma unroll
@@ -668,20 +703,43 @@ __global__ __launch_bounds__(512) void transform6_kernel(const float* __restrict
     // feature 0 at position f - 1: column n of the matrix in LDS is column n + 1 of W when whitening (3), its row k is row k + 1
     // of W when the input is in those coordinates (4, the un-whitening); both mod f
     const bool roll_n = set_col0_one == 3, roll_k = set_col0_one == 4;
-    for (int e = tid; e < NP * KS; e += 512) {
-        const int n = e / KS, k = e % KS;
-        const int ns = (roll_n && n < f) ? (n + 1 == f ? 0 : n + 1) : n, ks = (roll_k && k < f) ? (k + 1 == f ? 0 : k + 1) : k;
-        const float v = (k < f && n < f) ? W[ks * ld + ns] : 0.f;
-        const __bf16 h = (__bf16)v;
-        const float r1 = v - (float)h;
-        const __bf16 md = (__bf16)r1;
-        Wt[e] = h;
-        Wt[NP * KS + e] = md;
-        Wt[2 * NP * KS + e] = (__bf16)(r1 - (float)md);
-        if (v != 0.f) nz[(k >> 5) * NFB + (n >> 4)] = 1;          // benign race: every writer stores 1
+    // One item = eight consecutive k of one column n: consecutive threads take consecutive n (each of the eight loads of a wave
+    // reads a contiguous stretch of a row of W), the eight loads are independent and unconditional (an element outside W reads
+    // W[0] and is replaced by zero), and the eight parts of a plane leave as one 16-byte LDS write.
+    typedef __bf16 stage_bf16x8 __attribute__((ext_vector_type(8)));
+    stage_bf16x8* Ws = reinterpret_cast<stage_bf16x8*>(Wt);       // 16-byte units, as Wl below
+    for (int it = tid; it < NP * (KS / 8); it += 512) {
+        const int k8 = it / NP, n = it - k8 * NP;                 // (NP is a constant: no divide)
+        // the roll without a test of the mode per element: position + 1, f wraps to 0 (without a roll, position f is outside W)
+        const int rn = roll_n ? 1 : 0, rk = roll_k ? 1 : 0;
+        const int ns = n + rn == f ? 0 : n + rn;
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int k = 8 * k8 + j;
+            const int ks = k + rk == f ? 0 : k + rk;
+            const bool in_w = k < f && n < f;
+            v[j] = W[in_w ? ks * ld + ns : 0];
+            if (!in_w) v[j] = 0.f;
+        }
+        stage_bf16x8 ph, pm, pl;
+        bool any = false;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const __bf16 h = (__bf16)v[j];
+            const float r1 = v[j] - (float)h;
+            const __bf16 md = (__bf16)r1;
+            ph[j] = h; pm[j] = md; pl[j] = (__bf16)(r1 - (float)md);
+            any |= v[j] != 0.f;
+        }
+        const int at = (n * KS + 8 * k8) / 8;
+        Ws[at] = ph;
+        Ws[NP * KS / 8 + at] = pm;
+        Ws[2 * NP * KS / 8 + at] = pl;
+        if (any) nz[(k8 >> 2) * NFB + (n >> 4)] = 1;               // benign race: every writer stores 1 (k8 >> 2 < NKC: k < f there)
     }
     __syncthreads();
-    const int lane = tid & 63, wv = tid >> 6;
+    const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);    // (scalar: a wave's block index and its tests are)
     const int r = lane & 15, q = lane >> 4;
     const int nch = ld >> 2;
     unsigned cmask[NKC];                         // per K chunk: output blocks with a non-zero tile of W
@@ -752,30 +810,40 @@ __global__ __launch_bounds__(512) void transform6_kernel(const float* __restrict
                 acc[nb] = cc;
             }
         }
-        // acc[nb][reg] = out[blk*16 + 4q + reg][16 nb + r]
+        // acc[nb][reg] = out[blk*16 + 4q + reg][16 nb + r].  Every output block but the last lies inside the row in every layout
+        // (its columns end at 16 (NFB - 1) - 1 < f - 1 <= wid): its store needs no column test; only the last block has columns
+        // past `wid` and, in the split layout, feature f - 1 that goes to the pairs.  Only the last block of a launch has rows
+        // past m: a full block (wave-uniform test) stores without a row test either -- a straight line but for the last nb.
+        // (3) bits 4 nb + 2 (r / 8) + r % 8 of the row's bias replace the last mantissa bit of body positions 8 j, 8 j + 1 (j < 16):
+        // the row kernels that hold 8 consecutive features per lane rebuild the bias from the row they gathered instead of fetching
+        // the pair (csrc/wmf_iter.hip); the value moves by at most one ulp.  A select, not a branch.
+        const int wid = sp ? f - 1 : ld;
+        const bool stuff = set_col0_one == 3 && (r & 7) < 2;
+        const int stuff_sh = 2 * (r >> 3) + (r & 7);
+        auto store_rows = [&](auto full) {
 #pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            const int64_t orow = blk * 16 + 4 * q + reg;
-            // (3) the bias of the output row, for its bits: it sits in lane 4 q + reg (q = 0 there)
-            const unsigned bbits = set_col0_one == 3 ? (unsigned)__builtin_amdgcn_ds_bpermute((4 * q + reg) * 4, __builtin_bit_cast(int, bias_of_row)) : 0u;
-            if (orow < m) {
-                // split layout: packed body rows of f - 1 floats, feature f - 1 goes to the pairs
-                const int wid = sp ? f - 1 : ld;
-                float* o = out + orow * (int64_t)wid;
+            for (int reg = 0; reg < 4; ++reg) {
+                const int64_t orow = blk * 16 + 4 * q + reg;
+                // (3) the bias of the output row, for its bits: it sits in lane 4 q + reg (q = 0 there)
+                const unsigned bbits = set_col0_one == 3 ? (unsigned)__builtin_amdgcn_ds_bpermute((4 * q + reg) * 4, __builtin_bit_cast(int, bias_of_row)) : 0u;
+                if (decltype(full)::value || orow < m) {
+                    float* o = out + orow * (int64_t)wid;
 #pragma unroll
-                for (int nb = 0; nb < NFB; ++nb) {
-                    const int col = 16 * nb + r;
-                    float v = acc[nb][reg];
-                    // (3) bit 2 (col / 8) + col % 8 of the row's bias replaces the last mantissa bit of body positions 8 j, 8 j + 1
-                    // (j < 16): the row kernels that hold 8 consecutive features per lane rebuild the bias from the row they
-                    // gathered instead of fetching the pair (csrc/wmf_iter.hip); the value moves by at most one ulp
-                    if (set_col0_one == 3 && col < 128 && (col & 7) < 2)
-                        v = __builtin_bit_cast(float, (__builtin_bit_cast(unsigned, v) & ~1u) | ((bbits >> (2 * (col >> 3) + (col & 7))) & 1u));
-                    if (col < wid) o[col] = v;
-                    else if (sp && col == f - 1) col0_out[2 * orow] = v;
+                    for (int nb = 0; nb < NFB; ++nb) {
+                        const int col = 16 * nb + r;
+                        float v = acc[nb][reg];
+                        if (16 * nb < 128) {
+                            const unsigned vb = __builtin_bit_cast(unsigned, v);
+                            v = __builtin_bit_cast(float, stuff ? ((vb & ~1u) | ((bbits >> (4 * nb + stuff_sh)) & 1u)) : vb);
+                        }
+                        if (nb < NFB - 1 || col < wid) o[col] = v;
+                        else if (sp && col == f - 1) col0_out[2 * orow] = v;
+                    }
                 }
             }
-        }
+        };
+        if (blk * 16 + 16 <= m) store_rows(std::true_type{});
+        else store_rows(std::false_type{});
     };
     // one block of pieces at a time (two, as in transform_kernel, spill at 256 registers: the bf16 parts need room).  Two
     // 16-row blocks per trip sharing every B operand read (twelve MFMAs per three ds_read_b128 instead of six) were measured in
@@ -790,11 +858,24 @@ __global__ __launch_bounds__(512) void transform6_kernel(const float* __restrict
     }
 }
 
+// The number of compute units of the current device, asked once (as WMF_LDS_CEILING asks once per kernel).
+static int wmf_cu_count() {
+    static const int n = [] {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
+        return cus > 0 ? cus : 256;
+    }();
+    return n;
+}
+
 template <int NFB>
 static void launch_transform6(const float* in, int64_t m, int f, int ld, const float* W, int set_col0_one, float* out,
                               float* col0_out, int64_t grid, int64_t nblk, hipStream_t st) {
     constexpr size_t lds = (size_t)3 * 16 * NFB * 176 * 2;
     static_assert(lds <= 158 * 1024, "W planes do not fit LDS");
+    // The three planes of W leave room for one workgroup per CU, and every workgroup splits W into them before its first block:
+    // one workgroup per CU stages W once per launch (the grid-stride loop of the kernel follows the grid).
+    if (grid > wmf_cu_count()) grid = wmf_cu_count();
     static const char* nm = wmf_kname("transform6_kernel<%d>", NFB);
     WMF_LAUNCH_LDS(nm, (transform6_kernel<NFB>), lds, dim3((unsigned)grid), dim3(512), lds, st, in, m, f, ld, W, set_col0_one, out,
                    col0_out, nblk);
