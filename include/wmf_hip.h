@@ -193,6 +193,43 @@ int wmf_rank_topn_batch(const float* users, const float* items, int f, int ld, i
                         int64_t n_users, const int32_t* cand_idx, int64_t n_cand, int64_t topn, int32_t* out_pos,
                         float* out_scores, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The topn best items of the WHOLE catalogue [0, n_items) for every user of a batch, leaving out the items the user has
+ * seen: what RecModel/utils.py:3-17 (test_coverage) asks of WMF.rank (wmf_model.py:25-47) with
+ * np.delete(arange(n_items), seen) as the candidates, for all users in one fused pass -- scores by f32 MFMA, a running
+ * top-n per user; nothing of size n_users x n_items is ever stored.
+ * Inputs: all arrays on the device, factors in the library's layout (ld % 4 == 0, zero padding).  user_idx[b] selects the
+ *   user row of batch position b; a user may occur several times.
+ * Seen list: seen_indptr is int64[n_users + 1]; row b of that CSR belongs to batch position b (not to the user id);
+ *   seen_indices are item ids in [0, n_items), ascending within a row, duplicates allowed; the CSR is read as stored.
+ *   seen_indptr == NULL: nothing is excluded.
+ * Order: a higher score wins, equal scores go to the lower item id (-0.0 and +0.0 are equal).
+ * Outputs: out_items[b * topn + k] = the k-th best item not in row b.  out_scores (may be NULL) = its score, the same
+ *   arithmetic as wmf_rank_topn_batch (bit for bit) and wmf_predict_pairs.  out_count[b] (may be NULL) = min(topn, eligible
+ *   items); entries past it hold item -1 and score -inf.
+ * Limits: 1 <= topn <= WMF_RECOMMEND_MAX_TOPN, n_users >= 1, 1 <= n_items < 2^31.
+ * Slices: the catalogue is scanned in n_slices contiguous slices whose partial results are merged, so that a handful of
+ *   users still fills the device; the result does not depend on n_slices.  0: the library chooses from n_users, n_items and
+ *   the device's CU count, at most WMF_RECOMMEND_AUTO_SLICES; 1 .. WMF_RECOMMEND_MAX_SLICES forces it (slices beyond the
+ *   number of 16-item tiles are empty).
+ * Workspace: wmf_recommend_workspace_bytes(n_users, topn, n_slices) bytes of device memory =
+ *   WMF_RECOMMEND_WS_BASE + WMF_RECOMMEND_WS_PER_KEY * n_users * topn * (n_slices, or WMF_RECOMMEND_AUTO_SLICES for 0):
+ *   it does not depend on n_items.
+ * The call only enqueues: it does not allocate, synchronise or read back (unlike wmf_rank_topn).  WMF_EINVAL, before any
+ * HIP call, for a bad shape, a null pointer, topn or n_slices out of range or a workspace that is too small.
+ * Factors are finite; infinite scores order as floats; NaN scores are unspecified, but every index written is in range. */
+#define WMF_RECOMMEND_MAX_TOPN 128
+#define WMF_RECOMMEND_MAX_SLICES 256
+#define WMF_RECOMMEND_AUTO_SLICES 64
+#define WMF_RECOMMEND_WS_BASE 256
+#define WMF_RECOMMEND_WS_PER_KEY 8
+int64_t wmf_recommend_workspace_bytes(int64_t n_users, int64_t topn, int32_t n_slices);
+int wmf_recommend_topn(const float* users, const float* items, int f, int ld, int bias,
+                       const int32_t* user_idx, int64_t n_users, int64_t n_items,
+                       const int64_t* seen_indptr, const int32_t* seen_indices,
+                       int64_t topn, int32_t n_slices,
+                       int32_t* out_items, float* out_scores, int32_t* out_count,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
 /* RecModel.eval_topn / compute_hit, base_model.py:51-148, for all test entries at once.
  * Test entry p = (pair_user[p], pair_item[p]); its user's random candidates are row pair_row[p] of
  * candidates[n_rows][n_cand] (item rows, drawn by the caller exactly as base_model.py:62-63 draws them) and

@@ -5,5 +5,7 @@
 """
 from .base_model import RecModel  # noqa: F401
 from .wmf_model import WMF  # noqa: F401
+from . import utils  # noqa: F401
+from .utils import test_coverage  # noqa: F401
 
-__all__ = ["WMF", "RecModel"]
+__all__ = ["WMF", "RecModel", "utils", "test_coverage"]

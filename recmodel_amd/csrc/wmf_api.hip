@@ -524,6 +524,30 @@ int wmf_rank_topn_batch(const float* users, const float* items, int f, int ld, i
     return check_launch("wmf_rank_topn_batch");
 }
 
+int64_t wmf_recommend_workspace_bytes(int64_t n_users, int64_t topn, int32_t n_slices) { return wmf_recommend_ws_bytes(n_users, topn, n_slices); }
+
+int wmf_recommend_topn(const float* users, const float* items, int f, int ld, int bias, const int32_t* user_idx, int64_t n_users,
+                       int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, int64_t topn, int32_t n_slices,
+                       int32_t* out_items, float* out_scores, int32_t* out_count, void* workspace, int64_t workspace_bytes, void* stream) {
+    int rc = check_shape(f, ld);
+    if (rc) return rc;
+    if (!users || !items || !user_idx || !out_items || !workspace) { wmf_set_error("wmf_recommend_topn: null pointer"); return WMF_EINVAL; }
+    if (n_users < 1 || n_items < 1 || n_items > 0x7fffffffLL || topn < 1 || topn > WMF_RECOMMEND_MAX_TOPN || n_slices < 0 ||
+        n_slices > WMF_RECOMMEND_MAX_SLICES) {
+        wmf_set_error("wmf_recommend_topn: need n_users >= 1, 1 <= n_items < 2^31, 1 <= topn <= %d, 0 <= n_slices <= %d (n_users=%lld, n_items=%lld, topn=%lld, n_slices=%d)",
+                      WMF_RECOMMEND_MAX_TOPN, WMF_RECOMMEND_MAX_SLICES, (long long)n_users, (long long)n_items, (long long)topn, (int)n_slices);
+        return WMF_EINVAL;
+    }
+    if (workspace_bytes < wmf_recommend_ws_bytes(n_users, topn, n_slices)) {
+        wmf_set_error("wmf_recommend_topn: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
+                      (long long)wmf_recommend_ws_bytes(n_users, topn, n_slices));
+        return WMF_EINVAL;
+    }
+    return launch_error(wmf_launch_recommend(users, items, ld, bias, user_idx, n_users, n_items, seen_indptr, seen_indices, topn, n_slices,
+                                             out_items, out_scores, out_count, workspace, (hipStream_t)stream),
+                        "wmf_recommend_topn", f, ld, "");
+}
+
 int wmf_hit_counts(const float* users, const float* items, int f, int ld, int bias, const int32_t* pair_user,
                    const int32_t* pair_item, const int32_t* pair_row, int64_t n_pairs, const int32_t* candidates,
                    int32_t n_cand, const int32_t* slot, const int32_t* topn, int32_t n_topn, int64_t* hits, void* stream) {

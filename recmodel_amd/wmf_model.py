@@ -32,6 +32,9 @@ def _csr_parts(mat):
 # result is rounded to the model's dtype where the reference rounds it.
 F64_ROW_WEIGHT = 1024.0
 
+RECOMMEND_BATCH_USERS = 4096      # users per wmf_recommend_topn call of WMF.recommend (its workspace is 8 x 64 x topn bytes a user)
+RECOMMEND_MAX_TOPN = 128          # WMF_RECOMMEND_MAX_TOPN of include/wmf_hip.h: beyond it recommend() ranks user by user
+
 
 def _transformed_dtype(count_dtype, alpha, beta, pre_process_count):
     """dtype of the confidence weights the reference ends up with (wmf_model.py:119-123), by NumPy's own rules."""
@@ -218,6 +221,77 @@ class WMF(RecModel):
             ph = pos.cpu().numpy().reshape(nu, keep)
             out.extend(items[ph[j]] for j in range(nu))
         return out
+
+    # ------------------------------------------------------------------ a11: recommend
+    def recommend(self, users, topn=10, exclude=None, return_scores=False):
+        """The ``topn`` best items of the whole catalogue for each of ``users`` (an int or a sequence of ints; negative
+        indices count from the end, as in ``predict``), best first, equal scores in item order.  ``exclude``: a SciPy sparse
+        matrix of shape [users of the model, items], e.g. the training matrix -- the stored entries of a user's row (stored
+        zeros too) are never recommended to that user.  This is ``rank(np.delete(arange(n_items), seen_u), u, topn)`` for every
+        user (RecModel/utils.py:3-17 on wmf_model.py:25-47) in one fused device pass per batch (wmf_recommend_topn).
+        Returns int64 [len(users), topn], padded with -1 where a user has fewer eligible items; with ``return_scores`` also
+        the float32 scores, padded with -inf.  An int user gives one row."""
+        n_users_model, n_items = self.users.shape[0], self.items.shape[0]
+        seen = None
+        if exclude is not None:
+            if not scipy.sparse.issparse(exclude) or exclude.shape != (n_users_model, n_items):
+                raise ValueError(f"exclude must be a sparse matrix of shape {(n_users_model, n_items)}, got {getattr(exclude, 'shape', None)}")
+        one = np.ndim(users) == 0
+        u = np.atleast_1d(np.asarray(users)).reshape(-1).astype(np.int64)
+        if len(u) and (u.min() < -n_users_model or u.max() >= n_users_model):
+            raise IndexError("user index out of bounds")
+        topn = int(topn)
+        if topn < 1:
+            raise ValueError(f"topn must be at least 1, not {topn}")
+        _lib.require_gpu()
+        u = np.where(u < 0, u + n_users_model, u)
+        out_items = np.full((len(u), topn), -1, dtype=np.int64)
+        out_scores = np.full((len(u), topn), -np.inf, dtype=np.float32)
+        if exclude is not None and len(u):
+            seen = scipy.sparse.csr_matrix(exclude)[u]            # the requested rows, a copy
+            seen.sort_indices()
+        if len(u) == 0:
+            pass
+        elif topn > RECOMMEND_MAX_TOPN:
+            # beyond the fused kernel's buffers: the reference's formulation, user by user
+            everything = np.arange(n_items, dtype=np.int32)
+            for j, user in enumerate(u):
+                cand = everything if seen is None else np.delete(everything, seen.indices[seen.indptr[j]:seen.indptr[j + 1]])
+                best = self.rank(cand, int(user), topn) if len(cand) else cand
+                out_items[j, :len(best)] = best
+                if return_scores and len(best):
+                    out_scores[j, :len(best)] = self.predict([int(user)], best)
+        else:
+            self._recommend_fused(u, topn, seen, out_items, out_scores if return_scores else None)
+        if one:
+            out_items, out_scores = out_items[0], out_scores[0]
+        return (out_items, out_scores) if return_scores else out_items
+
+    def _recommend_fused(self, u, topn, seen, out_items, out_scores):
+        """Batches of RECOMMEND_BATCH_USERS users, all enqueued on one stream; one copy to the host at the end."""
+        users_t, items_t, f, ld = self._device_factors()
+        lib = _lib.load()
+        n, n_items = len(u), self.items.shape[0]
+        ut = torch.from_numpy(u.astype(np.int32)).cuda()
+        items_d = torch.empty(n, topn, dtype=torch.int32, device="cuda")
+        scores_d = torch.empty(n, topn, dtype=torch.float32, device="cuda") if out_scores is not None else None
+        if seen is not None:
+            indptr_d = torch.from_numpy(seen.indptr.astype(np.int64)).cuda()
+            indices_d = torch.from_numpy(np.append(seen.indices, 0).astype(np.int32)).cuda()      # (one spare: never empty)
+        per = max(1, int(RECOMMEND_BATCH_USERS))
+        ws_bytes = int(lib.wmf_recommend_workspace_bytes(min(per, n), topn, 0))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+        for b0 in range(0, n, per):
+            nb = min(per, n - b0)
+            # row b of the batch's CSR = row b0 + b of `seen`: a window of its pointers, which index the one indices array
+            ptr_b = indptr_d[b0: b0 + nb + 1] if seen is not None else None
+            _lib.check(lib.wmf_recommend_topn(
+                _ptr(users_t), _ptr(items_t), f, ld, int(self.bias is True), _ptr(ut[b0:]), nb, n_items,
+                _ptr(ptr_b) if ptr_b is not None else None, _ptr(indices_d) if seen is not None else None, topn, 0,
+                _ptr(items_d[b0:]), _ptr(scores_d[b0:]) if scores_d is not None else None, None, _ptr(ws), ws_bytes, _stream()))
+        out_items[:] = items_d.cpu().numpy()
+        if out_scores is not None:
+            out_scores[:] = scores_d.cpu().numpy()
 
     def _hit_counts(self, pair_user, pair_item, pair_row, candidates, slot, topn):
         """compute_hit (base_model.py:51-98) for every test entry in one launch: wmf_hit_counts."""
