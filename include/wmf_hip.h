@@ -230,6 +230,49 @@ int wmf_recommend_topn(const float* users, const float* items, int f, int ld, in
                        int32_t* out_items, float* out_scores, int32_t* out_count,
                        void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The exact place of held-out items in the full-catalogue order of wmf_recommend_topn: the dual query of that entry point, not
+ * "which are the topn best" but "at which place does this item stand", for unsampled, train-excluded Recall / NDCG / ARHR
+ * (RecModel.eval_ranking; the reference offers only the sampled Recall@N of base_model.py:100-148).  One counting pass over the
+ * catalogue for the whole batch -- scores by f32 MFMA, integer counters; nothing of size n_rows x n_items is ever stored.
+ * Inputs: all arrays on the device, factors in the library's layout (ld % 4 == 0, zero padding).  A ROW is a batch position b:
+ *   a user (user_idx[b]; a user may occur in several rows), a seen list and a target list.
+ * Seen list: as for wmf_recommend_topn -- seen_indptr is int64[n_rows + 1], row b of that CSR belongs to batch position b;
+ *   seen_indices are item ids in [0, n_items), ascending within a row, duplicates allowed.  Both NULL: nothing is excluded.
+ * Targets: target_indptr is int64[n_rows + 1]; target_indices[target_indptr[b] .. target_indptr[b + 1]) are the item ids of row
+ *   b in [0, n_items), in any order, duplicates allowed.  out_rank and out_score are indexed like target_indices.
+ * Outputs, for target p of row b:
+ *   out_rank[p] = the number of items j of [0, n_items) that are not in row b's seen list and stand strictly above the target in
+ *     the order of wmf_recommend_topn (a higher score wins, equal scores go to the lower item id): the 0-based place of the
+ *     target in recommend(user, topn = n_items, exclude = seen).  The other targets of the row are ordinary items and are
+ *     counted; duplicate targets get the same rank.  For every k <= WMF_RECOMMEND_MAX_TOPN the target is among the first k
+ *     entries of wmf_recommend_topn for the same row exactly when 0 <= out_rank[p] < k.
+ *     WMF_RANKPOS_SEEN: the target is in the row's seen list and is never recommended.
+ *     WMF_RANKPOS_BEYOND: the target lies past the row's first WMF_RANKPOS_MAX_TARGETS targets and was not counted (split
+ *     the row; WMF.rank_positions does).
+ *   out_score[p] (may be NULL) = the target's score, bit for bit what wmf_recommend_topn and wmf_rank_topn_batch return for the
+ *     pair; written for WMF_RANKPOS_SEEN targets too, not for WMF_RANKPOS_BEYOND ones.
+ * Limits: n_rows >= 1, 1 <= n_items < 2^31.
+ * Slices: as for wmf_recommend_topn (0: the library chooses; 1 .. WMF_RECOMMEND_MAX_SLICES forces it); the counts are
+ *   integers, so the result does not depend on n_slices.
+ * Workspace: wmf_rank_positions_workspace_bytes(n_rows, n_targets, n_slices) bytes of device memory =
+ *   WMF_RANKPOS_WS_BASE + WMF_RANKPOS_WS_PER_ROW * n_rows: it depends neither on n_items nor, with the per-row limit, on the
+ *   number of targets or slices.
+ * The call only enqueues: it does not allocate, synchronise or read back.  WMF_EINVAL, before any HIP call, for a bad shape, a
+ * null pointer (seen_indptr and seen_indices: both or neither), n_slices out of range or a workspace that is too small.
+ * Factors are finite; NaN scores are unspecified, but every index read or written is in range. */
+#define WMF_RANKPOS_MAX_TARGETS 16
+#define WMF_RANKPOS_SEEN (-1)
+#define WMF_RANKPOS_BEYOND (-2)
+#define WMF_RANKPOS_WS_BASE 256
+#define WMF_RANKPOS_WS_PER_ROW 260
+int64_t wmf_rank_positions_workspace_bytes(int64_t n_rows, int64_t n_targets, int32_t n_slices);
+int wmf_rank_positions(const float* users, const float* items, int f, int ld, int bias,
+                       const int32_t* user_idx, int64_t n_rows, int64_t n_items,
+                       const int64_t* seen_indptr, const int32_t* seen_indices,
+                       const int64_t* target_indptr, const int32_t* target_indices,
+                       int32_t n_slices, int32_t* out_rank, float* out_score,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
 /* RecModel.eval_topn / compute_hit, base_model.py:51-148, for all test entries at once.
  * Test entry p = (pair_user[p], pair_item[p]); its user's random candidates are row pair_row[p] of
  * candidates[n_rows][n_cand] (item rows, drawn by the caller exactly as base_model.py:62-63 draws them) and

@@ -51,6 +51,9 @@ SIGNATURES = {
     "wmf_recommend_workspace_bytes": (c_i64, [c_i64, c_i64, c_int]),
     "wmf_recommend_topn": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp,
                                    c_vp, c_i64, c_vp]),
+    "wmf_rank_positions_workspace_bytes": (c_i64, [c_i64, c_i64, c_int]),
+    "wmf_rank_positions": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp,
+                                   c_vp, c_i64, c_vp]),
     "wmf_hit_counts": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),
     "wmf_spmm_rows": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp]),
     "wmf_gather_rows": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_vp]),

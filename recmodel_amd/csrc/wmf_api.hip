@@ -548,6 +548,35 @@ int wmf_recommend_topn(const float* users, const float* items, int f, int ld, in
                         "wmf_recommend_topn", f, ld, "");
 }
 
+int64_t wmf_rank_positions_workspace_bytes(int64_t n_rows, int64_t n_targets, int32_t n_slices) {
+    (void)n_targets; (void)n_slices;                              // (at most WMF_RANKPOS_MAX_TARGETS a row are counted, by atomics)
+    return wmf_rank_positions_ws_bytes(n_rows);
+}
+
+int wmf_rank_positions(const float* users, const float* items, int f, int ld, int bias, const int32_t* user_idx, int64_t n_rows,
+                       int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const int64_t* target_indptr,
+                       const int32_t* target_indices, int32_t n_slices, int32_t* out_rank, float* out_score, void* workspace,
+                       int64_t workspace_bytes, void* stream) {
+    int rc = check_shape(f, ld);
+    if (rc) return rc;
+    if (!users || !items || !user_idx || !target_indptr || !target_indices || !out_rank || !workspace || (!seen_indptr != !seen_indices)) {
+        wmf_set_error("wmf_rank_positions: null pointer (seen_indptr and seen_indices: both or neither)"); return WMF_EINVAL;
+    }
+    if (n_rows < 1 || n_items < 1 || n_items > 0x7fffffffLL || n_slices < 0 || n_slices > WMF_RECOMMEND_MAX_SLICES) {
+        wmf_set_error("wmf_rank_positions: need n_rows >= 1, 1 <= n_items < 2^31, 0 <= n_slices <= %d (n_rows=%lld, n_items=%lld, n_slices=%d)",
+                      WMF_RECOMMEND_MAX_SLICES, (long long)n_rows, (long long)n_items, (int)n_slices);
+        return WMF_EINVAL;
+    }
+    if (workspace_bytes < wmf_rank_positions_ws_bytes(n_rows)) {
+        wmf_set_error("wmf_rank_positions: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
+                      (long long)wmf_rank_positions_ws_bytes(n_rows));
+        return WMF_EINVAL;
+    }
+    return launch_error(wmf_launch_rank_positions(users, items, ld, bias, user_idx, n_rows, n_items, seen_indptr, seen_indices, target_indptr,
+                                                  target_indices, n_slices, out_rank, out_score, workspace, (hipStream_t)stream),
+                        "wmf_rank_positions", f, ld, "");
+}
+
 int wmf_hit_counts(const float* users, const float* items, int f, int ld, int bias, const int32_t* pair_user,
                    const int32_t* pair_item, const int32_t* pair_row, int64_t n_pairs, const int32_t* candidates,
                    int32_t n_cand, const int32_t* slot, const int32_t* topn, int32_t n_topn, int64_t* hits, void* stream) {

@@ -220,6 +220,11 @@ int64_t wmf_recommend_ws_bytes(int64_t n_users, int64_t topn, int32_t n_slices);
 int wmf_launch_recommend(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
                          int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, int64_t topn, int32_t n_slices,
                          int32_t* out_items, float* out_scores, int32_t* out_count, void* ws, hipStream_t st);
+// wmf_rankpos.hip: exact full-catalogue ranks of target items, seen items left out
+int64_t wmf_rank_positions_ws_bytes(int64_t n_rows);
+int wmf_launch_rank_positions(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_rows,
+                              int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const int64_t* target_indptr,
+                              const int32_t* target_indices, int32_t n_slices, int32_t* out_rank, float* out_score, void* ws, hipStream_t st);
 int wmf_launch_gather_rows(const float* in, int ld, const int64_t* rows, int64_t n, float* out, hipStream_t st);
 int wmf_launch_confidence(float* values, int64_t nnz, double alpha, double beta, int mode, hipStream_t st);
 // float64 half step of the cores > 1 variants (wmf_f64.hip)

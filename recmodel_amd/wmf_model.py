@@ -15,7 +15,7 @@ import scipy.sparse
 import torch
 
 from . import _lib
-from .base_model import RecModel
+from .base_model import RecModel, ranking_inputs
 from .engine import AlsEngine, _ptr, _stream
 
 
@@ -34,6 +34,7 @@ F64_ROW_WEIGHT = 1024.0
 
 RECOMMEND_BATCH_USERS = 4096      # users per wmf_recommend_topn call of WMF.recommend (its workspace is 8 x 64 x topn bytes a user)
 RECOMMEND_MAX_TOPN = 128          # WMF_RECOMMEND_MAX_TOPN of include/wmf_hip.h: beyond it recommend() ranks user by user
+RANKPOS_MAX_TARGETS = 16          # WMF_RANKPOS_MAX_TARGETS of include/wmf_hip.h: rank_positions() splits longer rows
 
 
 def _transformed_dtype(count_dtype, alpha, beta, pre_process_count):
@@ -292,6 +293,66 @@ class WMF(RecModel):
         out_items[:] = items_d.cpu().numpy()
         if out_scores is not None:
             out_scores[:] = scores_d.cpu().numpy()
+
+    # ------------------------------------------------------------------ a12: rank_positions
+    def rank_positions(self, test_mat, exclude=None, users=None, return_scores=False):
+        """The exact place of every held-out item in the user's full-catalogue order: for each stored entry (u, t) of
+        ``test_mat`` (stored zeros too) the number of items that ``u`` has no stored entry for in ``exclude`` and that
+        ``recommend`` puts before ``t`` -- a higher score, or an equal score and a lower id -- so ``t`` is among
+        ``recommend(u, k, exclude)`` exactly when ``0 <= rank < k``; -1 for a ``t`` that is itself in ``exclude``.  Both
+        matrices are SciPy sparse of shape [users of the model, items]; they are canonicalised on copies (CSR, duplicates
+        summed, indices sorted).  ``users``: the rows asked for (negative indices count from the end), default all rows
+        with stored entries.  Returns ``(indptr, indices, ranks)`` -- the CSR structure of the canonicalised
+        ``test_mat[users]`` and int64 ranks aligned with ``indices`` -- and with ``return_scores`` also the float32 scores.
+        One counting pass over the catalogue per batch of rows (wmf_rank_positions); nothing is sampled."""
+        u, test, seen = ranking_inputs(test_mat, exclude, users, (self.users.shape[0], self.items.shape[0]))
+        _lib.require_gpu()
+        indptr, indices = test.indptr.astype(np.int64), test.indices.astype(np.int64)
+        ranks, scores = np.empty(len(indices), dtype=np.int64), np.empty(len(indices), dtype=np.float32)
+        if len(indices):
+            # a row of the device call holds at most RANKPOS_MAX_TARGETS targets: longer rows of test_mat become several
+            per_user = np.diff(indptr)
+            n_sub = -(-per_user // RANKPOS_MAX_TARGETS)
+            owner = np.repeat(np.arange(len(u)), n_sub)            # the row of `test` a device row belongs to
+            first = np.concatenate([[0], np.cumsum(n_sub)])[:-1]
+            starts = indptr[owner] + RANKPOS_MAX_TARGETS * (np.arange(len(owner)) - first[owner])
+            target_indptr = np.append(starts, indptr[-1]).astype(np.int64)
+            seen_rows = seen[owner] if seen is not None else None
+            r, s = self._rank_positions_fused(u[owner], target_indptr, indices, seen_rows, return_scores)
+            ranks[:] = r
+            if return_scores:
+                scores[:] = s
+        return (indptr, indices, ranks, scores) if return_scores else (indptr, indices, ranks)
+
+    def _rank_positions_fused(self, u, target_indptr, target_indices, seen, want_scores):
+        """Batches of RECOMMEND_BATCH_USERS rows, all enqueued on one stream; one copy to the host at the end."""
+        users_t, items_t, f, ld = self._device_factors()
+        lib = _lib.load()
+        n, n_items = len(u), self.items.shape[0]
+        ut = torch.from_numpy(u.astype(np.int32)).cuda()
+        tptr_d = torch.from_numpy(target_indptr).cuda()
+        tidx_d = torch.from_numpy(np.append(target_indices, 0).astype(np.int32)).cuda()       # (one spare: never empty)
+        rank_d = torch.empty(len(target_indices), dtype=torch.int32, device="cuda")
+        score_d = torch.empty(len(target_indices), dtype=torch.float32, device="cuda") if want_scores else None
+        if seen is not None:
+            sptr_d = torch.from_numpy(seen.indptr.astype(np.int64)).cuda()
+            sidx_d = torch.from_numpy(np.append(seen.indices, 0).astype(np.int32)).cuda()
+        per = max(1, int(RECOMMEND_BATCH_USERS))
+        ws_bytes = int(lib.wmf_rank_positions_workspace_bytes(min(per, n), len(target_indices), 0))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+        for b0 in range(0, n, per):
+            nb = min(per, n - b0)
+            # row b of the batch = row b0 + b: windows of the pointers, which index the whole index and output arrays
+            _lib.check(lib.wmf_rank_positions(
+                _ptr(users_t), _ptr(items_t), f, ld, int(self.bias is True), _ptr(ut[b0:]), nb, n_items,
+                _ptr(sptr_d[b0: b0 + nb + 1]) if seen is not None else None, _ptr(sidx_d) if seen is not None else None,
+                _ptr(tptr_d[b0: b0 + nb + 1]), _ptr(tidx_d), 0, _ptr(rank_d), _ptr(score_d) if want_scores else None,
+                _ptr(ws), ws_bytes, _stream()))
+        return rank_d.cpu().numpy(), (score_d.cpu().numpy() if want_scores else None)
+
+    def _rank_positions(self, test_mat, exclude, users):
+        """eval_ranking's exact ranks from the device: rank_positions."""
+        return self.rank_positions(test_mat, exclude, users)
 
     def _hit_counts(self, pair_user, pair_item, pair_row, candidates, slot, topn):
         """compute_hit (base_model.py:51-98) for every test entry in one launch: wmf_hit_counts."""
