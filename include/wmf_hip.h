@@ -165,6 +165,41 @@ int wmf_eval_sqerr(const float* users, const float* items, int f, int ld, int bi
                    const int64_t* indptr, const int32_t* indices, const float* values,
                    int64_t n, double* out3, void* workspace, void* stream);
 
+/* ---- audit of a half step: its objective and the backward error of every row ------------------------------------------
+ * One pass over the CSR of the half step that updated side R (rows x_u, X [n, ld]) against the fixed side F (Y), in float64
+ * on the factors as stored and independent of every solver path.  The CSR is read as stored (stored zeros count, duplicates
+ * are separate entries).  With y~_i = row i of F with column 0 read as 1 when bias != 0 and beta_i = F[i, 0] when bias != 0,
+ * else 0 (wmf_model.py:253-257, :279, :328-343), every stored entry e = (u, i, c) has
+ *     w = c - beta_i,      s = x_u . y~_i over all f columns  (not predict: with biases x_u[0] multiplies the 1)
+ * and the call returns
+ *     out_sums = { S1 = sum_e (1 + w)(1 - s)^2,  S2 = sum_e s^2,  N = number of entries }
+ *     out_rows[u] = { |r_u|^2, |b_u|^2, a_u }   (squared 2-norms: integer inputs stay exact)
+ *         r_u = dense_u + sum_e [w s - (w + 1)] y~_i,   dense_u = (G~ + lambda I) x_u supplied by the caller,
+ *                                                       G~ = sum_i y~_i y~_i^T = what wmf_gram(bias) returns
+ *         b_u = sum_e (w + 1) y~_i,      a_u = sum_e |w| |y~_i|^2
+ * r_u = A_u x_u - b_u for the A_u, b_u of wmf_model.py:237-239 and :343-350, so
+ *     objective of the half step   L     = <X^T X, G~>_F + S1 - S2 + lambda |X|_F^2   (the first term: s^2 over ALL pairs; every
+ *                                          row of the reference's half step minimises its share of L)
+ *     normwise backward error      eta_u = |r_u| / ((|G~ + lambda I|_F + a_u) |x_u| + |b_u|), 0 when the denominator is 0.
+ * X is the block whose row u belongs to CSR row u (as in wmf_eval_sqerr); indptr may be a window into longer arrays (indices and
+ * values are then the whole arrays).  dense is double [n, f], row-major without padding; NULL with out_rows == NULL (objective
+ * only: no r / b work).  out_sums double[3], out_rows double[n, 3] or NULL, all on the device.
+ * One wave per row; rows above 4096 entries get a workgroup each in a second launch.  No floating-point atomics and fixed
+ * reduction orders: two runs give the same bits.
+ * workspace: wmf_audit_workspace_bytes(n) bytes of device memory.  The calls only enqueue.  WMF_EINVAL, before any HIP call, for
+ * a bad shape, a null pointer, out_rows without dense, or a workspace that is too small.
+ * wmf_half_step_audit_f64: the same arithmetic on dense float64 factors X [n, f], Y [m, f] and float64 values -- the layouts of
+ * wmf_half_step_f64. */
+int64_t wmf_audit_workspace_bytes(int64_t n);
+int wmf_half_step_audit(const float* X, const float* Y, int f, int ld, int bias,
+                        const int64_t* indptr, const int32_t* indices, const float* values, int64_t n,
+                        const double* dense, double* out_sums, double* out_rows,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+int wmf_half_step_audit_f64(const double* X, const double* Y, int f, int bias,
+                            const int64_t* indptr, const int32_t* indices, const double* values, int64_t n,
+                            const double* dense, double* out_sums, double* out_rows,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+
 /* out[p] = predict(users_idx[p], items_idx[p])   wmf_model.py:205-211.
  * n_u == 1 or n_i == 1 broadcasts that index (the reference's one-user / one-item form).
  * An empty side (n_u == 0 or n_i == 0, the other 0 or 1) has no pairs: WMF_OK, nothing is read or written. */

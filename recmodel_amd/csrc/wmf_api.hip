@@ -416,6 +416,41 @@ int wmf_eval_sqerr(const float* users, const float* items, int f, int ld, int bi
     return check_launch("wmf_eval_sqerr");
 }
 
+int64_t wmf_audit_workspace_bytes(int64_t n) { return wmf_audit_ws_bytes(n); }
+
+// the checks the two audit entry points share (before any HIP call)
+static int check_audit(const char* what, const void* X, const void* Y, const void* indptr, const void* indices, const void* values, int64_t n,
+                       const double* dense, const double* out_sums, const double* out_rows, const void* workspace, int64_t workspace_bytes) {
+    if (!X || !Y || !indptr || !indices || !values || !out_sums || !workspace) { wmf_set_error("%s: null pointer", what); return WMF_EINVAL; }
+    if (n < 0 || n > 0x7fffffffLL) { wmf_set_error("%s: n=%lld outside [0, 2^31)", what, (long long)n); return WMF_EINVAL; }
+    if (out_rows && !dense) { wmf_set_error("%s: out_rows needs the dense term X (G~ + lambda I)", what); return WMF_EINVAL; }
+    if (workspace_bytes < wmf_audit_ws_bytes(n)) {
+        wmf_set_error("%s: workspace too small (%lld < %lld bytes)", what, (long long)workspace_bytes, (long long)wmf_audit_ws_bytes(n));
+        return WMF_EINVAL;
+    }
+    return WMF_OK;
+}
+
+int wmf_half_step_audit(const float* X, const float* Y, int f, int ld, int bias, const int64_t* indptr, const int32_t* indices,
+                        const float* values, int64_t n, const double* dense, double* out_sums, double* out_rows, void* workspace,
+                        int64_t workspace_bytes, void* stream) {
+    int rc = check_shape(f, ld);
+    if (rc) return rc;
+    if ((rc = check_audit("wmf_half_step_audit", X, Y, indptr, indices, values, n, dense, out_sums, out_rows, workspace, workspace_bytes))) return rc;
+    return launch_error(wmf_launch_audit(X, Y, f, ld, bias != 0, indptr, indices, values, n, dense, out_sums, out_rows, workspace,
+                                         (hipStream_t)stream), "wmf_half_step_audit", f, ld, "");
+}
+
+int wmf_half_step_audit_f64(const double* X, const double* Y, int f, int bias, const int64_t* indptr, const int32_t* indices,
+                            const double* values, int64_t n, const double* dense, double* out_sums, double* out_rows, void* workspace,
+                            int64_t workspace_bytes, void* stream) {
+    if (f < 1 || f > WMF_MAX_F) { wmf_set_error("wmf_half_step_audit_f64: factor width f=%d outside [1, %d]", f, WMF_MAX_F); return WMF_EINVAL; }
+    int rc = check_audit("wmf_half_step_audit_f64", X, Y, indptr, indices, values, n, dense, out_sums, out_rows, workspace, workspace_bytes);
+    if (rc) return rc;
+    return launch_error(wmf_launch_audit_f64(X, Y, f, bias != 0, indptr, indices, values, n, dense, out_sums, out_rows, workspace,
+                                             (hipStream_t)stream), "wmf_half_step_audit_f64", f, f, "");
+}
+
 int wmf_predict_pairs(const float* users, const float* items, int f, int ld, int bias, const int32_t* users_idx,
                       int64_t n_u, const int32_t* items_idx, int64_t n_i, float* out, void* stream) {
     int rc = check_shape(f, ld);

@@ -8,6 +8,7 @@
 
 #define WMF_GRAM_MAX_WAVES 4096
 #define WMF_EVAL_MAX_BLOCKS 2048
+#define WMF_AUDIT_MAX_BLOCKS 2048
 #define WMF_HEAVY_T 4096      /* rows with more stored entries are accumulated by several waves ... */
 #define WMF_SEG 2048          /* ... in segments of this many entries */
 #define WMF_WIDE_LU_GRID 64   /* workgroups (and workspace slices) of the pivoted-LU fallback for f > 144 */
@@ -202,6 +203,12 @@ int wmf_launch_spmm(const float* V, const int64_t* indptr, const int32_t* indice
 int wmf_launch_eval(const float* users, const float* items, int f, int ld, int bias, const int64_t* indptr,
                     const int32_t* indices, const float* values, int64_t n, double* out3, double* partial,
                     hipStream_t st);
+// wmf_audit.hip: objective sums and per-row backward-error terms of a half step, float32 and float64 factors
+int64_t wmf_audit_ws_bytes(int64_t n);
+int wmf_launch_audit(const float* X, const float* Y, int f, int ld, int bias, const int64_t* indptr, const int32_t* indices,
+                     const float* values, int64_t n, const double* dense, double* out_sums, double* out_rows, void* ws, hipStream_t st);
+int wmf_launch_audit_f64(const double* X, const double* Y, int f, int bias, const int64_t* indptr, const int32_t* indices,
+                         const double* values, int64_t n, const double* dense, double* out_sums, double* out_rows, void* ws, hipStream_t st);
 int wmf_launch_predict(const float* users, const float* items, int f, int ld, int bias, const int32_t* ui, int64_t n_u,
                        const int32_t* ii, int64_t n_i, float* out, hipStream_t st);
 int wmf_launch_hits(const float* users, const float* items, int ld, int bias, const int32_t* pair_user,

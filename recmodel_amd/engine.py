@@ -166,6 +166,20 @@ class HipKernels:
         _lib.check(self.lib.wmf_eval_sqerr(_ptr(users), _ptr(items), f, ld, int(bias), _ptr(indptr), _ptr(indices),
                                            _ptr(values), n, _ptr(out3), _ptr(ws), _stream()))
 
+    def audit_workspace_bytes(self, n):
+        return int(self.lib.wmf_audit_workspace_bytes(n))
+
+    def half_step_audit(self, X, Y, f, ld, bias, indptr, indices, values, n, dense, out_sums, out_rows, ws):
+        """Objective sums {S1, S2, N} and, with out_rows, {|r_u|^2, |b_u|^2, a_u} per row of a half step, in float64 on the
+        float32 factors as stored (include/wmf_hip.h, wmf_half_step_audit).  indptr may be a window into longer arrays."""
+        _lib.check(self.lib.wmf_half_step_audit(_ptr(X), _ptr(Y), f, ld, int(bias), _ptr(indptr), _ptr(indices), _ptr(values), n,
+                                                _ptr(dense), _ptr(out_sums), _ptr(out_rows), _ptr(ws), ws.numel(), _stream()))
+
+    def half_step_audit_f64(self, X, Y, f, bias, indptr, indices, values, n, dense, out_sums, out_rows, ws):
+        """The same on dense float64 factors [., f] and float64 values (the layouts of half_step_f64)."""
+        _lib.check(self.lib.wmf_half_step_audit_f64(_ptr(X), _ptr(Y), f, int(bias), _ptr(indptr), _ptr(indices), _ptr(values), n,
+                                                    _ptr(dense), _ptr(out_sums), _ptr(out_rows), _ptr(ws), ws.numel(), _stream()))
+
     def coo_to_csr(self, rows, cols, vals, n_rows, n_cols):
         """(indptr int64, indices int32, values) of the entries sorted stably by (row, column): wmf_coo_to_csr."""
         nnz = rows.numel()
@@ -258,6 +272,47 @@ def coo_to_csr(rows, cols, vals, n_rows, kernels=None, n_cols=None):
     indptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=rows.device)
     torch.cumsum(counts, 0, out=indptr[1:])
     return indptr, cols[order].to(torch.int32), vals[order]
+
+
+AUDIT_CHUNK_ROWS = 1 << 20      # rows per kernel call of an audit: bounds its float64 dense term and its workspace
+
+
+def audit_pass(kernel, K, X, Y, f, bias, gamma, G_fixed, indptr, indices, values, n, rows, chunk_rows=None):
+    """The device pass of an audit over the n rows of one CSR (the caller has the Gramians): ``kernel`` is
+    K.half_step_audit(X, Y, f, ld, ...) or K.half_step_audit_f64(X, Y, f, ...) with everything in front of ``bias`` bound.
+    X [>= n, >= f] is the updated side's block, G_fixed the float64 [f, f] Gramian G~ of the fixed side.  The dense term
+    X (G~ + gamma I) is a float64 matmul over chunks of at most AUDIT_CHUNK_ROWS rows, and the kernel is called per chunk
+    through a window of indptr.  Returns (float64 [3] = S1, S2, N on the device, eta float64 [n] or None)."""
+    dev = X.device
+    chunk_rows = max(1, int(chunk_rows or AUDIT_CHUNK_ROWS))
+    A = G_fixed.reshape(f, f) + float(gamma) * torch.eye(f, dtype=torch.float64, device=dev)
+    norm_a = torch.linalg.matrix_norm(A)
+    ws = torch.empty(K.audit_workspace_bytes(min(chunk_rows, max(n, 1))), dtype=torch.uint8, device=dev)
+    sums = torch.zeros(max(1, -(-n // chunk_rows)), 3, dtype=torch.float64, device=dev)
+    eta = torch.zeros(n, dtype=torch.float64, device=dev) if rows else None
+    if n <= 0:
+        return sums.sum(0), eta
+    for c, lo in enumerate(range(0, n, chunk_rows)):
+        ln = min(chunk_rows, n - lo)
+        xc = X[lo: lo + ln]
+        dense = out_rows = None
+        if rows:
+            x64 = xc[:, :f].to(torch.float64)
+            dense = (x64 @ A).contiguous()
+            out_rows = torch.empty(ln, 3, dtype=torch.float64, device=dev)
+        kernel(xc, bias, indptr[lo: lo + ln + 1], indices, values, ln, dense, sums[c], out_rows, ws)
+        if rows:
+            den = (norm_a + out_rows[:, 2]) * torch.linalg.vector_norm(x64, dim=1) + torch.sqrt(out_rows[:, 1])
+            eta[lo: lo + ln] = torch.where(den > 0, torch.sqrt(out_rows[:, 0]) / torch.where(den > 0, den, torch.ones_like(den)),
+                                           torch.zeros_like(den))
+    return sums.sum(0), eta
+
+
+def audit_result(all_pairs, sums, reg):
+    """The dict AlsEngine.audit returns, from <X^T X, G~>_F, the (all-reduced) {S1, S2, N} and gamma |X|_F^2."""
+    s1, s2, cnt = (float(v) for v in sums)
+    return {"loss": float(all_pairs) + s1 - s2 + float(reg), "all_pairs": float(all_pairs), "stored": s1 - s2, "reg": float(reg),
+            "n_stored": int(round(cnt))}
 
 
 MIN_CHUNK_ROWS = 32768          # default chunking never makes chunks smaller than this
@@ -1065,6 +1120,39 @@ class AlsEngine:
         if self.exchange:
             torch.distributed.all_reduce(self.eval_out, group=self.group)
         return tuple(float(x) for x in self.eval_out.cpu())
+
+    # ---------------------------------------------------------------- audit
+    def audit(self, side, rows=False):
+        """The objective the half step of ``side`` minimises -- the implicit-feedback loss over ALL pairs of this side's rows
+        and the fixed side's, L = <X^T X, G~>_F + S1 - S2 + gamma |X|_F^2 (include/wmf_hip.h, wmf_half_step_audit) -- on the
+        factors as they stand, in float64 and independent of the solver kernels; all-reduced over ranks.  Returns
+        {"loss", "all_pairs", "stored", "reg", "n_stored"}; with rows=True also "eta", the normwise backward error of the
+        normal equations of every row of this rank (float64 [n_local], local-row order).  Sides whose half step runs in
+        reduce or pipelined mode are not supported."""
+        for mode, on in (("reduce", self.reduce[side]), ("pipelined", self.pipe[side])):
+            if on:
+                raise NotImplementedError(f"audit({side!r}): the half step of this side runs in {mode} mode, which the audit does not support")
+        K, f = self.K, self.f
+        fixed = self._other(side)
+        self._ensure_gathered(fixed)
+        G = torch.zeros(2, f * f, dtype=torch.float64, device=self.device)
+        K.gram(self.factors[fixed], self.n_local[fixed], f, self.ld, self.bias, G[0], self.ws)      # G~ (as prepare does)
+        K.gram(self.factors[side], self.n_local[side], f, self.ld, False, G[1], self.ws)            # X^T X, plain
+        if self.exchange:
+            torch.distributed.all_reduce(G, group=self.group)
+        all_pairs = (G[0] * G[1]).sum()
+        reg = self.gamma * G[1].reshape(f, f).diagonal().sum()
+        csr = self.csr[side]
+        Y = self.X[fixed]
+        kernel = lambda xc, *rest: K.half_step_audit(xc, Y, f, self.ld, *rest)  # noqa: E731
+        sums, eta = audit_pass(kernel, K, self.factors[side], Y, f, self.bias, self.gamma, G[0], csr.indptr, csr.indices, csr.values,
+                               self.n_local[side], rows)
+        if self.exchange:
+            torch.distributed.all_reduce(sums, group=self.group)
+        out = audit_result(all_pairs.cpu(), sums.cpu(), reg.cpu())
+        if rows:
+            out["eta"] = eta
+        return out
 
     # ---------------------------------------------------------------- roofline bookkeeping
     def algorithmic_bytes_half(self, side):

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from .base_model import RecModel, ranking_inputs
-from .engine import AlsEngine, _ptr, _stream
+from .engine import AlsEngine, _ptr, _stream, audit_pass, audit_result
 
 
 def _csr_parts(mat):
@@ -42,6 +42,23 @@ def _transformed_dtype(count_dtype, alpha, beta, pre_process_count):
     probe = np.ones(1, dtype=count_dtype)
     with np.errstate(all="ignore"):
         return (alpha * np.log(1 + beta * probe)).dtype if pre_process_count == 'log' else (alpha * probe).dtype
+
+
+def audit_f64(K, X, Y, bias, gamma, indptr, indices, values, rows=False):
+    """AlsEngine.audit for dense float64 device factors X [n, f] (the updated side), Y [m, f] and float64 CSR values: the two
+    Gramians by float64 matmul, the pass over the CSR by wmf_half_step_audit_f64."""
+    f = X.shape[1]
+    Yt = Y
+    if bias:
+        Yt = Y.clone()
+        Yt[:, 0] = 1.0
+    G_fixed, G_side = Yt.T @ Yt, X.T @ X
+    kernel = lambda xc, *rest: K.half_step_audit_f64(xc, Y, f, *rest)  # noqa: E731
+    sums, eta = audit_pass(kernel, K, X, Y, f, bias, gamma, G_fixed, indptr, indices, values, X.shape[0], rows)
+    out = audit_result((G_fixed * G_side).sum().cpu(), sums.cpu(), (gamma * G_side.diagonal().sum()).cpu())
+    if rows:
+        out["eta"] = eta
+    return out
 
 
 class _Float64Steps:
@@ -75,9 +92,20 @@ class _Float64Steps:
         self.K.half_step_f64(Y, Y.shape[0], self.f, self.bias, indptr, indices, vals, n, self.gamma, out, self.ws, self.fail)
         self.X[side] = out.to(torch.float32).to(torch.float64) if self.store_float32 else out
 
-    def iteration(self):
+    def audit(self, side, rows=False):
+        """AlsEngine.audit on this object's float64 tensors (wmf_half_step_audit_f64)."""
+        fixed = "items" if side == "users" else "users"
+        indptr, indices, vals, n = self.csr[side]
+        return audit_f64(self.K, self.X[side], self.X[fixed], self.bias, self.gamma, indptr, indices, vals, rows)
+
+    def iteration(self, track=None):
+        """track: a dict that receives the objective of each half step right after it (train(track_objective=True))."""
         self._half("users", "items")
+        if track is not None:
+            track["users"] = self.audit("users")
         self._half("items", "users")
+        if track is not None:
+            track["items"] = self.audit("items")
         fail = int(self.fail[0])
         if fail:
             self.fail.zero_()
@@ -395,6 +423,60 @@ class WMF(RecModel):
             setattr(self, s, eng.get_factors(s).astype(self.dtype, copy=False))
         self._freeze()
 
+    # ------------------------------------------------------------------ a13: objective and per-row backward errors
+    def objective(self, count_mat, side="users", alpha=10, beta=1, pre_process_count='log'):
+        """The function the half step of ``side`` minimises, on the model's factors as they stand: the implicit-feedback
+        objective over ALL (user, item) pairs with the confidences ``train`` builds from ``count_mat`` (a copy is transformed
+        as there, wmf_model.py:119-123; ``side="items"`` reads count_mat.T.tocsr(), :128), in float64 on the device.
+        Returns {"loss", "all_pairs", "stored", "reg", "n_stored"}: loss = all_pairs + stored + reg, the square of the score over
+        all pairs, the stored entries' correction and gamma |X|_F^2 of ``side``.  Without biases, loss + gamma |F|_F^2 of
+        the other side is the same number from either side (the Hu-Koren-Volinsky objective)."""
+        return self._audit(count_mat, side, alpha, beta, pre_process_count, False)
+
+    def row_backward_errors(self, count_mat, side="users", alpha=10, beta=1, pre_process_count='log'):
+        """For every row of ``side`` the normwise backward error of its normal equations A_u x_u = b_u (wmf_model.py:237-239 /
+        :343-350) at the model's factors: |A_u x_u - b_u| / ((|G~ + gamma I|_F + a_u) |x_u| + |b_u|), float64 [n_side]; a row
+        the half step solved to working precision is at the unit roundoff of the factors' dtype."""
+        return self._audit(count_mat, side, alpha, beta, pre_process_count, True)
+
+    def _audit(self, count_mat, side, alpha, beta, pre_process_count, rows):
+        if self.weighted is not True:
+            raise ValueError("the objective and the row systems are those of the weighted branch (weighted=True)")
+        if side not in ("users", "items"):
+            raise ValueError(f"side must be 'users' or 'items', not {side!r}")
+        if pre_process_count not in ('log', 'linear'):
+            raise ValueError(f"Pre_process_count {pre_process_count} is not implement please use log or linear.")
+        if self.users is None:
+            raise ValueError("the model has no user factors yet: train it first")
+        shape = (self.users.shape[0], self.items.shape[0])
+        if not scipy.sparse.issparse(count_mat) or count_mat.shape != shape:
+            raise ValueError(f"count_mat must be a sparse matrix of shape {shape}, got {getattr(count_mat, 'shape', None)}")
+        if self.users.shape[1] != self.items.shape[1]:
+            raise ValueError(f"users and items have different widths: {self.users.shape[1]} and {self.items.shape[1]}")
+        _lib.require_gpu()
+        bias = self.bias is True
+        mode = 0 if pre_process_count == 'log' else 1
+        if self.users.dtype == np.float64 or self.items.dtype == np.float64:
+            K = self._new_engine().K
+            mat = scipy.sparse.csr_matrix(count_mat)
+            mat = mat if side == "users" else mat.T.tocsr()
+            fixed = "items" if side == "users" else "users"
+            dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).cuda()  # noqa: E731
+            vals = dev(mat.data, np.float64)
+            K.confidence_transform(vals, alpha, beta, mode)
+            out = audit_f64(K, dev(getattr(self, side), np.float64), dev(getattr(self, fixed), np.float64), bias, float(self.gamma),
+                            dev(mat.indptr, np.int64), dev(mat.indices, np.int32), vals, rows)
+        else:
+            eng = self._new_engine()
+            eng.set_factors("users", self.users)
+            eng.set_factors("items", self.items)
+            indptr, indices, values = _csr_parts(count_mat)
+            values = values.to(eng.device)
+            eng.K.confidence_transform(values, alpha, beta, mode)
+            eng.set_interactions(indptr, indices, values)
+            out = eng.audit(side, rows)
+        return out.pop("eta").cpu().numpy() if rows else out
+
     # ------------------------------------------------------------------ a3 / a4: operator seam
     def recompute_factors(self, Y, C, lambda_reg):
         """X_new for fixed factors Y and CSR C.  wmf_model.py:213-240 (host buffers in, host out)."""
@@ -452,9 +534,10 @@ class WMF(RecModel):
     # ------------------------------------------------------------------ a2: train
     def train(self, utility_mat, iterations, verbose=0, eval_mat=None, count_mat=None, alpha=10,
               cores=4, stopping_rounds=3, dtype='float64', min_improvement=0.0001,
-              pre_process_count='log', beta=1, preprocess_mat=False):
+              pre_process_count='log', beta=1, preprocess_mat=False, track_objective=False):
         """Alternating least squares with early stopping on eval MSE.  wmf_model.py:49-189.
-        Returns the index of the last iteration run."""
+        Returns the index of the last iteration run.  track_objective (weighted branch): ``self.objective_history`` gets one
+        {"iteration", "users", "items"} per iteration -- the objective of each half step right after it (``objective``)."""
         utility_mat = utility_mat.copy()
         if count_mat is not None:
             count_mat = count_mat.copy()
@@ -547,7 +630,19 @@ class WMF(RecModel):
             if verbose > 0:
                 print(f"Starting fitting iteration {iter}")
             start = time.time()
-            if f64 is not None:
+            if track_objective:
+                if iter == 0:
+                    self.objective_history = []
+                track = {"iteration": iter}
+                if f64 is not None:
+                    f64.iteration(track)
+                else:
+                    for side in ("users", "items"):
+                        eng.half_step(side)
+                        track[side] = eng.audit(side)
+                    eng.check_numerics()
+                self.objective_history.append(track)
+            elif f64 is not None:
                 f64.iteration()
             else:
                 eng.half_step("users")
