@@ -58,6 +58,16 @@ static int check_shape(int f, int ld) {
     return WMF_OK;
 }
 
+// The number of compute units of the current device, asked once (as WMF_LDS_CEILING asks once per kernel).
+int wmf_cu_count() {
+    static const int n = [] {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
+        return cus > 0 ? cus : 256;
+    }();
+    return n;
+}
+
 // ---- per-kernel event timing ------------------------------------------------------------------
 // Launch sites bracket every kernel with two events on its own stream (WMF_LAUNCH / WmfProfScope) while profiling is on.
 // wmf_profile_collect() waits for the events and folds them into a table keyed by (kernel symbol, tag); the tag is

@@ -858,16 +858,6 @@ __global__ __launch_bounds__(512) void transform6_kernel(const float* __restrict
     }
 }
 
-// The number of compute units of the current device, asked once (as WMF_LDS_CEILING asks once per kernel).
-static int wmf_cu_count() {
-    static const int n = [] {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
-        return cus > 0 ? cus : 256;
-    }();
-    return n;
-}
-
 template <int NFB>
 static void launch_transform6(const float* in, int64_t m, int f, int ld, const float* W, int set_col0_one, float* out,
                               float* col0_out, int64_t grid, int64_t nblk, hipStream_t st) {

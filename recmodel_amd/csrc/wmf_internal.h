@@ -227,6 +227,8 @@ int64_t wmf_recommend_ws_bytes(int64_t n_users, int64_t topn, int32_t n_slices);
 int wmf_launch_recommend(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
                          int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, int64_t topn, int32_t n_slices,
                          int32_t* out_items, float* out_scores, int32_t* out_count, void* ws, hipStream_t st);
+// (the slices of a scan over n_items for n_users rows: n_slices itself, or the automatic choice for 0; wmf_rankpos.hip cuts alike)
+int wmf_recommend_slices(int64_t n_users, int64_t n_items, int64_t topn, int32_t n_slices);
 // wmf_rankpos.hip: exact full-catalogue ranks of target items, seen items left out
 int64_t wmf_rank_positions_ws_bytes(int64_t n_rows);
 int wmf_launch_rank_positions(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_rows,
@@ -245,6 +247,7 @@ int wmf_launch_iter64(const double* V, const double* Y, int f, int bias, const i
                       const double* vals, int64_t n, int low, double* gout, int32_t* state, const int32_t* ctrl, hipStream_t st);
 
 void wmf_set_error(const char* fmt, ...);
+int wmf_cu_count();                              // compute units of the current device (wmf_api.hip)
 // Ablation switches whose results are WRONG (WMF_DBG_NO_ELIMINATION, _NO_ACCUMULATION, _NO_TILE_INVERSE) are compiled
 // into a -DWMF_LAB build only; the shipped library has no such code path.
 #ifdef WMF_LAB

@@ -14,6 +14,7 @@
 
 #include "wmf_common.h"
 #include "wmf_internal.h"
+#include "wmf_scan.h"
 
 // same arithmetic as pair_score() in wmf_eval.hip (kept in step with it: eval_prec, predict and rank must agree)
 __device__ __forceinline__ float rank_pair_score(const float* __restrict__ xu, const float* __restrict__ yi, int nch, int gl,
@@ -57,7 +58,8 @@ __global__ __launch_bounds__(256) void hit_kernel(const float* __restrict__ user
 
 // ---- batched rank: many users against one candidate list ------------------------------------------------
 // scores[u][c] for 16 users x 16 candidates per wave by f32 MFMA: both operands are row gathers of 16-byte pieces
-// (lane (r, q) reads piece 4 kk + q of user r and of candidate r), exactly the S = V V^T pattern of wmf_solve.hip.
+// (lane (r, q) reads piece 4 kk + q of user r and of candidate r), exactly the S = V V^T pattern of wmf_solve.hip: wmf_score_tile
+// (wmf_scan.h), which the catalogue scans and their per-row kernels share.
 // bias: the column-0 product is left out and users[u][0] + items[c][0] added (wmf_model.py:209-211).
 __global__ __launch_bounds__(256) void score_tile_kernel(const float* __restrict__ users, const float* __restrict__ items, int ld,
                                                          int bias, const int32_t* __restrict__ user_idx, int64_t nu,
@@ -71,34 +73,25 @@ __global__ __launch_bounds__(256) void score_tile_kernel(const float* __restrict
         const int64_t uu = min(16 * tu + r, nu - 1), cc = min(16 * tc + r, nc - 1);          // clamped: stores are masked
         const float4* urow = reinterpret_cast<const float4*>(users + (int64_t)user_idx[uu] * ld);
         const float4* irow = reinterpret_cast<const float4*>(items + (int64_t)cand_idx[cc] * ld);
-        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-        float ub = 0.f, ib = 0.f;
-        for (int c = q; c < ((nch + 3) & ~3); c += 4) {           // uniform trip count; pieces past the row are zero
-            float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-            if (c < nch) { a = urow[c]; b = irow[c]; }
-            if (bias && c == 0) { ub = a.x; ib = b.x; a.x = 0.f; }
-            acc = WMF_MFMA16(a.x, b.x, acc); acc = WMF_MFMA16(a.y, b.y, acc);
-            acc = WMF_MFMA16(a.z, b.z, acc); acc = WMF_MFMA16(a.w, b.w, acc);
-        }
-        // acc[reg] = score(user 16 tu + 4 q + reg, candidate 16 tc + r); the biases sit in the q = 0 lanes
-        const float ibr = __shfl(ib, r);                           // item bias of candidate r
+        const WmfScoreTile t = wmf_score_tile(urow, irow, nch, bias, q);
+        // t.acc[reg] = score(user 16 tu + 4 q + reg, candidate 16 tc + r); the biases sit in the q = 0 lanes
+        const float ibr = __shfl(t.ib, r);                         // item bias of candidate r
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
-            const float ubr = __shfl(ub, 4 * q + reg);             // user bias of user 4 q + reg
+            const float ubr = __shfl(t.ub, 4 * q + reg);           // user bias of user 4 q + reg
             const int64_t urow_i = 16 * tu + 4 * q + reg, ccol = 16 * tc + r;
-            if (urow_i < nu && ccol < nc) scores[urow_i * nc + ccol] = acc[reg] + (bias ? ubr + ibr : 0.f);
+            if (urow_i < nu && ccol < nc) scores[urow_i * nc + ccol] = t.acc[reg] + (bias ? ubr + ibr : 0.f);
         }
     }
 }
 
-// 64-bit sort keys of the batch: (user slot << 32) | ~rank_key(score): ascending order = users in order, each user's candidates by
+// 64-bit sort keys of the batch: (user slot << 32) | ~wmf_float_key(score): ascending order = users in order, each user's candidates by
 // descending score; the stable sort keeps equal scores in candidate order.  Payload = the candidate's position.
-__device__ __forceinline__ uint32_t rank_key(float s);
 __global__ void batch_keys_kernel(const float* __restrict__ scores, unsigned long long* __restrict__ keys, uint32_t* __restrict__ pos,
                                   int64_t nu, int64_t nc) {
     const int64_t n = nu * nc;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        keys[i] = ((unsigned long long)(i / nc) << 32) | (unsigned long long)(~rank_key(scores[i]));
+        keys[i] = ((unsigned long long)(i / nc) << 32) | (unsigned long long)(~wmf_float_key(scores[i]));
         pos[i] = (uint32_t)(i % nc);
     }
 }
@@ -110,8 +103,8 @@ __global__ void take_top_kernel(const uint32_t* __restrict__ spos, const unsigne
         const int64_t u = i / topn, k = i % topn;
         out_pos[i] = (int32_t)spos[u * nc + k];
         if (out_scores) {
-            const uint32_t key = ~(uint32_t)(skeys[u * nc + k] & 0xFFFFFFFFull);           // rank_key of the score, undone
-            out_scores[i] = __builtin_bit_cast(float, (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
+            const uint32_t key = ~(uint32_t)(skeys[u * nc + k] & 0xFFFFFFFFull);           // wmf_float_key of the score
+            out_scores[i] = wmf_key_float(key);
         }
     }
 }
@@ -156,10 +149,6 @@ int wmf_launch_rank_batch(const float* users, const float* items, int f, int ld,
     return 0;
 }
 
-__global__ void iota_kernel(int32_t* __restrict__ out, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = (int32_t)i;
-}
-
 int wmf_launch_hits(const float* users, const float* items, int ld, int bias, const int32_t* pair_user,
                     const int32_t* pair_item, const int32_t* pair_row, int64_t n_pairs, const int32_t* cand, int n_cand,
                     const int32_t* slot, const int32_t* topn, int n_topn, int64_t* hits, hipStream_t st) {
@@ -179,16 +168,11 @@ int wmf_launch_hits(const float* users, const float* items, int ld, int bias, co
 // few thousandths of the list unless the scores pile up -- is compacted as a 64-bit key (score key, ~position) and only
 // that short list is sorted (descending: equal scores come out in candidate order, so the result is deterministic although
 // the compaction order is not).  One 8-byte read-back tells the host how long the list is: the call synchronises its stream.
-__device__ __forceinline__ uint32_t rank_key(float s) {
-    const uint32_t u = __builtin_bit_cast(uint32_t, s);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);           // ascending in the float order
-}
-
 __global__ __launch_bounds__(256) void rank_hist_kernel(const float* __restrict__ scores, int64_t n, uint32_t* __restrict__ bins) {
     __shared__ uint32_t h[4096];
     for (int i = threadIdx.x; i < 4096; i += 256) h[i] = 0;
     __syncthreads();
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) atomicAdd(&h[rank_key(scores[i]) >> 20], 1u);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) atomicAdd(&h[wmf_float_key(scores[i]) >> 20], 1u);
     __syncthreads();
     for (int i = threadIdx.x; i < 4096; i += 256) if (h[i]) atomicAdd(&bins[i], h[i]);
 }
@@ -216,7 +200,7 @@ __global__ __launch_bounds__(256) void rank_compact_kernel(const float* __restri
                                                            unsigned long long* __restrict__ keys) {
     const uint32_t T = ctrl[0];
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const uint32_t k = rank_key(scores[i]);
+        const uint32_t k = wmf_float_key(scores[i]);
         // (~k, i): ascending order of these keys = descending score, equal scores in candidate order
         if ((k >> 20) >= T) keys[atomicAdd(&ctrl[1], 1u)] = ((unsigned long long)(~k) << 32) | (unsigned long long)(uint32_t)i;
     }

@@ -325,7 +325,7 @@ def test_rank_positions_beyond_the_scan_grid_cap():
     blocks of 64 rows x the largest slice count; the last block's only row is counted by the second trip."""
     f, bias = 5, 1
     n_slices = _constant("WMF_RECOMMEND_MAX_SLICES", ("include", "wmf_hip.h"))
-    cap = _constant("WMF_RANKPOS_SCAN_GRID")
+    cap = _constant("WMF_SCAN_GRID", ("recmodel_amd", "csrc", "wmf_scan.h"))
     n_rows = 64 * (cap // n_slices) + 1
     assert ((n_rows + 63) // 64) * n_slices > cap >= (n_rows // 64) * n_slices
     ld = _ld(f)

@@ -48,8 +48,8 @@ def _ld(f, extra=0):
     return ld
 
 
-def _launcher_constant(name):
-    text = open(os.path.join(ROOT, "recmodel_amd", "csrc", "wmf_recommend.hip")).read()
+def _launcher_constant(name, source="wmf_recommend.hip"):
+    text = open(os.path.join(ROOT, "recmodel_amd", "csrc", source)).read()
     return int(re.search(rf"#define\s+{name}\s+(\d+)", text).group(1))
 
 
@@ -294,13 +294,41 @@ def test_recommend_agrees_with_rank_topn_batch(f, bias, extra):
             assert (cnt == topn).all()
 
 
-# ------------------------------------------------------------------------------------------------------ 5. grid-stride caps
+# ------------------------------------------------------------------------------------------------- 5. the wave-count switch
+@pytest.mark.parametrize("bias", (0, 1))
+@pytest.mark.parametrize("f", (64, 129, 260))
+def test_recommend_on_both_sides_of_the_wave_count_switch(f, bias):
+    """topn = 64 is the last of the four-wave workgroup (64 batch positions), topn = 65 the first of the two-wave one (32), each
+    its own instantiation of the scan.  65 batch positions are two blocks of the first and three of the second, the last one
+    partial either way; 257 items end in a one-item tile.  EXACT class: bit for bit at the first slice count, the other slice
+    counts the same bits, and the 64 best of the topn = 65 answer are the topn = 64 answer."""
+    nu, ni = 65, 257
+    ld = _ld(f)
+    M, _ = _scores(f, bias, "exact")
+    users = _user_list(nu)
+    seen = _seen_rows(np.random.default_rng(3000 + 2 * f + bias), M[users], ni, 0)
+    rec = _Recommend(*_host(f, "exact"), f, ld, bias, users)
+    answers = {}
+    for topn in (64, 65):
+        for n_slices in (0, 1, 3):
+            got = rec(nu, ni, topn, n_slices, seen)
+            if topn not in answers:
+                answers[topn] = got
+                _check_exact(got, M, users, seen, ni, topn, (f, bias, ld, topn, n_slices))
+            else:
+                assert all(np.array_equal(a.view(np.int32), b.view(np.int32)) for a, b in zip(got, answers[topn])), (f, bias, ld, topn, n_slices)
+    (items64, sc64, cnt64), (items65, sc65, cnt65) = answers[64], answers[65]
+    assert np.array_equal(items65[:, :64], items64) and np.array_equal(sc65[:, :64].view(np.int32), sc64.view(np.int32))
+    assert np.array_equal(np.minimum(cnt65, 64), cnt64) and (cnt65 == 65).any() and (cnt64 < 64).any()
+
+
+# ------------------------------------------------------------------------------------------------------ 6. grid-stride caps
 def test_recommend_beyond_the_scan_grid_cap():
     """More (user block, slice) pairs than workgroups: 17 blocks of 64 users x the largest slice count.  Then the best items of
     the last block's user in the last tile, which the second trip scans."""
     f, bias, topn = 5, 1, 10
     n_slices = 256
-    cap = _launcher_constant("WMF_REC_SCAN_GRID")
+    cap = _launcher_constant("WMF_SCAN_GRID", "wmf_scan.h")
     n_users = 64 * (cap // n_slices) + 1
     assert ((n_users + 63) // 64) * n_slices > cap >= (n_users // 64) * n_slices
     ld = _ld(f)
