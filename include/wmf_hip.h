@@ -265,6 +265,47 @@ int wmf_recommend_topn(const float* users, const float* items, int f, int ld, in
                        int32_t* out_items, float* out_scores, int32_t* out_count,
                        void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Inverse row norms over the FEATURE columns, the scales of a cosine (wmf_similar_topn):
+ * out[i] = 1 / sqrt(S_i) rounded to float32, S_i = sum over the columns c in [bias, f) of M[i, c]^2 accumulated in float64 in a
+ * fixed order (two calls give the same bits); 0 where S_i == 0 or the quotient is not a finite float32.  With bias != 0 column 0
+ * is the bias and no feature; the padding columns [f, ld) are not read as features.  M is [n, ld] in the library's layout, out
+ * float32[n], both on the device; n == 0 is a no-op.  Enqueues only. */
+int wmf_row_inv_norms(const float* M, int64_t n, int f, int ld, int bias, float* out, void* stream);
+
+/* Neighbours in factor space: the topn rows of `catalogue` [n_rows, ld] closest to each of n_queries rows of `queries`, by dot
+ * product or cosine over the feature columns -- "which items are like this one" (both matrices the item factors) and the same for
+ * users.  The reference has no counterpart on the factor model (RecModel offers neighbourhoods through its separate item-KNN
+ * model only).  One fused pass: the catalogue scan, the running top-n and the merge of wmf_recommend_topn.
+ * Inputs: all arrays on the device, both matrices in the library's layout with the same f and ld; they may be the same matrix.
+ *   query_idx[b] selects the row of `queries` that batch position b asks for; a row may occur several times.
+ * Dot product: d(b, j) = the sum over the columns c in [bias, f) of queries[query_idx[b], c] * catalogue[j, c], in the score
+ *   tile's arithmetic (the operand pattern and MFMA order of wmf_recommend_topn and wmf_predict_pairs).  With bias != 0 column 0 is
+ *   left out of the sum and nothing is added: bit for bit wmf_recommend_topn(bias = 0) on copies whose column 0 is zero.
+ * Score: q_inv_norm == c_inv_norm == NULL: the score is d (dot product).  Both given (wmf_row_inv_norms of the two matrices):
+ *   score = (d * q_inv_norm[query_idx[b]]) * c_inv_norm[j] (cosine) -- two float32 multiplications in exactly that order, after the
+ *   sum; q_inv_norm is indexed by the row id, not by the batch position.  One pointer without the other is WMF_EINVAL.
+ * Self-exclusion: exclude_self != 0: catalogue row query_idx[b] is never returned for batch position b (meaningful when both
+ *   matrices are the same).
+ * Exclusion lists: excl_indptr is int64[n_queries + 1]; row b of that CSR belongs to batch position b; excl_indices are catalogue
+ *   rows in [0, n_rows), ascending within a row, duplicates allowed; read exactly as wmf_recommend_topn reads its seen list.  Both
+ *   pointers or neither (NULL: nothing else is excluded).
+ * Order, outputs, limits, slices and workspace are those of wmf_recommend_topn: a higher score wins, equal scores go to the lower
+ *   row id (-0.0 and +0.0 are equal); out_rows[b * topn + k] = the k-th best row, out_scores (may be NULL) its score, out_count[b]
+ *   (may be NULL) = min(topn, eligible rows), entries past it hold -1 and -inf; 1 <= topn <= WMF_RECOMMEND_MAX_TOPN, n_queries >= 1,
+ *   1 <= n_rows < 2^31; n_slices 0 (the library chooses) or 1 .. WMF_RECOMMEND_MAX_SLICES, and the result does not depend on it;
+ *   wmf_similar_workspace_bytes(n_queries, topn, n_slices) = wmf_recommend_workspace_bytes of the same arguments.
+ * The call only enqueues: it does not allocate, synchronise or read back.  WMF_EINVAL, before any HIP call, for a bad shape, a null
+ * pointer, an unpaired pointer, topn or n_slices out of range or a workspace that is too small.
+ * Factors and scales are finite; NaN scores are unspecified, but every index written is in range. */
+int64_t wmf_similar_workspace_bytes(int64_t n_queries, int64_t topn, int32_t n_slices);
+int wmf_similar_topn(const float* queries, const float* catalogue, int f, int ld, int bias,
+                     const float* q_inv_norm, const float* c_inv_norm,
+                     const int32_t* query_idx, int64_t n_queries, int64_t n_rows,
+                     int32_t exclude_self, const int64_t* excl_indptr, const int32_t* excl_indices,
+                     int64_t topn, int32_t n_slices,
+                     int32_t* out_rows, float* out_scores, int32_t* out_count,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+
 /* The exact place of held-out items in the full-catalogue order of wmf_recommend_topn: the dual query of that entry point, not
  * "which are the topn best" but "at which place does this item stand", for unsampled, train-excluded Recall / NDCG / ARHR
  * (RecModel.eval_ranking; the reference offers only the sampled Recall@N of base_model.py:100-148).  One counting pass over the

@@ -593,6 +593,44 @@ int wmf_recommend_topn(const float* users, const float* items, int f, int ld, in
                         "wmf_recommend_topn", f, ld, "");
 }
 
+int wmf_row_inv_norms(const float* M, int64_t n, int f, int ld, int bias, float* out, void* stream) {
+    int rc = check_shape(f, ld);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!M || !out))) { wmf_set_error("wmf_row_inv_norms: null pointer or negative size"); return WMF_EINVAL; }
+    if (n == 0) return WMF_OK;
+    wmf_launch_row_inv_norms(M, n, f, ld, bias, out, (hipStream_t)stream);
+    return check_launch("wmf_row_inv_norms");
+}
+
+int64_t wmf_similar_workspace_bytes(int64_t n_queries, int64_t topn, int32_t n_slices) { return wmf_recommend_ws_bytes(n_queries, topn, n_slices); }
+
+int wmf_similar_topn(const float* queries, const float* catalogue, int f, int ld, int bias, const float* q_inv_norm, const float* c_inv_norm,
+                     const int32_t* query_idx, int64_t n_queries, int64_t n_rows, int32_t exclude_self, const int64_t* excl_indptr,
+                     const int32_t* excl_indices, int64_t topn, int32_t n_slices, int32_t* out_rows, float* out_scores, int32_t* out_count,
+                     void* workspace, int64_t workspace_bytes, void* stream) {
+    int rc = check_shape(f, ld);
+    if (rc) return rc;
+    if (!queries || !catalogue || !query_idx || !out_rows || !workspace) { wmf_set_error("wmf_similar_topn: null pointer"); return WMF_EINVAL; }
+    if (!q_inv_norm != !c_inv_norm || !excl_indptr != !excl_indices) {
+        wmf_set_error("wmf_similar_topn: q_inv_norm and c_inv_norm, excl_indptr and excl_indices: both or neither"); return WMF_EINVAL;
+    }
+    if (n_queries < 1 || n_rows < 1 || n_rows > 0x7fffffffLL || topn < 1 || topn > WMF_RECOMMEND_MAX_TOPN || n_slices < 0 ||
+        n_slices > WMF_RECOMMEND_MAX_SLICES) {
+        wmf_set_error("wmf_similar_topn: need n_queries >= 1, 1 <= n_rows < 2^31, 1 <= topn <= %d, 0 <= n_slices <= %d (n_queries=%lld, n_rows=%lld, topn=%lld, n_slices=%d)",
+                      WMF_RECOMMEND_MAX_TOPN, WMF_RECOMMEND_MAX_SLICES, (long long)n_queries, (long long)n_rows, (long long)topn, (int)n_slices);
+        return WMF_EINVAL;
+    }
+    if (workspace_bytes < wmf_recommend_ws_bytes(n_queries, topn, n_slices)) {
+        wmf_set_error("wmf_similar_topn: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
+                      (long long)wmf_recommend_ws_bytes(n_queries, topn, n_slices));
+        return WMF_EINVAL;
+    }
+    return launch_error(wmf_launch_similar(queries, catalogue, ld, bias, q_inv_norm, c_inv_norm, query_idx, n_queries, n_rows, exclude_self,
+                                           excl_indptr, excl_indices, topn, n_slices, out_rows, out_scores, out_count, workspace,
+                                           (hipStream_t)stream),
+                        "wmf_similar_topn", f, ld, "");
+}
+
 int64_t wmf_rank_positions_workspace_bytes(int64_t n_rows, int64_t n_targets, int32_t n_slices) {
     (void)n_targets; (void)n_slices;                              // (at most WMF_RANKPOS_MAX_TARGETS a row are counted, by atomics)
     return wmf_rank_positions_ws_bytes(n_rows);

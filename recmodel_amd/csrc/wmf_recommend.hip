@@ -19,108 +19,10 @@
 #include "wmf_common.h"
 #include "wmf_internal.h"
 #include "wmf_scan.h"
+#include "wmf_topn.h"
 
 #define WMF_REC_MERGE_GRID 1024      /* workgroups of the merge, four users each */
 #define WMF_REC_SLICE_TILES 64       /* an automatic slice holds at least this many 16-item tiles */
-
-// The buffers of the wave's users in `mask` (bit u = user u of 16) cut back to their topn best, sorted best first; thr[u] = the
-// topn-th best once there are that many.  A key's place is the number of keys above it (the keys are distinct): every lane
-// holds up to four keys of the buffer (cap <= 256) and counts against broadcast reads of all of them.
-__device__ __forceinline__ void rec_compact(unsigned mask, unsigned long long* __restrict__ keys, int* __restrict__ cnt,
-                                            unsigned long long* __restrict__ thr, int cap, int topn, int lane) {
-    while (mask) {
-        const int u = __builtin_ctz(mask);
-        mask &= mask - 1;
-        unsigned long long* ku = keys + u * cap;
-        const int n = min(cnt[u], cap);
-        unsigned long long e[4];
-        int place[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            e[k] = (lane + 64 * k < n) ? ku[lane + 64 * k] : 0ull;
-            place[k] = 0;
-        }
-        for (int j = 0; j < n; ++j) {
-            const unsigned long long o = ku[j];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) place[k] += (o > e[k]) ? 1 : 0;
-        }
-        wmf_wave_sync();                                           // every read of the buffer before the first write
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (lane + 64 * k < n && place[k] < topn) {
-                ku[place[k]] = e[k];
-                if (place[k] == topn - 1) thr[u] = e[k];
-            }
-        }
-        if (lane == 0) cnt[u] = min(n, topn);
-        wmf_wave_sync();
-    }
-}
-
-// The scan's epilogue: a running top-n per user.  LDS past the stages: [keys: 16 users x cap per wave][thresholds][counts].
-// partial[(b * n_slices + slice) * topn + k]: the k-th best key of batch position b in that slice, 0 = none.
-template <int NW>
-struct RecTopN {
-    const int64_t* __restrict__ seen_indptr; const int32_t* __restrict__ seen_indices;
-    int64_t n_users; int topn, cap, n_slices;
-    unsigned long long* __restrict__ partial;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
-    unsigned long long* keys; unsigned long long* thr_l; int* cnt;
-    int64_t u0; int sl;
-    unsigned long long thr[4];
-    int64_t seen_lo[4], seen_hi[4];
-
-    __device__ __forceinline__ void begin(unsigned char* lds, int64_t u0_, int sl_) {
-        u0 = u0_; sl = sl_;
-        keys = reinterpret_cast<unsigned long long*>(lds) + (size_t)wave * 16 * cap;
-        thr_l = reinterpret_cast<unsigned long long*>(lds) + (size_t)NW * 16 * cap + wave * 16;
-        cnt = reinterpret_cast<int*>(lds + ((size_t)NW * 16 * cap + NW * 16) * 8) + wave * 16;
-        if (lane < 16) { cnt[lane] = 0; thr_l[lane] = 0ull; }
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            thr[reg] = 0ull; seen_lo[reg] = 0; seen_hi[reg] = 0;
-            const int64_t b = u0 + 4 * q + reg;
-            if (seen_indptr && b < n_users) { seen_lo[reg] = seen_indptr[b]; seen_hi[reg] = seen_indptr[b + 1]; }
-        }
-        wmf_wave_sync();
-    }
-    // A key that beats the user's threshold is looked up in the user's sorted seen list and, if it is not there, appended
-    __device__ __forceinline__ void score(int reg, int, int64_t item, unsigned long long key, bool in_range) {
-        bool take = in_range && u0 + 4 * q + reg < n_users && key > thr[reg];
-        if (take && seen_lo[reg] < seen_hi[reg]) {
-            int64_t lo = seen_lo[reg], hi = seen_hi[reg];
-            while (lo < hi) {                                      // first entry >= item
-                const int64_t mid = (lo + hi) >> 1;
-                if (seen_indices[mid] < (int32_t)item) lo = mid + 1; else hi = mid;
-            }
-            take = !(lo < seen_hi[reg] && seen_indices[lo] == (int32_t)item);
-        }
-        if (take) {
-            const int slot = atomicAdd(&cnt[4 * q + reg], 1);      // at most 16 per user and tile: below cap
-            if (slot < cap) keys[(4 * q + reg) * cap + slot] = key;
-        }
-    }
-    // a buffer the next tile could overflow is cut back to its topn best
-    __device__ __forceinline__ void tile(int) {
-        wmf_wave_sync();
-        const unsigned full = (unsigned)(__ballot(cnt[r] > cap - 16) & 0xFFFFull);
-        if (full) {
-            rec_compact(full, keys, cnt, thr_l, cap, topn, lane);
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) thr[reg] = thr_l[4 * q + reg];
-        }
-    }
-    __device__ __forceinline__ void end() {
-        rec_compact((unsigned)(__ballot(cnt[r] > 0) & 0xFFFFull), keys, cnt, thr_l, cap, topn, lane);
-        for (int u = 0; u < 16 && u0 + u < n_users; ++u) {
-            unsigned long long* out = partial + ((u0 + u) * n_slices + sl) * topn;
-            const int n = cnt[u];
-            for (int k = lane; k < topn; k += 64) out[k] = k < n ? keys[u * cap + k] : 0ull;
-        }
-        wmf_wave_sync();                                           // the buffers are read before the next pair resets them
-    }
-};
 
 // NIT, TPS: the scan's width class; NW: waves of a workgroup (the key buffers of 16 NW users share the LDS with the stages)
 template <int NIT, int TPS, int NW>
@@ -176,9 +78,6 @@ __global__ __launch_bounds__(256) void recommend_merge_kernel(const unsigned lon
 }
 
 // ---- launcher ---------------------------------------------------------------------------------------------------------------
-static inline int rec_cap(int64_t topn) { return (int)(2 * topn > 32 ? 2 * topn : 32); }       // >= topn + 16, <= 256
-static inline int rec_waves(int64_t topn) { return rec_cap(topn) <= 128 ? 4 : 2; }               // 64 KB of key buffers at most
-
 int64_t wmf_recommend_ws_bytes(int64_t n_users, int64_t topn, int32_t n_slices) {
     if (n_users < 1 || topn < 1 || n_slices < 0) return 256;
     const int64_t s = n_slices == 0 ? WMF_RECOMMEND_AUTO_SLICES : n_slices;
@@ -197,6 +96,14 @@ int wmf_recommend_slices(int64_t n_users, int64_t n_items, int64_t topn, int32_t
     return (int)(s < 1 ? 1 : s);
 }
 
+void wmf_launch_topn_merge(const unsigned long long* partial, int64_t n_rows, int n_slices, int topn, int32_t* out_rows, float* out_scores,
+                           int32_t* out_count, hipStream_t st) {
+    int64_t grid = (n_rows + 3) / 4;
+    if (grid > WMF_REC_MERGE_GRID) grid = WMF_REC_MERGE_GRID;
+    WMF_LAUNCH("recommend_merge_kernel", recommend_merge_kernel, dim3((unsigned)grid), dim3(256), 0, st, partial, n_rows, n_slices, topn,
+               out_rows, out_scores, out_count);
+}
+
 template <int NIT, int TPS>
 static int rec_launch_scan(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
                            int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, int topn, int n_slices,
@@ -204,7 +111,7 @@ static int rec_launch_scan(const float* users, const float* items, int ld, int b
     return wmf_dispatch_list<4, 2>(rec_waves(topn), [&](auto nw) {
         constexpr int NW = decltype(nw)::value;
         const int cap = rec_cap(topn);
-        const size_t lds = wmf_scan_stage_bytes(TPS, ld) + ((size_t)NW * 16 * cap + NW * 16) * 8 + (size_t)NW * 16 * 4;
+        const size_t lds = wmf_scan_stage_bytes(TPS, ld) + rec_lds_bytes(NW, cap);
         const int64_t tiles = (n_items + 15) / 16, tiles_per_slice = (tiles + n_slices - 1) / n_slices;
         const int64_t n_work = ((n_users + 16 * NW - 1) / (16 * NW)) * n_slices;
         const int64_t grid = n_work < WMF_SCAN_GRID ? n_work : WMF_SCAN_GRID;
@@ -227,9 +134,6 @@ int wmf_launch_recommend(const float* users, const float* items, int ld, int bia
     else if (nit <= 17) rc = rec_launch_scan<17, 1>(users, items, ld, bias, user_idx, n_users, n_items, seen_indptr, seen_indices, (int)topn, slices, partial, st);
     else return WMF_L_NO_KERNEL;
     if (rc) return rc;
-    int64_t grid = (n_users + 3) / 4;
-    if (grid > WMF_REC_MERGE_GRID) grid = WMF_REC_MERGE_GRID;
-    WMF_LAUNCH("recommend_merge_kernel", recommend_merge_kernel, dim3((unsigned)grid), dim3(256), 0, st, partial, n_users, slices, (int)topn,
-               out_items, out_scores, out_count);
+    wmf_launch_topn_merge(partial, n_users, slices, (int)topn, out_items, out_scores, out_count, st);
     return WMF_L_OK;
 }

@@ -1,6 +1,6 @@
 // What the serving kernels share (gfx950): the order-preserving score key, the 16 x 16 score tile of score_tile_kernel, and the
 // full-catalogue scan of wmf_recommend.hip (a running top-n per user) and wmf_rankpos.hip (counts above the users' target keys):
-// one scoring loop, two epilogue policies.
+// one scoring loop, the epilogue and the scoring rule as compile-time policies (wmf_similar.hip: the neighbours of a row).
 #pragma once
 #include "wmf_common.h"
 
@@ -61,7 +61,8 @@ __device__ __forceinline__ float wmf_diag_score(const float4* __restrict__ urow,
 // A workgroup of NW waves holds 16 rows per wave in registers and walks a contiguous SLICE of the catalogue's 16-item tiles, which
 // it stages once in LDS for all its waves; the work units are the (block of 16 NW rows, slice) pairs.
 // NIT: trips of the feature loop a wave can hold a row for (4 NIT pieces of 16 bytes per row); TPS: 16-item tiles per stage.
-// Dynamic LDS: [two stages of TPS x 16 item rows, (nch | 1) pieces apart][the policy's].  The policy P, a local of the kernel whose
+// Dynamic LDS: [two stages of TPS x 16 item rows, (nch | 1) pieces apart][the policy's][the scoring policy's, which its kernel
+// places].  The policy P, a local of the kernel whose
 // per-lane state is fixed-size arrays under compile-time indices, is called by every lane of a wave together:
 //   p.begin(lds, u0, sl)                  a unit starts: lds = the dynamic LDS past the stages, u0 = the wave's first batch position
 //                                         (waves past the batch are called too), sl = the slice
@@ -71,10 +72,20 @@ __device__ __forceinline__ float wmf_diag_score(const float4* __restrict__ urow,
 //   p.end()                               the slice is done; score, tile and end only in waves with u0 < n_rows
 __host__ __device__ static inline size_t wmf_scan_stage_bytes(int tps, int ld) { return (size_t)2 * tps * 16 * ((ld >> 2) | 1) * 16; }
 
-template <int NIT, int TPS, int NW, class P>
+// What a score is made of besides the sum of the MFMAs is a second, compile-time policy S.  WmfModelScore (S::SCALED false) is the
+// score of the model, wmf_score_tile's, as the text of the loop: acc + (user bias + item bias), the biases added last.  A policy with
+// S::SCALED (wmf_similar.hip) leaves column 0 of a bias model out of both operands, adds nothing, and is called by every lane of a
+// wave together (load and store by every thread of the workgroup):
+//   s.rows(rs, user_idx, u0, n_rows, q)         rs[reg] = the per-row term of row u0 + 4 q + reg (the slot of the user bias)
+//   s.load(tile_first, n_items) / s.store(buf)  with the global loads / the LDS stores of a stage: what travels with it
+//   s.item(r, buf, j)                           the per-item term of item row r of the j-th tile of stage buffer buf
+//   s.score(acc, rs, is)                        the score
+struct WmfModelScore { static constexpr bool SCALED = false; };
+
+template <int NIT, int TPS, int NW, class P, class S = WmfModelScore>
 __device__ __forceinline__ void wmf_catalogue_scan(const float* __restrict__ users, const float* __restrict__ items, int ld, int bias,
                                                    const int32_t* __restrict__ user_idx, int64_t n_rows, int64_t n_items, int n_slices,
-                                                   int64_t tiles_per_slice, int64_t n_work, P& p) {
+                                                   int64_t tiles_per_slice, int64_t n_work, P& p, S sp = S()) {
     extern __shared__ __align__(16) unsigned char wmf_scan_smem[];
     constexpr int PRE = (TPS * NIT + NW - 1) / NW;                // 16-byte pieces of a stage per thread
     const int tid = threadIdx.x;
@@ -113,8 +124,12 @@ __device__ __forceinline__ void wmf_catalogue_scan(const float* __restrict__ use
                 ureg[it] = (it < nit && c < nch) ? urow[c] : make_float4(0.f, 0.f, 0.f, 0.f);
             }
             if (bias && q == 0) { ubv = ureg[0].x; ureg[0].x = 0.f; }
+            if constexpr (S::SCALED) {
+                sp.rows(ubr, user_idx, u0, n_rows, q);
+            } else {
 #pragma unroll
-            for (int reg = 0; reg < 4; ++reg) ubr[reg] = __shfl(ubv, 4 * q + reg);    // user bias of user 4 q + reg
+                for (int reg = 0; reg < 4; ++reg) ubr[reg] = __shfl(ubv, 4 * q + reg);    // user bias of user 4 q + reg
+            }
         }
         p.begin(wmf_scan_smem + wmf_scan_stage_bytes(TPS, ld), u0, sl);
 
@@ -122,13 +137,19 @@ __device__ __forceinline__ void wmf_catalogue_scan(const float* __restrict__ use
         // array was kept in scratch)
         float4 pre[PRE];
 #define WMF_SCAN_LOAD_STAGE(TILE_FIRST)                                                                                       \
-    _Pragma("unroll") for (int k = 0; k < PRE; ++k) {                                                                         \
-        const int64_t gi = min(16 * (TILE_FIRST) + (pk[k] >> 8), n_items - 1);   /* clamped: the scores are masked */          \
-        pre[k] = pk[k] >= 0 ? items4[gi * nch + (pk[k] & 255)] : make_float4(0.f, 0.f, 0.f, 0.f);                              \
+    {                                                                                                                         \
+        _Pragma("unroll") for (int k = 0; k < PRE; ++k) {                                                                     \
+            const int64_t gi = min(16 * (TILE_FIRST) + (pk[k] >> 8), n_items - 1);   /* clamped: the scores are masked */      \
+            pre[k] = pk[k] >= 0 ? items4[gi * nch + (pk[k] & 255)] : make_float4(0.f, 0.f, 0.f, 0.f);                          \
+        }                                                                                                                     \
+        if constexpr (S::SCALED) sp.load(TILE_FIRST, n_items);                                                                \
     }
 #define WMF_SCAN_STORE_STAGE(BUF)                                                                                             \
-    _Pragma("unroll") for (int k = 0; k < PRE; ++k)                                                                           \
-        if (pk[k] >= 0) stage[(BUF) * stage_f4 + (pk[k] >> 8) * stride + (pk[k] & 255)] = pre[k];
+    {                                                                                                                         \
+        _Pragma("unroll") for (int k = 0; k < PRE; ++k)                                                                       \
+            if (pk[k] >= 0) stage[(BUF) * stage_f4 + (pk[k] >> 8) * stride + (pk[k] & 255)] = pre[k];                         \
+        if constexpr (S::SCALED) sp.store(BUF);                                                                               \
+    }
 
         if (n_st > 0) { WMF_SCAN_LOAD_STAGE(t0) WMF_SCAN_STORE_STAGE(0) }
         __syncthreads();
@@ -150,7 +171,11 @@ __device__ __forceinline__ void wmf_catalogue_scan(const float* __restrict__ use
                         for (int j = 0; j < TPS; ++j) {
                             float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
                             if (c < nch) b = st[(16 * j + r) * stride + c];
-                            if (bias && c == 0) ibv[j] = b.x;      // (the user's column 0 is already zero in ureg)
+                            if constexpr (S::SCALED) {
+                                if (bias && c == 0) b.x = 0.f;     // the bias column is no feature
+                            } else {
+                                if (bias && c == 0) ibv[j] = b.x;  // (the user's column 0 is already zero in ureg)
+                            }
                             acc[j] = WMF_MFMA16(a.x, b.x, acc[j]); acc[j] = WMF_MFMA16(a.y, b.y, acc[j]);
                             acc[j] = WMF_MFMA16(a.z, b.z, acc[j]); acc[j] = WMF_MFMA16(a.w, b.w, acc[j]);
                         }
@@ -161,10 +186,12 @@ __device__ __forceinline__ void wmf_catalogue_scan(const float* __restrict__ use
                 for (int j = 0; j < TPS; ++j) {
                     if (tile_first + j < t1) {
                         const int64_t item = 16 * (tile_first + j) + r;
-                        const float ibr = __shfl(ibv[j], r);
+                        float ibr;
+                        if constexpr (S::SCALED) ibr = sp.item(r, (int)(s & 1), j); else ibr = __shfl(ibv[j], r);
 #pragma unroll
                         for (int reg = 0; reg < 4; ++reg) {
-                            const float sc = acc[j][reg] + (bias ? ubr[reg] + ibr : 0.f);
+                            float sc;
+                            if constexpr (S::SCALED) sc = sp.score(acc[j][reg], ubr[reg], ibr); else sc = acc[j][reg] + (bias ? ubr[reg] + ibr : 0.f);
                             p.score(reg, j, item, wmf_item_key(sc, item), item < n_items);
                         }
                         p.tile(j);

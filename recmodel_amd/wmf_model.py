@@ -137,6 +137,7 @@ class WMF(RecModel):
         self.dtype = dtype
         self._engine = None
         self._dev = None           # (key, users_t, items_t, f, ld): device copies of the public arrays for predict() / rank()
+        self._inv_norms = {}       # {"users" / "items": float32 [rows] on the device}: inverse feature norms of the copies in _dev
 
     # ------------------------------------------------------------------ engine plumbing
     def _new_engine(self):
@@ -160,7 +161,20 @@ class WMF(RecModel):
                 t[:, :f] = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
                 return t
             self._dev = (key, up(self.users), up(self.items), f, ld)
+            self._inv_norms = {}
         return self._dev[1:]
+
+    def _device_inv_norms(self, side):
+        """(users_t, items_t, f, ld, inverse feature norms of ``side``): wmf_row_inv_norms on the device copy, kept exactly as
+        long as that copy is -- by identity for the frozen arrays ``train`` leaves behind, computed again on every call for a
+        writable array, which is uploaded again on every call."""
+        users_t, items_t, f, ld = dev = self._device_factors()
+        if side not in self._inv_norms:
+            mat = users_t if side == "users" else items_t
+            out = torch.empty(mat.shape[0], dtype=torch.float32, device="cuda")
+            _lib.check(_lib.load().wmf_row_inv_norms(_ptr(mat), mat.shape[0], f, ld, int(self.bias is True), _ptr(out), _stream()))
+            self._inv_norms[side] = out
+        return dev + (self._inv_norms[side],)
 
     # ------------------------------------------------------------------ a7: predict
     def predict(self, users, items):
@@ -322,6 +336,73 @@ class WMF(RecModel):
         if out_scores is not None:
             out_scores[:] = scores_d.cpu().numpy()
 
+    # ------------------------------------------------------------------ a14: similar_items, similar_users
+    def similar_items(self, items, topn=10, metric='cosine', exclude_self=True, return_scores=False):
+        """The ``topn`` items closest to each of ``items`` in factor space (an int or a sequence of ints; negative indices count
+        from the end), best first, equal scores in item order.  ``metric``: 'cosine' or 'dot', over the features -- the bias
+        column of a bias model is not a feature in either.  ``exclude_self``: the item itself is not among its neighbours.
+        One fused device pass over the catalogue per batch (wmf_similar_topn); a float64 model is served from its float32
+        device copies, as ``recommend`` is.  The device copies hold both factor matrices, so the model must have its ``users``
+        (an AttributeError otherwise, before the GPU is touched).  Arrays that ``train`` left behind are read-only: their copies
+        and inverse norms are made once; with a writable array every call uploads both matrices and computes the norms again
+        -- freeze the arrays (``a.flags.writeable = False``) when they no longer change.  Returns int64 [len(items), topn], padded with -1 where there are fewer rows; with
+        ``return_scores`` also the float32 scores, padded with -inf.  An int gives one row.  ``topn`` is at most
+        RECOMMEND_MAX_TOPN: there is no slower path beyond it, a larger ``topn`` is a ValueError."""
+        return self._similar("items", items, topn, metric, exclude_self, return_scores)
+
+    def similar_users(self, users, topn=10, metric='cosine', exclude_self=True, return_scores=False):
+        """``similar_items`` among the users: the ``topn`` users closest to each of ``users``."""
+        return self._similar("users", users, topn, metric, exclude_self, return_scores)
+
+    def _similar(self, side, ids, topn, metric, exclude_self, return_scores):
+        if metric not in ('cosine', 'dot'):
+            raise ValueError(f"metric must be 'cosine' or 'dot', not {metric!r}")
+        topn = int(topn)
+        if topn < 1 or topn > RECOMMEND_MAX_TOPN:
+            raise ValueError(f"topn must be between 1 and {RECOMMEND_MAX_TOPN}, not {topn}")
+        if self.users is None:                                      # (the device copies are of both matrices; as in predict)
+            raise AttributeError("the model has no user factors yet: train it, or assign users, before asking for neighbours")
+        n_rows = getattr(self, side).shape[0]
+        one = np.ndim(ids) == 0
+        q = np.atleast_1d(np.asarray(ids)).reshape(-1).astype(np.int64)
+        if len(q) and (q.min() < -n_rows or q.max() >= n_rows):
+            raise IndexError(f"{side[:-1]} index out of bounds")
+        _lib.require_gpu()
+        q = np.where(q < 0, q + n_rows, q)
+        out_rows = np.full((len(q), topn), -1, dtype=np.int64)
+        out_scores = np.full((len(q), topn), -np.inf, dtype=np.float32)
+        if len(q):
+            self._similar_fused(side, q, topn, metric == 'cosine', bool(exclude_self), out_rows, out_scores if return_scores else None)
+        if one:
+            out_rows, out_scores = out_rows[0], out_scores[0]
+        return (out_rows, out_scores) if return_scores else out_rows
+
+    def _similar_fused(self, side, q, topn, cosine, exclude_self, out_rows, out_scores):
+        """Batches of RECOMMEND_BATCH_USERS queries, all enqueued on one stream; one copy to the host at the end."""
+        if cosine:
+            users_t, items_t, f, ld, norms = self._device_inv_norms(side)
+        else:
+            users_t, items_t, f, ld = self._device_factors()
+            norms = None
+        mat = users_t if side == "users" else items_t
+        lib = _lib.load()
+        n = len(q)
+        qt = torch.from_numpy(q.astype(np.int32)).cuda()
+        rows_d = torch.empty(n, topn, dtype=torch.int32, device="cuda")
+        scores_d = torch.empty(n, topn, dtype=torch.float32, device="cuda") if out_scores is not None else None
+        per = max(1, int(RECOMMEND_BATCH_USERS))
+        ws_bytes = int(lib.wmf_similar_workspace_bytes(min(per, n), topn, 0))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+        for b0 in range(0, n, per):
+            nb = min(per, n - b0)
+            _lib.check(lib.wmf_similar_topn(
+                _ptr(mat), _ptr(mat), f, ld, int(self.bias is True), _ptr(norms) if cosine else None, _ptr(norms) if cosine else None,
+                _ptr(qt[b0:]), nb, mat.shape[0], int(exclude_self), None, None, topn, 0,
+                _ptr(rows_d[b0:]), _ptr(scores_d[b0:]) if scores_d is not None else None, None, _ptr(ws), ws_bytes, _stream()))
+        out_rows[:] = rows_d.cpu().numpy()
+        if out_scores is not None:
+            out_scores[:] = scores_d.cpu().numpy()
+
     # ------------------------------------------------------------------ a12: rank_positions
     def rank_positions(self, test_mat, exclude=None, users=None, return_scores=False):
         """The exact place of every held-out item in the user's full-catalogue order: for each stored entry (u, t) of
@@ -417,6 +498,7 @@ class WMF(RecModel):
         self.items.flags.writeable = False
         self._synced = (id(self.users), id(self.items))
         self._dev = None
+        self._inv_norms = {}
 
     def _pull(self, eng, sides=("users", "items")):
         for s in sides:
