@@ -41,12 +41,15 @@ static int check_launch(const char* what) {
     return WMF_OK;
 }
 
-// What a launcher answered (WmfLaunchRc), as the entry point's WMF_E* and message; `layout`: what WMF_L_LAYOUT means there
-static int launch_error(int lrc, const char* what, int f, int ld, const char* layout) {
+// What a launcher answered (WmfLaunchRc), as the entry point's WMF_E* and message; `layout`, `hip`, `too_many`: what WMF_L_LAYOUT,
+// WMF_L_HIP and WMF_L_TOO_MANY_KEYS mean there
+static int launch_error(int lrc, const char* what, int f, int ld, const char* layout, const char* hip = "hipMemsetAsync failed",
+                        const char* too_many = "") {
     switch (lrc) {
         case WMF_L_OK: return check_launch(what);
-        case WMF_L_HIP: wmf_set_error("%s: hipMemsetAsync failed", what); return WMF_EHIP;
+        case WMF_L_HIP: wmf_set_error("%s: %s", what, hip); return WMF_EHIP;
         case WMF_L_LAYOUT: wmf_set_error("%s: %s", what, layout); return WMF_EINVAL;
+        case WMF_L_TOO_MANY_KEYS: wmf_set_error("%s: %s", what, too_many); return WMF_EINVAL;
         default: wmf_set_error("%s: no kernel for f=%d, ld=%d", what, f, ld); return WMF_EINVAL;
     }
 }
@@ -55,6 +58,30 @@ static int check_shape(int f, int ld) {
     if (f < 1 || f > WMF_MAX_F) { wmf_set_error("factor width f=%d outside [1, %d]", f, WMF_MAX_F); return WMF_EINVAL; }
     if (ld < f || (ld & 3)) { wmf_set_error("leading dimension ld=%d must be a multiple of 4 and >= f=%d", ld, f); return WMF_EINVAL; }
     if (ld > 272) { wmf_set_error("leading dimension ld=%d too large", ld); return WMF_EINVAL; }
+    return WMF_OK;
+}
+
+// The checks the three catalogue-scan entry points share (before any HIP call).  null_text: what a missing pointer is called there;
+// own: the refusal of the call's own pointer rules, found by the caller, or NULL; rows / cat: the names the message prints for
+// n_rows / n_items; topn: NULL when the call has none; need(): the workspace of the call, asked once the sizes are in range
+template <class Need>
+static int check_scan_call(const char* what, const void* users, const void* items, const void* user_idx, const void* out, const void* workspace,
+                           const char* null_text, const char* own, const char* rows, int64_t n_rows, const char* cat, int64_t n_items,
+                           const int64_t* topn, int32_t n_slices, int64_t workspace_bytes, Need&& need) {
+    if (!users || !items || !user_idx || !out || !workspace) { wmf_set_error("%s: %s", what, null_text); return WMF_EINVAL; }
+    if (own) { wmf_set_error("%s: %s", what, own); return WMF_EINVAL; }
+    if (n_rows < 1 || n_items < 1 || n_items > 0x7fffffffLL || (topn && (*topn < 1 || *topn > WMF_RECOMMEND_MAX_TOPN)) || n_slices < 0 ||
+        n_slices > WMF_RECOMMEND_MAX_SLICES) {
+        if (topn) wmf_set_error("%s: need %s >= 1, 1 <= %s < 2^31, 1 <= topn <= %d, 0 <= n_slices <= %d (%s=%lld, %s=%lld, topn=%lld, n_slices=%d)", what, rows,
+                                cat, WMF_RECOMMEND_MAX_TOPN, WMF_RECOMMEND_MAX_SLICES, rows, (long long)n_rows, cat, (long long)n_items, (long long)*topn, (int)n_slices);
+        else wmf_set_error("%s: need %s >= 1, 1 <= %s < 2^31, 0 <= n_slices <= %d (%s=%lld, %s=%lld, n_slices=%d)", what, rows, cat,
+                           WMF_RECOMMEND_MAX_SLICES, rows, (long long)n_rows, cat, (long long)n_items, (int)n_slices);
+        return WMF_EINVAL;
+    }
+    if (workspace_bytes < need()) {
+        wmf_set_error("%s: workspace too small (%lld < %lld bytes)", what, (long long)workspace_bytes, (long long)need());
+        return WMF_EINVAL;
+    }
     return WMF_OK;
 }
 
@@ -422,8 +449,8 @@ int wmf_eval_sqerr(const float* users, const float* items, int f, int ld, int bi
     int rc = check_shape(f, ld);
     if (rc) return rc;
     if (!users || !items || !indptr || !out3 || !workspace || n < 0) { wmf_set_error("wmf_eval_sqerr: null pointer"); return WMF_EINVAL; }
-    wmf_launch_eval(users, items, f, ld, bias, indptr, indices, values, n, out3, (double*)workspace, (hipStream_t)stream);
-    return check_launch("wmf_eval_sqerr");
+    return launch_error(wmf_launch_eval(users, items, f, ld, bias, indptr, indices, values, n, out3, (double*)workspace, (hipStream_t)stream),
+                        "wmf_eval_sqerr", f, ld, "");
 }
 
 int64_t wmf_audit_workspace_bytes(int64_t n) { return wmf_audit_ws_bytes(n); }
@@ -471,8 +498,8 @@ int wmf_predict_pairs(const float* users, const float* items, int f, int ld, int
         return WMF_EINVAL;
     }
     if (n_u <= 0 || n_i <= 0) return WMF_OK;                      // an empty side against one index: no pair, nothing read or written
-    wmf_launch_predict(users, items, f, ld, bias, users_idx, n_u, items_idx, n_i, out, (hipStream_t)stream);
-    return check_launch("wmf_predict_pairs");
+    return launch_error(wmf_launch_predict(users, items, f, ld, bias, users_idx, n_u, items_idx, n_i, out, (hipStream_t)stream),
+                        "wmf_predict_pairs", f, ld, "");
 }
 
 int64_t wmf_partial_row_floats(int f) { return wmf_directw_partial_floats(f); }
@@ -541,12 +568,13 @@ int wmf_rank_topn(const float* users, const float* items, int f, int ld, int bia
         wmf_set_error("wmf_rank_topn: need 1 <= topn <= n_cand < 2^31 (topn=%lld, n_cand=%lld)", (long long)topn, (long long)n_cand);
         return WMF_EINVAL;
     }
-    const int lrc = wmf_launch_rank(users, items, f, ld, bias, user_idx, cand_idx, n_cand, topn, out_pos, out_scores, workspace,
-                                    workspace_bytes, (hipStream_t)stream);
-    if (lrc == -3) { wmf_set_error("wmf_rank_topn: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)wmf_rank_ws_bytes(n_cand)); return WMF_EINVAL; }
-    if (lrc == -4) { wmf_set_error("wmf_rank_topn: too many keys for the device sort (2^32 or more)"); return WMF_EINVAL; }
-    if (lrc) { wmf_set_error("wmf_rank_topn: device sort or copy failed"); return WMF_EHIP; }
-    return check_launch("wmf_rank_topn");
+    if (workspace_bytes < wmf_rank_ws_bytes(n_cand)) {
+        wmf_set_error("wmf_rank_topn: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)wmf_rank_ws_bytes(n_cand));
+        return WMF_EINVAL;
+    }
+    return launch_error(wmf_launch_rank(users, items, f, ld, bias, user_idx, cand_idx, n_cand, topn, out_pos, out_scores, workspace,
+                                        (hipStream_t)stream),
+                        "wmf_rank_topn", f, ld, "", "device sort or copy failed", "too many keys for the device sort (2^32 or more)");
 }
 
 int64_t wmf_rank_batch_workspace_bytes(int64_t n_users, int64_t n_cand) { return wmf_rank_batch_ws_bytes(n_users, n_cand); }
@@ -561,12 +589,10 @@ int wmf_rank_topn_batch(const float* users, const float* items, int f, int ld, i
         wmf_set_error("wmf_rank_topn_batch: need n_users, n_cand >= 1, 1 <= topn <= n_cand, n_users * n_cand < 2^31");
         return WMF_EINVAL;
     }
-    const int lrc = wmf_launch_rank_batch(users, items, f, ld, bias, user_idx, n_users, cand_idx, n_cand, topn, out_pos, out_scores,
-                                          workspace, workspace_bytes, (hipStream_t)stream);
-    if (lrc == -3) { wmf_set_error("wmf_rank_topn_batch: workspace too small"); return WMF_EINVAL; }
-    if (lrc == -4) { wmf_set_error("wmf_rank_topn_batch: too many keys for the device sort (2^32 or more)"); return WMF_EINVAL; }
-    if (lrc) { wmf_set_error("wmf_rank_topn_batch: device sort failed"); return WMF_EHIP; }
-    return check_launch("wmf_rank_topn_batch");
+    if (workspace_bytes < wmf_rank_batch_ws_bytes(n_users, n_cand)) { wmf_set_error("wmf_rank_topn_batch: workspace too small"); return WMF_EINVAL; }
+    return launch_error(wmf_launch_rank_batch(users, items, f, ld, bias, user_idx, n_users, cand_idx, n_cand, topn, out_pos, out_scores,
+                                              workspace, (hipStream_t)stream),
+                        "wmf_rank_topn_batch", f, ld, "", "device sort failed", "too many keys for the device sort (2^32 or more)");
 }
 
 int64_t wmf_recommend_workspace_bytes(int64_t n_users, int64_t topn, int32_t n_slices) { return wmf_recommend_ws_bytes(n_users, topn, n_slices); }
@@ -576,18 +602,8 @@ int wmf_recommend_topn(const float* users, const float* items, int f, int ld, in
                        int32_t* out_items, float* out_scores, int32_t* out_count, void* workspace, int64_t workspace_bytes, void* stream) {
     int rc = check_shape(f, ld);
     if (rc) return rc;
-    if (!users || !items || !user_idx || !out_items || !workspace) { wmf_set_error("wmf_recommend_topn: null pointer"); return WMF_EINVAL; }
-    if (n_users < 1 || n_items < 1 || n_items > 0x7fffffffLL || topn < 1 || topn > WMF_RECOMMEND_MAX_TOPN || n_slices < 0 ||
-        n_slices > WMF_RECOMMEND_MAX_SLICES) {
-        wmf_set_error("wmf_recommend_topn: need n_users >= 1, 1 <= n_items < 2^31, 1 <= topn <= %d, 0 <= n_slices <= %d (n_users=%lld, n_items=%lld, topn=%lld, n_slices=%d)",
-                      WMF_RECOMMEND_MAX_TOPN, WMF_RECOMMEND_MAX_SLICES, (long long)n_users, (long long)n_items, (long long)topn, (int)n_slices);
-        return WMF_EINVAL;
-    }
-    if (workspace_bytes < wmf_recommend_ws_bytes(n_users, topn, n_slices)) {
-        wmf_set_error("wmf_recommend_topn: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
-                      (long long)wmf_recommend_ws_bytes(n_users, topn, n_slices));
-        return WMF_EINVAL;
-    }
+    if ((rc = check_scan_call("wmf_recommend_topn", users, items, user_idx, out_items, workspace, "null pointer", nullptr, "n_users", n_users, "n_items",
+                              n_items, &topn, n_slices, workspace_bytes, [&] { return wmf_recommend_ws_bytes(n_users, topn, n_slices); }))) return rc;
     return launch_error(wmf_launch_recommend(users, items, ld, bias, user_idx, n_users, n_items, seen_indptr, seen_indices, topn, n_slices,
                                              out_items, out_scores, out_count, workspace, (hipStream_t)stream),
                         "wmf_recommend_topn", f, ld, "");
@@ -610,21 +626,10 @@ int wmf_similar_topn(const float* queries, const float* catalogue, int f, int ld
                      void* workspace, int64_t workspace_bytes, void* stream) {
     int rc = check_shape(f, ld);
     if (rc) return rc;
-    if (!queries || !catalogue || !query_idx || !out_rows || !workspace) { wmf_set_error("wmf_similar_topn: null pointer"); return WMF_EINVAL; }
-    if (!q_inv_norm != !c_inv_norm || !excl_indptr != !excl_indices) {
-        wmf_set_error("wmf_similar_topn: q_inv_norm and c_inv_norm, excl_indptr and excl_indices: both or neither"); return WMF_EINVAL;
-    }
-    if (n_queries < 1 || n_rows < 1 || n_rows > 0x7fffffffLL || topn < 1 || topn > WMF_RECOMMEND_MAX_TOPN || n_slices < 0 ||
-        n_slices > WMF_RECOMMEND_MAX_SLICES) {
-        wmf_set_error("wmf_similar_topn: need n_queries >= 1, 1 <= n_rows < 2^31, 1 <= topn <= %d, 0 <= n_slices <= %d (n_queries=%lld, n_rows=%lld, topn=%lld, n_slices=%d)",
-                      WMF_RECOMMEND_MAX_TOPN, WMF_RECOMMEND_MAX_SLICES, (long long)n_queries, (long long)n_rows, (long long)topn, (int)n_slices);
-        return WMF_EINVAL;
-    }
-    if (workspace_bytes < wmf_recommend_ws_bytes(n_queries, topn, n_slices)) {
-        wmf_set_error("wmf_similar_topn: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
-                      (long long)wmf_recommend_ws_bytes(n_queries, topn, n_slices));
-        return WMF_EINVAL;
-    }
+    const char* own = (!q_inv_norm != !c_inv_norm || !excl_indptr != !excl_indices)
+                          ? "q_inv_norm and c_inv_norm, excl_indptr and excl_indices: both or neither" : nullptr;
+    if ((rc = check_scan_call("wmf_similar_topn", queries, catalogue, query_idx, out_rows, workspace, "null pointer", own, "n_queries", n_queries,
+                              "n_rows", n_rows, &topn, n_slices, workspace_bytes, [&] { return wmf_recommend_ws_bytes(n_queries, topn, n_slices); }))) return rc;
     return launch_error(wmf_launch_similar(queries, catalogue, ld, bias, q_inv_norm, c_inv_norm, query_idx, n_queries, n_rows, exclude_self,
                                            excl_indptr, excl_indices, topn, n_slices, out_rows, out_scores, out_count, workspace,
                                            (hipStream_t)stream),
@@ -642,19 +647,10 @@ int wmf_rank_positions(const float* users, const float* items, int f, int ld, in
                        int64_t workspace_bytes, void* stream) {
     int rc = check_shape(f, ld);
     if (rc) return rc;
-    if (!users || !items || !user_idx || !target_indptr || !target_indices || !out_rank || !workspace || (!seen_indptr != !seen_indices)) {
-        wmf_set_error("wmf_rank_positions: null pointer (seen_indptr and seen_indices: both or neither)"); return WMF_EINVAL;
-    }
-    if (n_rows < 1 || n_items < 1 || n_items > 0x7fffffffLL || n_slices < 0 || n_slices > WMF_RECOMMEND_MAX_SLICES) {
-        wmf_set_error("wmf_rank_positions: need n_rows >= 1, 1 <= n_items < 2^31, 0 <= n_slices <= %d (n_rows=%lld, n_items=%lld, n_slices=%d)",
-                      WMF_RECOMMEND_MAX_SLICES, (long long)n_rows, (long long)n_items, (int)n_slices);
-        return WMF_EINVAL;
-    }
-    if (workspace_bytes < wmf_rank_positions_ws_bytes(n_rows)) {
-        wmf_set_error("wmf_rank_positions: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
-                      (long long)wmf_rank_positions_ws_bytes(n_rows));
-        return WMF_EINVAL;
-    }
+    const char* null_text = "null pointer (seen_indptr and seen_indices: both or neither)";
+    const char* own = (!target_indptr || !target_indices || (!seen_indptr != !seen_indices)) ? null_text : nullptr;
+    if ((rc = check_scan_call("wmf_rank_positions", users, items, user_idx, out_rank, workspace, null_text, own, "n_rows", n_rows, "n_items", n_items,
+                              nullptr, n_slices, workspace_bytes, [&] { return wmf_rank_positions_ws_bytes(n_rows); }))) return rc;
     return launch_error(wmf_launch_rank_positions(users, items, ld, bias, user_idx, n_rows, n_items, seen_indptr, seen_indices, target_indptr,
                                                   target_indices, n_slices, out_rank, out_score, workspace, (hipStream_t)stream),
                         "wmf_rank_positions", f, ld, "");
@@ -670,9 +666,9 @@ int wmf_hit_counts(const float* users, const float* items, int f, int ld, int bi
         return WMF_EINVAL;
     }
     if (n_pairs > 0 && (!pair_user || !pair_item || !pair_row || !candidates || !slot)) { wmf_set_error("wmf_hit_counts: null pointer"); return WMF_EINVAL; }
-    if (wmf_launch_hits(users, items, ld, bias, pair_user, pair_item, pair_row, n_pairs, candidates, n_cand, slot, topn, n_topn,
-                        hits, (hipStream_t)stream)) { wmf_set_error("wmf_hit_counts: hipMemsetAsync failed"); return WMF_EHIP; }
-    return check_launch("wmf_hit_counts");
+    return launch_error(wmf_launch_hits(users, items, ld, bias, pair_user, pair_item, pair_row, n_pairs, candidates, n_cand, slot, topn, n_topn,
+                                        hits, (hipStream_t)stream),
+                        "wmf_hit_counts", f, ld, "");
 }
 
 int wmf_gather_rows(const float* in, int ld, const int64_t* rows, int64_t n, float* out, void* stream) {
@@ -702,12 +698,16 @@ int wmf_coo_to_csr(const int64_t* rows, const int64_t* cols, const float* values
         (nnz > 0 && (!rows || !cols || !values || !indices_out || !values_out || !workspace))) {
         wmf_set_error("wmf_coo_to_csr: null pointer or bad size"); return WMF_EINVAL;
     }
-    const int rc = wmf_launch_coo_to_csr(rows, cols, values, nnz, n_rows, n_cols, indptr_out, indices_out, values_out, bad_flag,
-                                         workspace, workspace_bytes, (hipStream_t)stream);
-    if (rc == -3) { wmf_set_error("wmf_coo_to_csr: workspace too small (need %lld bytes)", (long long)wmf_csr_ws_bytes(nnz, n_rows, n_cols)); return WMF_EINVAL; }
-    if (rc == -4) { wmf_set_error("wmf_coo_to_csr: n_rows * n_cols must fit 63 bits and nnz 32"); return WMF_EINVAL; }
-    if (rc) { wmf_set_error("wmf_coo_to_csr: sort failed"); return WMF_EHIP; }
-    return check_launch("wmf_coo_to_csr");
+    static const char* const too_many = "n_rows * n_cols must fit 63 bits and nnz 32";
+    if ((n_rows > 0 && (unsigned long long)n_rows > 0x7fffffffffffffffull / (unsigned long long)n_cols) || nnz >= (1ll << 32)) {
+        wmf_set_error("wmf_coo_to_csr: %s", too_many); return WMF_EINVAL;
+    }
+    if (nnz > 0 && workspace_bytes < wmf_csr_ws_bytes(nnz, n_rows, n_cols)) {
+        wmf_set_error("wmf_coo_to_csr: workspace too small (need %lld bytes)", (long long)wmf_csr_ws_bytes(nnz, n_rows, n_cols)); return WMF_EINVAL;
+    }
+    return launch_error(wmf_launch_coo_to_csr(rows, cols, values, nnz, n_rows, n_cols, indptr_out, indices_out, values_out, bad_flag, workspace,
+                                              (hipStream_t)stream),
+                        "wmf_coo_to_csr", 0, 0, "", "sort failed", too_many);
 }
 
 int wmf_confidence_transform(float* values, int64_t nnz, double alpha, double beta, int mode, void* stream) {

@@ -26,6 +26,21 @@ __device__ __forceinline__ float wmf_row16_sum(float v) {
     return v;
 }
 
+// The score of a (user, item) pair by a 16-lane group, on every lane of it: lane gl handles 16-byte pieces gl, gl + 16, ... of the
+// two factor rows.  bias: column 0 does not enter the product; the score adds both column-0 values instead.  The one arithmetic
+// of predict, eval_prec, rank and the hit counts.
+__device__ __forceinline__ float wmf_pair_score(const float* __restrict__ xu, const float* __restrict__ yi, int nch, int gl, int bias) {
+    float s = 0.f;
+    for (int c = gl; c < nch; c += 16) {
+        const float4 a = reinterpret_cast<const float4*>(xu)[c];
+        const float4 b = reinterpret_cast<const float4*>(yi)[c];
+        float first = a.x * b.x;
+        if (bias && c == 0) first = a.x + b.x;
+        s += first + a.y * b.y + a.z * b.z + a.w * b.w;
+    }
+    return wmf_row16_sum(s);
+}
+
 // Four independent row sums as 16 v_add_f32_dpp (hipcc leaves a v_mov_dpp + add pair per stage).  The four
 // values are interleaved so that three instructions separate a register's write from its DPP read (the
 // hazard needs two wait states); the leading s_nop covers the first stage.

@@ -59,14 +59,10 @@ int64_t wmf_csr_ws_bytes(int64_t nnz, int64_t n_rows, int64_t n_cols) {
     return (int64_t)(2 * al256((size_t)nnz * 8) + 2 * al256((size_t)nnz * 4) + 256 + wmf_sort_ws_bytes(nnz) + 256);
 }
 
-// returns 0, -2 (HIP failure), -3 (workspace too small), -4 (n_rows * n_cols does not fit 63 bits or nnz >= 2^32)
+// (n_rows * n_cols fits 63 bits, nnz 32, and ws holds wmf_csr_ws_bytes: the entry point's checks)
 int wmf_launch_coo_to_csr(const int64_t* rows, const int64_t* cols, const float* vals, int64_t nnz, int64_t n_rows, int64_t n_cols,
-                          int64_t* indptr, int32_t* indices, float* values, int32_t* bad_flag, void* ws, int64_t ws_bytes,
-                          hipStream_t st) {
-    if (n_rows > 0 && n_cols > 0 && (unsigned long long)n_rows > (0x7fffffffffffffffull / (unsigned long long)n_cols)) return -4;
-    if (nnz >= (1ll << 32)) return -4;
-    if (nnz <= 0) return hipMemsetAsync(indptr, 0, (size_t)(n_rows + 1) * 8, st) == hipSuccess ? 0 : -2;
-    if (ws_bytes < wmf_csr_ws_bytes(nnz, n_rows, n_cols)) return -3;
+                          int64_t* indptr, int32_t* indices, float* values, int32_t* bad_flag, void* ws, hipStream_t st) {
+    if (nnz <= 0) return hipMemsetAsync(indptr, 0, (size_t)(n_rows + 1) * 8, st) == hipSuccess ? WMF_L_OK : WMF_L_HIP;
     char* base = static_cast<char*>(ws);
     const size_t a8 = al256((size_t)nnz * 8), a4 = al256((size_t)nnz * 4);
     auto* keys = reinterpret_cast<unsigned long long*>(base);
@@ -80,10 +76,10 @@ int wmf_launch_coo_to_csr(const int64_t* rows, const int64_t* cols, const float*
     WMF_LAUNCH("csr_keys_kernel", csr_keys_kernel, dim3((unsigned)grid), dim3(256), 0, st, rows, cols, nnz, n_rows, n_cols, keys, ids,
                bad_flag);
     bool in_alt = false;
-    if (const int src = wmf_sort_u64(keys, skeys, ids, sids, nnz, bits, temp, st, &in_alt)) return src;      // (-2 launch failure, -4 too many keys)
+    if (const int src = wmf_sort_u64(keys, skeys, ids, sids, nnz, bits, temp, st, &in_alt)) return src;
     if (!in_alt) { auto* tk = keys; keys = skeys; skeys = tk; auto* ti = ids; ids = sids; sids = ti; }   // (skeys / sids: the sorted arrays)
     WMF_LAUNCH("csr_gather_kernel", csr_gather_kernel, dim3((unsigned)grid), dim3(256), 0, st, skeys, sids, vals, nnz, n_cols, indices,
                values);
     WMF_LAUNCH("csr_indptr_kernel", csr_indptr_kernel, dim3((unsigned)grid), dim3(256), 0, st, skeys, nnz, n_rows, n_cols, indptr);
-    return 0;
+    return WMF_L_OK;
 }

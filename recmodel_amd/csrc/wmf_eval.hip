@@ -5,21 +5,6 @@
 #include "wmf_common.h"
 #include "wmf_internal.h"
 
-// dot of two factor rows by a 16-lane group: lane gl handles 16-byte pieces gl, gl+16, ...
-// bias: column 0 does not enter the product; the score adds both column-0 values instead.
-__device__ __forceinline__ float pair_score(const float* __restrict__ xu, const float* __restrict__ yi, int nch, int gl,
-                                            int bias) {
-    float s = 0.f;
-    for (int c = gl; c < nch; c += 16) {
-        const float4 a = reinterpret_cast<const float4*>(xu)[c];
-        const float4 b = reinterpret_cast<const float4*>(yi)[c];
-        float first = a.x * b.x;
-        if (bias && c == 0) first = a.x + b.x;
-        s += first + a.y * b.y + a.z * b.z + a.w * b.w;
-    }
-    return wmf_row16_sum(s);
-}
-
 __global__ __launch_bounds__(256) void predict_kernel(const float* __restrict__ users, const float* __restrict__ items,
                                                       int ld, int bias, const int32_t* __restrict__ ui, int64_t n_u,
                                                       const int32_t* __restrict__ ii, int64_t n_i, int64_t n,
@@ -28,7 +13,7 @@ __global__ __launch_bounds__(256) void predict_kernel(const float* __restrict__ 
     const int nch = ld >> 2;
     for (int64_t p = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4); p < n; p += (int64_t)gridDim.x * 16) {
         const int u = ui[n_u == 1 ? 0 : p], i = ii[n_i == 1 ? 0 : p];
-        const float s = pair_score(users + (int64_t)u * ld, items + (int64_t)i * ld, nch, gl, bias);
+        const float s = wmf_pair_score(users + (int64_t)u * ld, items + (int64_t)i * ld, nch, gl, bias);
         if (gl == 0) out[p] = s;
     }
 }
@@ -37,13 +22,13 @@ int wmf_launch_predict(const float* users, const float* items, int f, int ld, in
                        const int32_t* ii, int64_t n_i, float* out, hipStream_t st) {
     (void)f;
     const int64_t n = n_u > n_i ? n_u : n_i;
-    if (n <= 0) return 0;
+    if (n <= 0) return WMF_L_OK;
     int64_t grid = (n + 15) / 16;
     if (grid > 8192) grid = 8192;
     WmfProfScope ps("predict_kernel", st);
     hipLaunchKernelGGL(predict_kernel, dim3((unsigned)grid), dim3(256), 0, st, users, items, ld, bias, ui, n_u, ii, n_i,
                        n, out);
-    return 0;
+    return WMF_L_OK;
 }
 
 // One wave per user row, four stored entries at a time (one per 16-lane group).  Stored zeros are
@@ -64,7 +49,7 @@ __global__ __launch_bounds__(256) void eval_kernel(const float* __restrict__ use
             const int64_t e = act ? j : lo;                       // lo < hi inside this loop: a valid entry
             const float v = vals[e];
             const int i = indices[e];
-            const float s = pair_score(xu, items + (int64_t)i * ld, nch, gl, bias);
+            const float s = wmf_pair_score(xu, items + (int64_t)i * ld, nch, gl, bias);
             if (act && gl == 0 && v != 0.f) {
                 const double e = (double)v - (double)s;
                 sq += e * e; ab += fabs(e); cnt += 1.0;
@@ -100,7 +85,7 @@ int wmf_launch_eval(const float* users, const float* items, int f, int ld, int b
     WMF_LAUNCH("eval_kernel", eval_kernel, dim3((unsigned)grid), dim3(256), 0, st, users, items, ld, bias, indptr, indices,
                values, n, partial);
     WMF_LAUNCH("eval_finish_kernel", eval_finish_kernel, dim3(1), dim3(64), 0, st, partial, (int)grid, out3);
-    return 0;
+    return WMF_L_OK;
 }
 
 __global__ __launch_bounds__(256) void confidence_kernel(float* __restrict__ v, int64_t n, float alpha, float beta,

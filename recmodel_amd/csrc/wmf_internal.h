@@ -73,7 +73,7 @@ int wmf_launch_transform(const float* in, int64_t m, int f, int ld, const float*
 
 // ---- how a launch is routed ("How a launch is routed") --------------------------------------------------------------
 // What a launcher answers; wmf_api.hip (launch_error) turns it into WMF_E* and the message.
-enum WmfLaunchRc { WMF_L_OK = 0, WMF_L_NO_KERNEL = -1, WMF_L_HIP = -2, WMF_L_LAYOUT = -3 };
+enum WmfLaunchRc { WMF_L_OK = 0, WMF_L_NO_KERNEL = -1, WMF_L_HIP = -2, WMF_L_LAYOUT = -3, WMF_L_TOO_MANY_KEYS = -4 };
 
 // What is the same for every launch of one wmf_solve_rows call.  Host only: a launch site unpacks it into the kernel's positional
 // arguments.  side: NULL, or the {last feature, bias} pairs of the split layout (V is then the packed body); biasv / bstride: what
@@ -142,8 +142,7 @@ void wmf_launch_bias_adjust(const float* vals, const int32_t* indices, const flo
 // wmf_csr.hip: COO -> CSR, stable in (row, column)
 int64_t wmf_csr_ws_bytes(int64_t nnz, int64_t n_rows, int64_t n_cols);
 int wmf_launch_coo_to_csr(const int64_t* rows, const int64_t* cols, const float* vals, int64_t nnz, int64_t n_rows, int64_t n_cols,
-                          int64_t* indptr, int32_t* indices, float* values, int32_t* bad_flag, void* ws, int64_t ws_bytes,
-                          hipStream_t st);
+                          int64_t* indptr, int32_t* indices, float* values, int32_t* bad_flag, void* ws, hipStream_t st);
 int wmf_wide_supported(int f);
 int wmf_launch_wide(const RowArgs& a, RowList l);
 // wmf_iter.hip: rows with 33 .. wmf_iter_dmax entries whose whitened system is close to the identity, by a matrix-free
@@ -216,12 +215,10 @@ int wmf_launch_hits(const float* users, const float* items, int ld, int bias, co
                     const int32_t* slot, const int32_t* topn, int n_topn, int64_t* hits, hipStream_t st);
 int64_t wmf_rank_ws_bytes(int64_t n);
 int wmf_launch_rank(const float* users, const float* items, int f, int ld, int bias, const int32_t* user_idx,
-                    const int32_t* cand, int64_t n, int64_t topn, int32_t* out_pos, float* out_scores, void* ws,
-                    int64_t ws_bytes, hipStream_t st);
+                    const int32_t* cand, int64_t n, int64_t topn, int32_t* out_pos, float* out_scores, void* ws, hipStream_t st);
 int64_t wmf_rank_batch_ws_bytes(int64_t nu, int64_t nc);
 int wmf_launch_rank_batch(const float* users, const float* items, int f, int ld, int bias, const int32_t* user_idx, int64_t nu,
-                          const int32_t* cand, int64_t nc, int64_t topn, int32_t* out_pos, float* out_scores, void* ws,
-                          int64_t ws_bytes, hipStream_t st);
+                          const int32_t* cand, int64_t nc, int64_t topn, int32_t* out_pos, float* out_scores, void* ws, hipStream_t st);
 // wmf_recommend.hip: full-catalogue top-n with per-user exclusions (workspace: n_slices = 0 is sized for the automatic cap)
 int64_t wmf_recommend_ws_bytes(int64_t n_users, int64_t topn, int32_t n_slices);
 int wmf_launch_recommend(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,

@@ -16,20 +16,6 @@
 #include "wmf_internal.h"
 #include "wmf_scan.h"
 
-// same arithmetic as pair_score() in wmf_eval.hip (kept in step with it: eval_prec, predict and rank must agree)
-__device__ __forceinline__ float rank_pair_score(const float* __restrict__ xu, const float* __restrict__ yi, int nch, int gl,
-                                                 int bias) {
-    float s = 0.f;
-    for (int c = gl; c < nch; c += 16) {
-        const float4 a = reinterpret_cast<const float4*>(xu)[c];
-        const float4 b = reinterpret_cast<const float4*>(yi)[c];
-        float first = a.x * b.x;
-        if (bias && c == 0) first = a.x + b.x;
-        s += first + a.y * b.y + a.z * b.z + a.w * b.w;
-    }
-    return wmf_row16_sum(s);
-}
-
 __global__ __launch_bounds__(256) void hit_kernel(const float* __restrict__ users, const float* __restrict__ items, int ld,
                                                   int bias, const int32_t* __restrict__ pair_user,
                                                   const int32_t* __restrict__ pair_item, const int32_t* __restrict__ pair_row,
@@ -40,14 +26,14 @@ __global__ __launch_bounds__(256) void hit_kernel(const float* __restrict__ user
     const int nch = ld >> 2;
     for (int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); p < n_pairs; p += (int64_t)gridDim.x * 4) {
         const float* xu = users + (int64_t)pair_user[p] * ld;
-        const float s_true = rank_pair_score(xu, items + (int64_t)pair_item[p] * ld, nch, gl, bias);
+        const float s_true = wmf_pair_score(xu, items + (int64_t)pair_item[p] * ld, nch, gl, bias);
         const int32_t* crow = cand + (int64_t)pair_row[p] * n_cand;
         const int sl = slot[pair_row[p]];                          // this position holds the test item itself
         int higher = 0;
         for (int jb = 0; jb < n_cand; jb += 4) {                   // uniform trip count across the four groups
             const int j = jb + grp;
             const bool act = j < n_cand && j != sl;
-            const float s = rank_pair_score(xu, items + (int64_t)crow[j < n_cand ? j : 0] * ld, nch, gl, bias);
+            const float s = wmf_pair_score(xu, items + (int64_t)crow[j < n_cand ? j : 0] * ld, nch, gl, bias);
             higher += (act && s > s_true) ? 1 : 0;
         }
         higher += __shfl_xor(higher, 16);
@@ -118,11 +104,9 @@ int64_t wmf_rank_batch_ws_bytes(int64_t nu, int64_t nc) {
 
 int wmf_launch_rank_batch(const float* users, const float* items, int f, int ld, int bias, const int32_t* user_idx, int64_t nu,
                           const int32_t* cand, int64_t nc, int64_t topn, int32_t* out_pos, float* out_scores, void* ws,
-                          int64_t ws_bytes, hipStream_t st) {
+                          hipStream_t st) {
     (void)f;
-    if (nu <= 0 || nc <= 0) return 0;
-    if (nu * nc >= (int64_t)1 << 31) return -4;
-    if (ws_bytes < wmf_rank_batch_ws_bytes(nu, nc)) return -3;
+    if (nu <= 0 || nc <= 0) return WMF_L_OK;
     const size_t arr = (((size_t)nu * nc * 4 + 255) / 256) * 256;
     char* base = static_cast<char*>(ws);
     float* scores = reinterpret_cast<float*>(base);
@@ -143,23 +127,23 @@ int wmf_launch_rank_batch(const float* users, const float* items, int f, int ld,
     int ubits = 1;
     while ((nu >> ubits) != 0) ++ubits;
     bool in_alt = false;
-    if (const int src = wmf_sort_u64(keys, skeys, pos, spos, nu * nc, 32 + ubits, temp, st, &in_alt)) return src;      // (-2 launch failure, -4 too many keys)
+    if (const int src = wmf_sort_u64(keys, skeys, pos, spos, nu * nc, 32 + ubits, temp, st, &in_alt)) return src;
     hipLaunchKernelGGL(take_top_kernel, dim3(1024), dim3(256), 0, st, in_alt ? spos : pos, in_alt ? skeys : keys, nu, nc, topn, out_pos,
                        out_scores);
-    return 0;
+    return WMF_L_OK;
 }
 
 int wmf_launch_hits(const float* users, const float* items, int ld, int bias, const int32_t* pair_user,
                     const int32_t* pair_item, const int32_t* pair_row, int64_t n_pairs, const int32_t* cand, int n_cand,
                     const int32_t* slot, const int32_t* topn, int n_topn, int64_t* hits, hipStream_t st) {
-    if (hipMemsetAsync(hits, 0, (size_t)n_topn * sizeof(int64_t), st) != hipSuccess) return -2;
-    if (n_pairs <= 0) return 0;
+    if (hipMemsetAsync(hits, 0, (size_t)n_topn * sizeof(int64_t), st) != hipSuccess) return WMF_L_HIP;
+    if (n_pairs <= 0) return WMF_L_OK;
     int64_t grid = (n_pairs + 3) / 4;
     if (grid > 16384) grid = 16384;
     WmfProfScope ps("hit_kernel", st);
     hipLaunchKernelGGL(hit_kernel, dim3((unsigned)grid), dim3(256), 0, st, users, items, ld, bias, pair_user, pair_item, pair_row,
                        n_pairs, cand, n_cand, slot, topn, n_topn, reinterpret_cast<unsigned long long*>(hits));
-    return 0;
+    return WMF_L_OK;
 }
 
 // ---- rank of one user: top-n SELECT, as the reference's np.argpartition + argsort of the n best (wmf_model.py:40-43),
@@ -224,9 +208,8 @@ int64_t wmf_rank_ws_bytes(int64_t n) {
 
 int wmf_launch_rank(const float* users, const float* items, int f, int ld, int bias, const int32_t* user_idx,
                     const int32_t* cand, int64_t n, int64_t topn, int32_t* out_pos, float* out_scores, void* ws,
-                    int64_t ws_bytes, hipStream_t st) {
-    if (n <= 0) return 0;
-    if (ws_bytes < wmf_rank_ws_bytes(n)) return -3;
+                    hipStream_t st) {
+    if (n <= 0) return WMF_L_OK;
     const size_t arr = (((size_t)n * 4 + 255) / 256) * 256;
     char* base = static_cast<char*>(ws);
     float* scores = reinterpret_cast<float*>(base);
@@ -235,21 +218,21 @@ int wmf_launch_rank(const float* users, const float* items, int f, int ld, int b
     uint32_t* bins = reinterpret_cast<uint32_t*>(base + 5 * arr);
     uint32_t* ctrl = bins + 4096;
     void* temp = base + 5 * arr + 4096 * 4 + 256;
-    if (wmf_launch_predict(users, items, f, ld, bias, user_idx, 1, cand, n, scores, st)) return -1;
-    if (hipMemsetAsync(bins, 0, 4096 * 4 + 256, st) != hipSuccess) return -2;
+    if (wmf_launch_predict(users, items, f, ld, bias, user_idx, 1, cand, n, scores, st)) return WMF_L_HIP;
+    if (hipMemsetAsync(bins, 0, 4096 * 4 + 256, st) != hipSuccess) return WMF_L_HIP;
     int64_t grid = (n + 255) / 256;
     if (grid > 2048) grid = 2048;
     WMF_LAUNCH("rank_hist_kernel", rank_hist_kernel, dim3((unsigned)grid), dim3(256), 0, st, scores, n, bins);
     WMF_LAUNCH("rank_pick_kernel", rank_pick_kernel, dim3(1), dim3(256), 0, st, bins, topn, ctrl);
     WMF_LAUNCH("rank_compact_kernel", rank_compact_kernel, dim3((unsigned)grid), dim3(256), 0, st, scores, n, ctrl, keys);
     uint32_t host_ctrl[2] = {0, 0};
-    if (hipMemcpyAsync(host_ctrl, ctrl, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -2;
+    if (hipMemcpyAsync(host_ctrl, ctrl, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return WMF_L_HIP;
     const size_t m = host_ctrl[1];
-    if ((int64_t)m < topn || (int64_t)m > n) return -2;
+    if ((int64_t)m < topn || (int64_t)m > n) return WMF_L_HIP;
     bool in_alt = false;
-    if (const int src = wmf_sort_u64(keys, skeys, nullptr, nullptr, (int64_t)m, 64, temp, st, &in_alt)) return src;      // (-2 launch failure, -4 too many keys)
+    if (const int src = wmf_sort_u64(keys, skeys, nullptr, nullptr, (int64_t)m, 64, temp, st, &in_alt)) return src;
     if (!in_alt) skeys = keys;
     hipLaunchKernelGGL(rank_take_kernel, dim3((unsigned)((topn + 255) / 256 > 1024 ? 1024 : (topn + 255) / 256)), dim3(256), 0, st,
                        skeys, scores, topn, out_pos, out_scores);
-    return 0;
+    return WMF_L_OK;
 }

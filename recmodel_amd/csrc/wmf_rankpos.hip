@@ -196,36 +196,25 @@ int64_t wmf_rank_positions_ws_bytes(int64_t n_rows) {
 }
 static_assert(WMF_RANKPOS_WS_PER_ROW == RP_T * 16 + 4, "tkey, counts and tpos of RP_T slots and tn, per row");
 
-template <int NIT, int TPS>
-static int rp_launch_scan(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_rows, int64_t n_items,
-                          const RankposWs& w, int n_slices, hipStream_t st) {
-    const size_t lds = wmf_scan_stage_bytes(TPS, ld) + (size_t)RP_NW * 16 * RP_T * 8 + (size_t)RP_NW * 16 * (RP_T + 1) * 4;
-    const int64_t tiles = (n_items + 15) / 16, tiles_per_slice = (tiles + n_slices - 1) / n_slices;
-    const int64_t n_work = ((n_rows + 16 * RP_NW - 1) / (16 * RP_NW)) * n_slices;
-    const int64_t grid = n_work < WMF_SCAN_GRID ? n_work : WMF_SCAN_GRID;
-    static const char* name = wmf_kname("rankpos_scan_kernel<%d, %d>", NIT, TPS);
-    WMF_LAUNCH_LDS(name, (rankpos_scan_kernel<NIT, TPS>), 64 * 1024, dim3((unsigned)grid), dim3(64 * RP_NW), lds, st, users, items, ld, bias,
-                   user_idx, n_rows, n_items, w.tkey, w.tn, n_slices, tiles_per_slice, n_work, w.counts);
-    return WMF_L_OK;
-}
-
 int wmf_launch_rank_positions(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_rows,
                               int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const int64_t* target_indptr,
                               const int32_t* target_indices, int32_t n_slices, int32_t* out_rank, float* out_score, void* ws, hipStream_t st) {
-    const int nit = ((ld >> 2) + 3) >> 2;
-    if (nit > 17) return WMF_L_NO_KERNEL;
     const RankposWs w = rp_carve(ws, n_rows);
-    const int slices = wmf_recommend_slices(n_rows, n_items, 1, n_slices);              // (topn = 1: the four-wave block of that scan)
+    // (topn = 1: the slices of the four-wave block of wmf_recommend.hip's scan)
+    WmfScanArgs a = {users, items, ld, bias, user_idx, n_rows, n_items, wmf_recommend_slices(n_rows, n_items, 1, n_slices), st};
+    wmf_scan_geometry(a, RP_NW);
     int64_t row_grid = (n_rows + 3) / 4;
     if (row_grid > WMF_RANKPOS_ROW_GRID) row_grid = WMF_RANKPOS_ROW_GRID;
-    WMF_LAUNCH("rankpos_target_kernel", rankpos_target_kernel, dim3((unsigned)row_grid), dim3(256), 0, st, users, items, ld, bias, user_idx, n_rows,
-               n_items, target_indptr, target_indices, out_rank, out_score, w.tkey, w.counts, w.tpos, w.tn);
-    int rc;
-    if (nit <= 4) rc = rp_launch_scan<4, 4>(users, items, ld, bias, user_idx, n_rows, n_items, w, slices, st);
-    else if (nit <= 9) rc = rp_launch_scan<9, 2>(users, items, ld, bias, user_idx, n_rows, n_items, w, slices, st);
-    else rc = rp_launch_scan<17, 1>(users, items, ld, bias, user_idx, n_rows, n_items, w, slices, st);
-    if (rc) return rc;
-    WMF_LAUNCH("rankpos_finish_kernel", rankpos_finish_kernel, dim3((unsigned)row_grid), dim3(256), 0, st, users, items, ld, bias, user_idx, n_rows,
-               n_items, seen_indptr, seen_indices, target_indptr, w.tkey, w.counts, w.tpos, w.tn, out_rank);
-    return WMF_L_OK;
+    return wmf_dispatch_scan(ld, [&](auto nit, auto tps) {           // (no kernel for the width: nothing is launched)
+        constexpr int NIT = decltype(nit)::value, TPS = decltype(tps)::value;
+        WMF_LAUNCH("rankpos_target_kernel", rankpos_target_kernel, dim3((unsigned)row_grid), dim3(256), 0, st, users, items, ld, bias, user_idx,
+                   n_rows, n_items, target_indptr, target_indices, out_rank, out_score, w.tkey, w.counts, w.tpos, w.tn);
+        static const char* name = wmf_kname("rankpos_scan_kernel<%d, %d>", NIT, TPS);
+        WMF_LAUNCH_LDS(name, (rankpos_scan_kernel<NIT, TPS>), 64 * 1024, dim3((unsigned)a.grid), dim3(64 * RP_NW),
+                       wmf_scan_stage_bytes(TPS, ld) + (size_t)RP_NW * 16 * RP_T * 8 + (size_t)RP_NW * 16 * (RP_T + 1) * 4, st, a.users, a.items,
+                       a.ld, a.bias, a.user_idx, a.n_rows, a.n_items, w.tkey, w.tn, a.n_slices, a.tiles_per_slice, a.n_work, w.counts);
+        WMF_LAUNCH("rankpos_finish_kernel", rankpos_finish_kernel, dim3((unsigned)row_grid), dim3(256), 0, st, users, items, ld, bias, user_idx,
+                   n_rows, n_items, seen_indptr, seen_indices, target_indptr, w.tkey, w.counts, w.tpos, w.tn, out_rank);
+        return (int)WMF_L_OK;
+    });
 }

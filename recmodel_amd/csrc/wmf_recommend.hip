@@ -104,36 +104,24 @@ void wmf_launch_topn_merge(const unsigned long long* partial, int64_t n_rows, in
                out_rows, out_scores, out_count);
 }
 
-template <int NIT, int TPS>
-static int rec_launch_scan(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
-                           int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, int topn, int n_slices,
-                           unsigned long long* partial, hipStream_t st) {
-    return wmf_dispatch_list<4, 2>(rec_waves(topn), [&](auto nw) {
-        constexpr int NW = decltype(nw)::value;
-        const int cap = rec_cap(topn);
-        const size_t lds = wmf_scan_stage_bytes(TPS, ld) + rec_lds_bytes(NW, cap);
-        const int64_t tiles = (n_items + 15) / 16, tiles_per_slice = (tiles + n_slices - 1) / n_slices;
-        const int64_t n_work = ((n_users + 16 * NW - 1) / (16 * NW)) * n_slices;
-        const int64_t grid = n_work < WMF_SCAN_GRID ? n_work : WMF_SCAN_GRID;
-        static const char* name = wmf_kname("recommend_scan_kernel<%d, %d, %d>", NIT, TPS, NW);
-        WMF_LAUNCH_LDS(name, (recommend_scan_kernel<NIT, TPS, NW>), 112 * 1024, dim3((unsigned)grid), dim3(64 * NW), lds, st, users, items, ld,
-                       bias, user_idx, n_users, n_items, seen_indptr, seen_indices, topn, cap, n_slices, tiles_per_slice, n_work, partial);
-        return (int)WMF_L_OK;
-    });
-}
-
 int wmf_launch_recommend(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
                          int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, int64_t topn, int32_t n_slices,
                          int32_t* out_items, float* out_scores, int32_t* out_count, void* ws, hipStream_t st) {
-    const int slices = wmf_recommend_slices(n_users, n_items, topn, n_slices);
+    WmfScanArgs a = {users, items, ld, bias, user_idx, n_users, n_items, wmf_recommend_slices(n_users, n_items, topn, n_slices), st};
     unsigned long long* partial = reinterpret_cast<unsigned long long*>(ws);
-    const int nit = ((ld >> 2) + 3) >> 2;
-    int rc;
-    if (nit <= 4) rc = rec_launch_scan<4, 4>(users, items, ld, bias, user_idx, n_users, n_items, seen_indptr, seen_indices, (int)topn, slices, partial, st);
-    else if (nit <= 9) rc = rec_launch_scan<9, 2>(users, items, ld, bias, user_idx, n_users, n_items, seen_indptr, seen_indices, (int)topn, slices, partial, st);
-    else if (nit <= 17) rc = rec_launch_scan<17, 1>(users, items, ld, bias, user_idx, n_users, n_items, seen_indptr, seen_indices, (int)topn, slices, partial, st);
-    else return WMF_L_NO_KERNEL;
+    const int n = (int)topn, cap = rec_cap(topn);
+    const int rc = wmf_dispatch_scan(ld, [&](auto nit, auto tps) {
+        return wmf_dispatch_list<4, 2>(rec_waves(topn), [&](auto nw) {
+            constexpr int NIT = decltype(nit)::value, TPS = decltype(tps)::value, NW = decltype(nw)::value;
+            wmf_scan_geometry(a, NW);
+            static const char* name = wmf_kname("recommend_scan_kernel<%d, %d, %d>", NIT, TPS, NW);
+            WMF_LAUNCH_LDS(name, (recommend_scan_kernel<NIT, TPS, NW>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW),
+                           wmf_scan_stage_bytes(TPS, ld) + rec_lds_bytes(NW, cap), st, a.users, a.items, a.ld, a.bias, a.user_idx, a.n_rows,
+                           a.n_items, seen_indptr, seen_indices, n, cap, a.n_slices, a.tiles_per_slice, a.n_work, partial);
+            return (int)WMF_L_OK;
+        });
+    });
     if (rc) return rc;
-    wmf_launch_topn_merge(partial, n_users, slices, (int)topn, out_items, out_scores, out_count, st);
+    wmf_launch_topn_merge(partial, n_users, a.n_slices, n, out_items, out_scores, out_count, st);
     return WMF_L_OK;
 }

@@ -3,6 +3,7 @@
 // one scoring loop, the epilogue and the scoring rule as compile-time policies (wmf_similar.hip: the neighbours of a row).
 #pragma once
 #include "wmf_common.h"
+#include "wmf_internal.h"
 
 #define WMF_SCAN_GRID 4096           /* workgroups of a catalogue scan: (user block, slice) pairs beyond it take another trip */
 
@@ -205,4 +206,30 @@ __device__ __forceinline__ void wmf_catalogue_scan(const float* __restrict__ use
     }
 #undef WMF_SCAN_LOAD_STAGE
 #undef WMF_SCAN_STORE_STAGE
+}
+
+// ---- the host side of a scan launch ---------------------------------------------------------------------------------------------
+// What every launch of a catalogue scan takes, in the spirit of RowArgs.  Host only: a launch site unpacks it into the kernel's
+// positional arguments.  tiles_per_slice, n_work and grid are wmf_scan_geometry's.
+struct WmfScanArgs {
+    const float* users; const float* items; int ld, bias; const int32_t* user_idx;
+    int64_t n_rows, n_items; int n_slices; hipStream_t st;
+    int64_t tiles_per_slice, n_work, grid;
+};
+// n_slices slices of the catalogue's 16-item tiles, one work unit per (block of 16 nw rows, slice), WMF_SCAN_GRID workgroups at most
+static inline void wmf_scan_geometry(WmfScanArgs& a, int nw) {
+    const int64_t tiles = (a.n_items + 15) / 16;
+    a.tiles_per_slice = (tiles + a.n_slices - 1) / a.n_slices;
+    a.n_work = ((a.n_rows + 16 * nw - 1) / (16 * nw)) * a.n_slices;
+    a.grid = a.n_work < WMF_SCAN_GRID ? a.n_work : WMF_SCAN_GRID;
+}
+// The width class of a scan (as wmf_dispatch_list): fn(wmf_int<NIT>{}, wmf_int<TPS>{}) for the class that holds a row of ld floats,
+// WMF_L_NO_KERNEL beyond the widest.  Exactly these three are instantiated.
+template <class Fn>
+static inline int wmf_dispatch_scan(int ld, Fn&& fn) {
+    const int nit = ((ld >> 2) + 3) >> 2;
+    if (nit <= 4) return fn(wmf_int<4>{}, wmf_int<4>{});
+    if (nit <= 9) return fn(wmf_int<9>{}, wmf_int<2>{});
+    if (nit <= 17) return fn(wmf_int<17>{}, wmf_int<1>{});
+    return WMF_L_NO_KERNEL;
 }

@@ -101,41 +101,27 @@ void wmf_launch_row_inv_norms(const float* M, int64_t n, int f, int ld, int bias
     WMF_LAUNCH("row_inv_norms_kernel", row_inv_norms_kernel, dim3((unsigned)grid), dim3(256), 0, st, M, n, f, ld, bias ? 1 : 0, out);
 }
 
-template <int NIT, int TPS>
-static int sim_launch_scan(const float* queries, const float* catalogue, int ld, int bias, const float* q_scale, const float* c_scale,
-                           const int32_t* query_idx, int64_t n_queries, int64_t n_rows, const int32_t* self_idx, const int64_t* excl_indptr,
-                           const int32_t* excl_indices, int topn, int n_slices, unsigned long long* partial, hipStream_t st) {
-    return wmf_dispatch_list<4, 2>(rec_waves(topn), [&](auto nw) {
-        constexpr int NW = decltype(nw)::value;
-        const int cap = rec_cap(topn);
-        const size_t lds = wmf_scan_stage_bytes(TPS, ld) + rec_lds_bytes(NW, cap) + (size_t)2 * TPS * 16 * 4;
-        const int64_t tiles = (n_rows + 15) / 16, tiles_per_slice = (tiles + n_slices - 1) / n_slices;
-        const int64_t n_work = ((n_queries + 16 * NW - 1) / (16 * NW)) * n_slices;
-        const int64_t grid = n_work < WMF_SCAN_GRID ? n_work : WMF_SCAN_GRID;
-        static const char* name = wmf_kname("similar_scan_kernel<%d, %d, %d>", NIT, TPS, NW);
-        WMF_LAUNCH_LDS(name, (similar_scan_kernel<NIT, TPS, NW>), 112 * 1024, dim3((unsigned)grid), dim3(64 * NW), lds, st, queries, catalogue,
-                       ld, bias, q_scale, c_scale, query_idx, n_queries, n_rows, self_idx, excl_indptr, excl_indices, topn, cap, n_slices,
-                       tiles_per_slice, n_work, partial);
-        return (int)WMF_L_OK;
-    });
-}
-
 int wmf_launch_similar(const float* queries, const float* catalogue, int ld, int bias, const float* q_inv_norm, const float* c_inv_norm,
                        const int32_t* query_idx, int64_t n_queries, int64_t n_rows, int exclude_self, const int64_t* excl_indptr,
                        const int32_t* excl_indices, int64_t topn, int32_t n_slices, int32_t* out_rows, float* out_scores,
                        int32_t* out_count, void* ws, hipStream_t st) {
-    const int slices = wmf_recommend_slices(n_queries, n_rows, topn, n_slices);
+    WmfScanArgs a = {queries, catalogue, ld, bias, query_idx, n_queries, n_rows, wmf_recommend_slices(n_queries, n_rows, topn, n_slices), st};
     unsigned long long* partial = reinterpret_cast<unsigned long long*>(ws);
     const int32_t* self_idx = exclude_self ? query_idx : nullptr;
-    const int nit = ((ld >> 2) + 3) >> 2;
-    int rc;
-#define SIM_ARGS queries, catalogue, ld, bias, q_inv_norm, c_inv_norm, query_idx, n_queries, n_rows, self_idx, excl_indptr, excl_indices, (int)topn, slices, partial, st
-    if (nit <= 4) rc = sim_launch_scan<4, 4>(SIM_ARGS);
-    else if (nit <= 9) rc = sim_launch_scan<9, 2>(SIM_ARGS);
-    else if (nit <= 17) rc = sim_launch_scan<17, 1>(SIM_ARGS);
-    else return WMF_L_NO_KERNEL;
-#undef SIM_ARGS
+    const int n = (int)topn, cap = rec_cap(topn);
+    const int rc = wmf_dispatch_scan(ld, [&](auto nit, auto tps) {
+        return wmf_dispatch_list<4, 2>(rec_waves(topn), [&](auto nw) {
+            constexpr int NIT = decltype(nit)::value, TPS = decltype(tps)::value, NW = decltype(nw)::value;
+            wmf_scan_geometry(a, NW);
+            static const char* name = wmf_kname("similar_scan_kernel<%d, %d, %d>", NIT, TPS, NW);
+            WMF_LAUNCH_LDS(name, (similar_scan_kernel<NIT, TPS, NW>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW),
+                           wmf_scan_stage_bytes(TPS, ld) + rec_lds_bytes(NW, cap) + (size_t)2 * TPS * 16 * 4, st, a.users, a.items, a.ld, a.bias,
+                           q_inv_norm, c_inv_norm, a.user_idx, a.n_rows, a.n_items, self_idx, excl_indptr, excl_indices, n, cap, a.n_slices,
+                           a.tiles_per_slice, a.n_work, partial);
+            return (int)WMF_L_OK;
+        });
+    });
     if (rc) return rc;
-    wmf_launch_topn_merge(partial, n_queries, slices, (int)topn, out_rows, out_scores, out_count, st);
+    wmf_launch_topn_merge(partial, n_queries, a.n_slices, n, out_rows, out_scores, out_count, st);
     return WMF_L_OK;
 }

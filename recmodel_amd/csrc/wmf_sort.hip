@@ -149,8 +149,8 @@ size_t wmf_sort_ws_bytes(int64_t n) {
 int wmf_sort_u64(unsigned long long* keys, unsigned long long* keys_alt, uint32_t* vals, uint32_t* vals_alt, int64_t n, int bits,
                  void* ws, hipStream_t st, bool* in_alt) {
     *in_alt = false;
-    if (n <= 1 || bits <= 0) return 0;
-    if (n >= (1ll << 32)) return -4;                             // tile offsets and the payload are 32-bit (wmf_sort.h: "too many keys")
+    if (n <= 1 || bits <= 0) return WMF_L_OK;
+    if (n >= (1ll << 32)) return WMF_L_TOO_MANY_KEYS;            // tile offsets and the payload are 32-bit (wmf_sort.h)
     const int64_t ntiles = (n + SORT_TILE - 1) / SORT_TILE, len = 16 * ntiles, nchunks = (len + SORT_SCAN_CHUNK - 1) / SORT_SCAN_CHUNK;
     uint32_t* hist = static_cast<uint32_t*>(ws);
     uint32_t* sums = hist + ((len + 63) / 64) * 64;
@@ -169,5 +169,5 @@ int wmf_sort_u64(unsigned long long* keys, unsigned long long* keys_alt, uint32_
         uint32_t* tv = vi; vi = vo; vo = tv;
         *in_alt = !*in_alt;
     }
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return hipGetLastError() == hipSuccess ? WMF_L_OK : WMF_L_HIP;
 }

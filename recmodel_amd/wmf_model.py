@@ -37,6 +37,14 @@ RECOMMEND_MAX_TOPN = 128          # WMF_RECOMMEND_MAX_TOPN of include/wmf_hip.h:
 RANKPOS_MAX_TARGETS = 16          # WMF_RANKPOS_MAX_TARGETS of include/wmf_hip.h: rank_positions() splits longer rows
 
 
+def _wrapped_ids(ids, n, what, dtype=np.int32):
+    """The integer array ``ids`` as row numbers of a matrix of ``n`` rows -- a negative id counts from the end -- in ``dtype``;
+    an IndexError that names ``what`` for an id outside [-n, n)."""
+    if len(ids) and (ids.min() < -n or ids.max() >= n):
+        raise IndexError(f"{what} index out of bounds")
+    return np.where(ids < 0, ids + n, ids).astype(dtype)
+
+
 def _transformed_dtype(count_dtype, alpha, beta, pre_process_count):
     """dtype of the confidence weights the reference ends up with (wmf_model.py:119-123), by NumPy's own rules."""
     probe = np.ones(1, dtype=count_dtype)
@@ -189,11 +197,8 @@ class WMF(RecModel):
             return np.zeros(0, dtype=self.items.dtype)
         if len(u) != len(i) and len(i) == 1:
             i = np.repeat(i, len(u))
-        if (u.min() < -self.users.shape[0] or u.max() >= self.users.shape[0]
-                or i.min() < -self.items.shape[0] or i.max() >= self.items.shape[0]):
-            raise IndexError("user or item index out of bounds")
-        u = np.where(u < 0, u + self.users.shape[0], u).astype(np.int32)
-        i = np.where(i < 0, i + self.items.shape[0], i).astype(np.int32)
+        u = _wrapped_ids(u, self.users.shape[0], "user or item")
+        i = _wrapped_ids(i, self.items.shape[0], "user or item")
         users_t, items_t, f, ld = self._device_factors()
         lib = _lib.load()
         ut, it = torch.from_numpy(u).cuda(), torch.from_numpy(i).cuda()
@@ -219,15 +224,11 @@ class WMF(RecModel):
             return self._rank_many(items, users, keep)
         if keep <= 0:
             return items[:0]
-        u = int(np.asarray(users).reshape(-1)[0])
-        idx = np.asarray(items).astype(np.int64)
-        if not (-self.users.shape[0] <= u < self.users.shape[0]) or idx.min() < -self.items.shape[0] or idx.max() >= self.items.shape[0]:
-            raise IndexError("user or item index out of bounds")
-        idx = np.where(idx < 0, idx + self.items.shape[0], idx).astype(np.int32)
+        u = _wrapped_ids(np.array([int(np.asarray(users).reshape(-1)[0])]), self.users.shape[0], "user or item")
+        idx = _wrapped_ids(np.asarray(items).astype(np.int64), self.items.shape[0], "user or item")
         users_t, items_t, f, ld = self._device_factors()
         lib = _lib.load()
-        ut = torch.tensor([u % self.users.shape[0]], dtype=torch.int32, device="cuda")
-        it = torch.from_numpy(idx).cuda()
+        ut, it = torch.from_numpy(u).cuda(), torch.from_numpy(idx).cuda()
         ws_bytes = int(lib.wmf_rank_workspace_bytes(n))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
         pos = torch.empty(keep, dtype=torch.int32, device="cuda")
@@ -239,13 +240,8 @@ class WMF(RecModel):
         """rank() for a list of users: scores of 16 x 16 (user, candidate) tiles by MFMA, one segmented sort
         (wmf_rank_topn_batch), in batches of at most 2^26 scores."""
         n = len(items)
-        u = np.asarray(users).reshape(-1).astype(np.int64)
-        idx = np.asarray(items).astype(np.int64)
-        if (u.min() < -self.users.shape[0] or u.max() >= self.users.shape[0] or idx.min() < -self.items.shape[0]
-                or idx.max() >= self.items.shape[0]):
-            raise IndexError("user or item index out of bounds")
-        u = np.where(u < 0, u + self.users.shape[0], u).astype(np.int32)
-        idx = np.where(idx < 0, idx + self.items.shape[0], idx).astype(np.int32)
+        u = _wrapped_ids(np.asarray(users).reshape(-1).astype(np.int64), self.users.shape[0], "user or item")
+        idx = _wrapped_ids(np.asarray(items).astype(np.int64), self.items.shape[0], "user or item")
         users_t, items_t, f, ld = self._device_factors()
         lib = _lib.load()
         it = torch.from_numpy(idx).cuda()
@@ -280,14 +276,11 @@ class WMF(RecModel):
             if not scipy.sparse.issparse(exclude) or exclude.shape != (n_users_model, n_items):
                 raise ValueError(f"exclude must be a sparse matrix of shape {(n_users_model, n_items)}, got {getattr(exclude, 'shape', None)}")
         one = np.ndim(users) == 0
-        u = np.atleast_1d(np.asarray(users)).reshape(-1).astype(np.int64)
-        if len(u) and (u.min() < -n_users_model or u.max() >= n_users_model):
-            raise IndexError("user index out of bounds")
+        u = _wrapped_ids(np.atleast_1d(np.asarray(users)).reshape(-1).astype(np.int64), n_users_model, "user", np.int64)
         topn = int(topn)
         if topn < 1:
             raise ValueError(f"topn must be at least 1, not {topn}")
         _lib.require_gpu()
-        u = np.where(u < 0, u + n_users_model, u)
         out_items = np.full((len(u), topn), -1, dtype=np.int64)
         out_scores = np.full((len(u), topn), -np.inf, dtype=np.float32)
         if exclude is not None and len(u):
@@ -310,31 +303,41 @@ class WMF(RecModel):
             out_items, out_scores = out_items[0], out_scores[0]
         return (out_items, out_scores) if return_scores else out_items
 
-    def _recommend_fused(self, u, topn, seen, out_items, out_scores):
-        """Batches of RECOMMEND_BATCH_USERS users, all enqueued on one stream; one copy to the host at the end."""
-        users_t, items_t, f, ld = self._device_factors()
-        lib = _lib.load()
-        n, n_items = len(u), self.items.shape[0]
-        ut = torch.from_numpy(u.astype(np.int32)).cuda()
-        items_d = torch.empty(n, topn, dtype=torch.int32, device="cuda")
-        scores_d = torch.empty(n, topn, dtype=torch.float32, device="cuda") if out_scores is not None else None
-        if seen is not None:
-            indptr_d = torch.from_numpy(seen.indptr.astype(np.int64)).cuda()
-            indices_d = torch.from_numpy(np.append(seen.indices, 0).astype(np.int32)).cuda()      # (one spare: never empty)
+    def _scan_batches(self, ids, csrs, ws_bytes, outs, call):
+        """The batch loop of the fused catalogue calls (recommend, the neighbours, rank_positions): windows of
+        RECOMMEND_BATCH_USERS rows, all enqueued on one stream, one copy to the host at the end.  ``ids``: the row of the factors
+        each batch position reads; ``csrs``: per-position lists as (indptr, indices), or None, uploaded once; ``ws_bytes(rows)``:
+        the workspace of a batch; ``outs``: the device outputs (None: not asked for).  ``call(b0, nb, ids, csrs, ws, ws_bytes,
+        stream)`` enqueues the nb positions from b0 on: pointers to the ids from b0 on and, for each CSR, to the window of its
+        pointers and to its one indices array (None, None without it) -- row b of the batch is row b0 + b.  Returns the host
+        copies of ``outs``."""
+        n = len(ids)
+        ids_d = torch.from_numpy(ids.astype(np.int32)).cuda()
+        csrs_d = [None if c is None else (torch.from_numpy(c[0].astype(np.int64)).cuda(),         # (one spare index: never empty)
+                                          torch.from_numpy(np.append(c[1], 0).astype(np.int32)).cuda()) for c in csrs]
         per = max(1, int(RECOMMEND_BATCH_USERS))
-        ws_bytes = int(lib.wmf_recommend_workspace_bytes(min(per, n), topn, 0))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+        nbytes = int(ws_bytes(min(per, n)))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
         for b0 in range(0, n, per):
             nb = min(per, n - b0)
-            # row b of the batch's CSR = row b0 + b of `seen`: a window of its pointers, which index the one indices array
-            ptr_b = indptr_d[b0: b0 + nb + 1] if seen is not None else None
-            _lib.check(lib.wmf_recommend_topn(
-                _ptr(users_t), _ptr(items_t), f, ld, int(self.bias is True), _ptr(ut[b0:]), nb, n_items,
-                _ptr(ptr_b) if ptr_b is not None else None, _ptr(indices_d) if seen is not None else None, topn, 0,
-                _ptr(items_d[b0:]), _ptr(scores_d[b0:]) if scores_d is not None else None, None, _ptr(ws), ws_bytes, _stream()))
-        out_items[:] = items_d.cpu().numpy()
+            windows = [(_ptr(c[0][b0: b0 + nb + 1]), _ptr(c[1])) if c else (None, None) for c in csrs_d]
+            _lib.check(call(b0, nb, _ptr(ids_d[b0:]), windows, _ptr(ws), nbytes, _stream()))
+        return [o if o is None else o.cpu().numpy() for o in outs]
+
+    def _recommend_fused(self, u, topn, seen, out_items, out_scores):
+        """wmf_recommend_topn in batches (_scan_batches); the rows of ``seen`` are those of ``u``."""
+        users_t, items_t, f, ld = self._device_factors()
+        lib = _lib.load()
+        items_d = torch.empty(len(u), topn, dtype=torch.int32, device="cuda")
+        scores_d = torch.empty(len(u), topn, dtype=torch.float32, device="cuda") if out_scores is not None else None
+        out_items[:], scores = self._scan_batches(
+            u, [None if seen is None else (seen.indptr, seen.indices)],
+            lambda rows: lib.wmf_recommend_workspace_bytes(rows, topn, 0), [items_d, scores_d],
+            lambda b0, nb, ids, csrs, *ws: lib.wmf_recommend_topn(
+                _ptr(users_t), _ptr(items_t), f, ld, int(self.bias is True), ids, nb, self.items.shape[0], *csrs[0], topn, 0,
+                _ptr(items_d[b0:]), _ptr(scores_d[b0:]) if scores_d is not None else None, None, *ws))
         if out_scores is not None:
-            out_scores[:] = scores_d.cpu().numpy()
+            out_scores[:] = scores
 
     # ------------------------------------------------------------------ a14: similar_items, similar_users
     def similar_items(self, items, topn=10, metric='cosine', exclude_self=True, return_scores=False):
@@ -364,11 +367,8 @@ class WMF(RecModel):
             raise AttributeError("the model has no user factors yet: train it, or assign users, before asking for neighbours")
         n_rows = getattr(self, side).shape[0]
         one = np.ndim(ids) == 0
-        q = np.atleast_1d(np.asarray(ids)).reshape(-1).astype(np.int64)
-        if len(q) and (q.min() < -n_rows or q.max() >= n_rows):
-            raise IndexError(f"{side[:-1]} index out of bounds")
+        q = _wrapped_ids(np.atleast_1d(np.asarray(ids)).reshape(-1).astype(np.int64), n_rows, side[:-1], np.int64)
         _lib.require_gpu()
-        q = np.where(q < 0, q + n_rows, q)
         out_rows = np.full((len(q), topn), -1, dtype=np.int64)
         out_scores = np.full((len(q), topn), -np.inf, dtype=np.float32)
         if len(q):
@@ -378,7 +378,7 @@ class WMF(RecModel):
         return (out_rows, out_scores) if return_scores else out_rows
 
     def _similar_fused(self, side, q, topn, cosine, exclude_self, out_rows, out_scores):
-        """Batches of RECOMMEND_BATCH_USERS queries, all enqueued on one stream; one copy to the host at the end."""
+        """wmf_similar_topn in batches (_scan_batches): the rows ``q`` of ``side`` against all of its rows."""
         if cosine:
             users_t, items_t, f, ld, norms = self._device_inv_norms(side)
         else:
@@ -386,22 +386,16 @@ class WMF(RecModel):
             norms = None
         mat = users_t if side == "users" else items_t
         lib = _lib.load()
-        n = len(q)
-        qt = torch.from_numpy(q.astype(np.int32)).cuda()
-        rows_d = torch.empty(n, topn, dtype=torch.int32, device="cuda")
-        scores_d = torch.empty(n, topn, dtype=torch.float32, device="cuda") if out_scores is not None else None
-        per = max(1, int(RECOMMEND_BATCH_USERS))
-        ws_bytes = int(lib.wmf_similar_workspace_bytes(min(per, n), topn, 0))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
-        for b0 in range(0, n, per):
-            nb = min(per, n - b0)
-            _lib.check(lib.wmf_similar_topn(
+        rows_d = torch.empty(len(q), topn, dtype=torch.int32, device="cuda")
+        scores_d = torch.empty(len(q), topn, dtype=torch.float32, device="cuda") if out_scores is not None else None
+        out_rows[:], scores = self._scan_batches(
+            q, [], lambda rows: lib.wmf_similar_workspace_bytes(rows, topn, 0), [rows_d, scores_d],
+            lambda b0, nb, ids, csrs, *ws: lib.wmf_similar_topn(
                 _ptr(mat), _ptr(mat), f, ld, int(self.bias is True), _ptr(norms) if cosine else None, _ptr(norms) if cosine else None,
-                _ptr(qt[b0:]), nb, mat.shape[0], int(exclude_self), None, None, topn, 0,
-                _ptr(rows_d[b0:]), _ptr(scores_d[b0:]) if scores_d is not None else None, None, _ptr(ws), ws_bytes, _stream()))
-        out_rows[:] = rows_d.cpu().numpy()
+                ids, nb, mat.shape[0], int(exclude_self), None, None, topn, 0,
+                _ptr(rows_d[b0:]), _ptr(scores_d[b0:]) if scores_d is not None else None, None, *ws))
         if out_scores is not None:
-            out_scores[:] = scores_d.cpu().numpy()
+            out_scores[:] = scores
 
     # ------------------------------------------------------------------ a12: rank_positions
     def rank_positions(self, test_mat, exclude=None, users=None, return_scores=False):
@@ -434,30 +428,18 @@ class WMF(RecModel):
         return (indptr, indices, ranks, scores) if return_scores else (indptr, indices, ranks)
 
     def _rank_positions_fused(self, u, target_indptr, target_indices, seen, want_scores):
-        """Batches of RECOMMEND_BATCH_USERS rows, all enqueued on one stream; one copy to the host at the end."""
+        """wmf_rank_positions in batches (_scan_batches); returns [ranks, scores or None] aligned with ``target_indices``."""
         users_t, items_t, f, ld = self._device_factors()
         lib = _lib.load()
-        n, n_items = len(u), self.items.shape[0]
-        ut = torch.from_numpy(u.astype(np.int32)).cuda()
-        tptr_d = torch.from_numpy(target_indptr).cuda()
-        tidx_d = torch.from_numpy(np.append(target_indices, 0).astype(np.int32)).cuda()       # (one spare: never empty)
         rank_d = torch.empty(len(target_indices), dtype=torch.int32, device="cuda")
         score_d = torch.empty(len(target_indices), dtype=torch.float32, device="cuda") if want_scores else None
-        if seen is not None:
-            sptr_d = torch.from_numpy(seen.indptr.astype(np.int64)).cuda()
-            sidx_d = torch.from_numpy(np.append(seen.indices, 0).astype(np.int32)).cuda()
-        per = max(1, int(RECOMMEND_BATCH_USERS))
-        ws_bytes = int(lib.wmf_rank_positions_workspace_bytes(min(per, n), len(target_indices), 0))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
-        for b0 in range(0, n, per):
-            nb = min(per, n - b0)
-            # row b of the batch = row b0 + b: windows of the pointers, which index the whole index and output arrays
-            _lib.check(lib.wmf_rank_positions(
-                _ptr(users_t), _ptr(items_t), f, ld, int(self.bias is True), _ptr(ut[b0:]), nb, n_items,
-                _ptr(sptr_d[b0: b0 + nb + 1]) if seen is not None else None, _ptr(sidx_d) if seen is not None else None,
-                _ptr(tptr_d[b0: b0 + nb + 1]), _ptr(tidx_d), 0, _ptr(rank_d), _ptr(score_d) if want_scores else None,
-                _ptr(ws), ws_bytes, _stream()))
-        return rank_d.cpu().numpy(), (score_d.cpu().numpy() if want_scores else None)
+        # (the pointers index the whole output arrays, as they do the index arrays)
+        return self._scan_batches(
+            u, [None if seen is None else (seen.indptr, seen.indices), (target_indptr, target_indices)],
+            lambda rows: lib.wmf_rank_positions_workspace_bytes(rows, len(target_indices), 0), [rank_d, score_d],
+            lambda b0, nb, ids, csrs, *ws: lib.wmf_rank_positions(
+                _ptr(users_t), _ptr(items_t), f, ld, int(self.bias is True), ids, nb, self.items.shape[0], *csrs[0], *csrs[1], 0,
+                _ptr(rank_d), _ptr(score_d) if want_scores else None, *ws))
 
     def _rank_positions(self, test_mat, exclude, users):
         """eval_ranking's exact ranks from the device: rank_positions."""

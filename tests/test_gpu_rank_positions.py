@@ -8,10 +8,6 @@ ties, and ROUNDED, standard normal, held by two derived conditions and no tolera
 wmf_recommend_topn on the same device buffers, and the interval the float64 scores and their bound B(u, i) leave for the rank.
 Shapes are the smallest at which the kernels can go wrong: row counts around the 16 users of a wave, catalogue lengths around the
 16-item tile and the stage, every slice count from one to more slices than tiles, target counts around the per-row limit."""
-import functools
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
@@ -19,70 +15,17 @@ import torch
 import rankpos_ref as pref
 import recommend_ref as rref
 import serving_ref as ref
-from conftest import ROOT
+from scan_cases import N_ITEMS, N_PATTERNS, N_USERS, _api, _constant, _dev, _host, _ld, _scores, _seen_rows, _user_list, case
 
 pytestmark = pytest.mark.gpu
 
-WIDTHS = (1, 4, 5, 16, 63, 64, 65, 100, 128, 129, 144, 192, 193, 256, 257, 260)
-LD_EXTRA = {5: 4, 64: 4, 100: 8, 129: 4, 257: 4, 260: 12}
-CASES = [(f, b, 0) for f in WIDTHS for b in (0, 1) if f >= 2 or not b] + [(f, b, e) for f, e in LD_EXTRA.items() for b in (0, 1)]
-case = pytest.mark.parametrize("f,bias,extra", CASES, ids=[f"f{f}-b{b}" + (f"-ld+{e}" if e else "") for f, b, e in CASES])
-N_USERS, N_ITEMS = 40, 300
 GRID_ROWS, GRID_ITEMS, GRID_SLICES = (1, 15, 16, 17, 33, 40), (1, 15, 16, 17, 255, 256, 257, 300), (0, 1, 2, 3, 7, 64)
 RANK_SENTINEL, SCORE_SENTINEL = -777, -12345.0
 LEAD, TAIL = 3, 5                                                  # untouched entries before the first and after the last target
-N_PATTERNS = 8
+MAX_T = _constant("WMF_RANKPOS_MAX_TARGETS", "include/wmf_hip.h")
 
 
 # ------------------------------------------------------------------------------------------------------------------ helpers
-def _api():
-    from recmodel_amd import _lib
-    from recmodel_amd.engine import _ptr, _stream
-    return _lib, _lib.load(), _ptr, _stream
-
-
-def _dev(a, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
-
-
-def _ld(f, extra=0):
-    ld = _api()[1].wmf_ld_for(f) + extra
-    assert ld % 4 == 0 and f <= ld <= 272
-    return ld
-
-
-def _constant(name, path=("recmodel_amd", "csrc", "wmf_rankpos.hip")):
-    text = open(os.path.join(ROOT, *path)).read()
-    return int(re.search(rf"#define\s+{name}\s+\(?(-?\d+)\)?", text).group(1))
-
-
-MAX_T = _constant("WMF_RANKPOS_MAX_TARGETS", ("include", "wmf_hip.h"))
-
-
-@functools.lru_cache(maxsize=None)
-def _host(f, cls):
-    make = ref.exact_factors if cls == "exact" else ref.rounded_factors
-    Uf, If = make(N_USERS, f, 10 * f + 1), make(N_ITEMS, f, 10 * f + 2)
-    Uf.setflags(write=False)
-    If.setflags(write=False)
-    return Uf, If
-
-
-@functools.lru_cache(maxsize=None)
-def _scores(f, bias, cls):
-    """Reference scores of every (user, item): int64 (EXACT) or float64 with its bound (ROUNDED).  Computed once, never written."""
-    Uf, If = _host(f, cls)
-    if cls == "exact":
-        out = (ref.score_matrix_int(Uf, If, np.arange(N_USERS), np.arange(N_ITEMS), bias), None)
-    else:
-        uu, ii = np.repeat(np.arange(N_USERS), N_ITEMS), np.tile(np.arange(N_ITEMS), N_USERS)
-        out = (ref.scores_f64(Uf, If, uu, ii, bias).reshape(N_USERS, N_ITEMS), ref.score_bound(Uf, If, uu, ii, bias).reshape(N_USERS, N_ITEMS))
-    for a in out:
-        if a is not None:
-            a.setflags(write=False)
-    return out
-
-
 class _Device:
     """wmf_rank_positions and wmf_recommend_topn on prefixes of one user list and of one item matrix, on the same device buffers."""
 
@@ -129,41 +72,6 @@ class _Device:
         _lib.check(lib.wmf_recommend_topn(_ptr(self.Ud), _ptr(self.Id), f, ld, bias, _ptr(self.user_idx), n_rows, n_items, _ptr(ip_d),
                                           _ptr(idx_d), topn, n_slices, _ptr(items), _ptr(sc), None, _ptr(ws), ws.numel(), _stream()))
         return items.cpu().numpy(), sc.cpu().numpy()
-
-
-def _user_list(n=N_USERS):
-    users = np.arange(n) % N_USERS
-    if n > 9:
-        users[9] = users[2]                                         # one user in two rows, with different seen rows (patterns 2 and 1)
-    return users
-
-
-def _seen_rows(rng, user_scores, n_items, shift):
-    """The seen rows of tests/test_gpu_recommend.py, one per batch position, every pattern in turn: 0 nothing, 1 everything, 2 all
-    but three, 3 one whole 16-item tile, 4 exactly the 50 best-scoring items, 5 duplicated ids, 6 the last item (and a few more),
-    7 a random subset.  Ascending."""
-    rows, everything = [], np.arange(n_items)
-    for b, s in enumerate(user_scores):
-        p = (b + shift) % N_PATTERNS
-        if p == 0:
-            row = everything[:0]
-        elif p == 1:
-            row = everything
-        elif p == 2:
-            row = np.delete(everything, rng.choice(n_items, min(3, n_items), replace=False))
-        elif p == 3:
-            t = int(rng.integers(0, (n_items + 15) // 16))
-            row = everything[16 * t: 16 * t + 16]
-        elif p == 4:
-            row = np.sort(ref.stable_topn(s[:n_items], min(50, n_items)))
-        elif p == 5:
-            row = np.sort(np.repeat(rng.integers(0, n_items, 9), rng.integers(1, 4, 9)))
-        elif p == 6:
-            row = np.unique(np.append(rng.integers(0, n_items, 4), n_items - 1))
-        else:
-            row = np.flatnonzero(rng.random(n_items) < 0.3)
-        rows.append(row.astype(np.int64))
-    return rows
 
 
 def _target_rows(rng, user_scores, seen, n_items, kinds):
@@ -324,8 +232,8 @@ def test_rank_positions_beyond_the_scan_grid_cap():
     """More (user block, slice) pairs than workgroups of the scan, and more rows than the per-row kernels take in one trip: 17
     blocks of 64 rows x the largest slice count; the last block's only row is counted by the second trip."""
     f, bias = 5, 1
-    n_slices = _constant("WMF_RECOMMEND_MAX_SLICES", ("include", "wmf_hip.h"))
-    cap = _constant("WMF_SCAN_GRID", ("recmodel_amd", "csrc", "wmf_scan.h"))
+    n_slices = _constant("WMF_RECOMMEND_MAX_SLICES", "include/wmf_hip.h")
+    cap = _constant("WMF_SCAN_GRID", "recmodel_amd/csrc/wmf_scan.h")
     n_rows = 64 * (cap // n_slices) + 1
     assert ((n_rows + 63) // 64) * n_slices > cap >= (n_rows // 64) * n_slices
     ld = _ld(f)
@@ -344,7 +252,7 @@ def test_rank_positions_beyond_the_scan_grid_cap():
 def test_rank_positions_beyond_the_row_grid_cap():
     """More rows than the target and finish kernels' workgroups take in one trip (four each)."""
     f, bias = 5, 1
-    n_rows = 4 * _constant("WMF_RANKPOS_ROW_GRID") + 37
+    n_rows = 4 * _constant("WMF_RANKPOS_ROW_GRID", "recmodel_amd/csrc/wmf_rankpos.hip") + 37
     ld = _ld(f)
     M, _ = _scores(f, bias, "exact")
     users = np.arange(n_rows) % N_USERS

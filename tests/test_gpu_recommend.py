@@ -7,76 +7,22 @@ The vocabulary of tests/test_gpu_serving.py: the same widths, bias settings and 
 real ties, and ROUNDED, standard normal, held to the derived bound B(u, i).  Shapes are the smallest at which the kernel can go
 wrong: user counts around the 16 users of a wave, catalogue lengths around the 16-item tile and the stage, every slice count from
 one to more slices than tiles, topn from 1 to the maximum and beyond the catalogue.  The result may not depend on the slices."""
-import functools
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
 
 import recommend_ref as rref
 import serving_ref as ref
-from conftest import ROOT, record_error
+from conftest import record_error
+from scan_cases import N_ITEMS, N_PATTERNS, N_USERS, _api, _check_rounded_order, _constant, _dev, _host, _ld, _scores, _seen_rows, _user_list, case
 
 pytestmark = pytest.mark.gpu
 
-WIDTHS = (1, 4, 5, 16, 63, 64, 65, 100, 128, 129, 144, 192, 193, 256, 257, 260)
-LD_EXTRA = {5: 4, 64: 4, 100: 8, 129: 4, 257: 4, 260: 12}
-CASES = [(f, b, 0) for f in WIDTHS for b in (0, 1) if f >= 2 or not b] + [(f, b, e) for f, e in LD_EXTRA.items() for b in (0, 1)]
-case = pytest.mark.parametrize("f,bias,extra", CASES, ids=[f"f{f}-b{b}" + (f"-ld+{e}" if e else "") for f, b, e in CASES])
-N_USERS, N_ITEMS = 40, 300
 GRID_USERS, GRID_ITEMS, GRID_TOPN, GRID_SLICES = (1, 15, 16, 17, 33, 40), (1, 15, 16, 17, 255, 256, 257, 300), (1, 2, 10, 64, 128), (0, 1, 2, 3, 7, 64)
 SENTINEL = -12345.0
-N_PATTERNS = 8
 
 
 # ------------------------------------------------------------------------------------------------------------------ helpers
-def _api():
-    from recmodel_amd import _lib
-    from recmodel_amd.engine import _ptr, _stream
-    return _lib, _lib.load(), _ptr, _stream
-
-
-def _dev(a, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
-
-
-def _ld(f, extra=0):
-    ld = _api()[1].wmf_ld_for(f) + extra
-    assert ld % 4 == 0 and f <= ld <= 272
-    return ld
-
-
-def _launcher_constant(name, source="wmf_recommend.hip"):
-    text = open(os.path.join(ROOT, "recmodel_amd", "csrc", source)).read()
-    return int(re.search(rf"#define\s+{name}\s+(\d+)", text).group(1))
-
-
-@functools.lru_cache(maxsize=None)
-def _host(f, cls):
-    make = ref.exact_factors if cls == "exact" else ref.rounded_factors
-    Uf, If = make(N_USERS, f, 10 * f + 1), make(N_ITEMS, f, 10 * f + 2)
-    Uf.setflags(write=False)
-    If.setflags(write=False)
-    return Uf, If
-
-
-@functools.lru_cache(maxsize=None)
-def _scores(f, bias, cls):
-    """Reference scores of every (user, item): int64 (EXACT) or float64 with its bound (ROUNDED).  Computed once, never written."""
-    Uf, If = _host(f, cls)
-    if cls == "exact":
-        out = (ref.score_matrix_int(Uf, If, np.arange(N_USERS), np.arange(N_ITEMS), bias), None)
-    else:
-        uu, ii = np.repeat(np.arange(N_USERS), N_ITEMS), np.tile(np.arange(N_ITEMS), N_USERS)
-        out = (ref.scores_f64(Uf, If, uu, ii, bias).reshape(N_USERS, N_ITEMS), ref.score_bound(Uf, If, uu, ii, bias).reshape(N_USERS, N_ITEMS))
-    for a in out:
-        if a is not None:
-            a.setflags(write=False)
-    return out
-
-
 class _Recommend:
     """wmf_recommend_topn on prefixes of one user list and of one item matrix."""
 
@@ -99,52 +45,6 @@ class _Recommend:
         _lib.check(lib.wmf_recommend_topn(_ptr(self.Ud), _ptr(self.Id), f, ld, bias, _ptr(self.user_idx), n_users, n_items, _ptr(ip_d),
                                           _ptr(idx_d), topn, n_slices, _ptr(items), _ptr(sc), _ptr(cnt), _ptr(ws), ws.numel(), _stream()))
         return items.cpu().numpy(), (sc.cpu().numpy() if scores else None), (cnt.cpu().numpy() if count else None)
-
-
-def _user_list(n=N_USERS):
-    users = np.arange(n) % N_USERS
-    if n > 9:
-        users[9] = users[2]                                         # one user twice, with different seen rows (patterns 2 and 1)
-    return users
-
-
-def _seen_rows(rng, user_scores, n_items, shift):
-    """One seen row per batch position, every pattern in turn: 0 nothing, 1 everything, 2 all but three, 3 one whole 16-item tile,
-    4 exactly the 50 best-scoring items, 5 duplicated ids, 6 the last item (and a few more), 7 a random subset.  Ascending."""
-    rows, everything = [], np.arange(n_items)
-    for b, s in enumerate(user_scores):
-        p = (b + shift) % N_PATTERNS
-        if p == 0:
-            row = everything[:0]
-        elif p == 1:
-            row = everything
-        elif p == 2:
-            row = np.delete(everything, rng.choice(n_items, min(3, n_items), replace=False))
-        elif p == 3:
-            t = int(rng.integers(0, (n_items + 15) // 16))
-            row = everything[16 * t: 16 * t + 16]
-        elif p == 4:
-            row = np.sort(ref.stable_topn(s[:n_items], min(50, n_items)))
-        elif p == 5:
-            row = np.sort(np.repeat(rng.integers(0, n_items, 9), rng.integers(1, 4, 9)))
-        elif p == 6:
-            row = np.unique(np.append(rng.integers(0, n_items, 4), n_items - 1))
-        else:
-            row = np.flatnonzero(rng.random(n_items) < 0.3)
-        rows.append(row.astype(np.int64))
-    return rows
-
-
-def _check_rounded_order(pos, ref_scores, bound, what):
-    """The rule of tests/test_gpu_serving.py: positions are unique and the reference score of the k-th returned candidate is
-    within B of the k-th best reference score (B of whichever of the two has the larger one).  Returns the worst ratio."""
-    assert len(np.unique(pos)) == len(pos) and pos.min() >= 0 and pos.max() < len(ref_scores), what
-    best = ref.stable_topn(ref_scores, len(pos))
-    gap = np.abs(ref_scores[pos] - ref_scores[best])
-    allowed = np.maximum(bound[pos], bound[best])
-    ratio = float((gap / allowed).max())
-    assert ratio <= 1.0, (what, ratio)
-    return ratio
 
 
 def _check_exact(got, M, users, seen, n_items, topn, what):
@@ -328,7 +228,7 @@ def test_recommend_beyond_the_scan_grid_cap():
     the last block's user in the last tile, which the second trip scans."""
     f, bias, topn = 5, 1, 10
     n_slices = 256
-    cap = _launcher_constant("WMF_SCAN_GRID", "wmf_scan.h")
+    cap = _constant("WMF_SCAN_GRID", "recmodel_amd/csrc/wmf_scan.h")
     n_users = 64 * (cap // n_slices) + 1
     assert ((n_users + 63) // 64) * n_slices > cap >= (n_users // 64) * n_slices
     ld = _ld(f)
@@ -351,7 +251,7 @@ def test_recommend_beyond_the_scan_grid_cap():
 def test_recommend_beyond_the_merge_grid_cap():
     """More users than the merge kernel's workgroups take in one trip (four each)."""
     f, bias, topn = 5, 1, 10
-    n_users = 4 * _launcher_constant("WMF_REC_MERGE_GRID") + 37
+    n_users = 4 * _constant("WMF_REC_MERGE_GRID", "recmodel_amd/csrc/wmf_recommend.hip") + 37
     ld = _ld(f)
     M, _ = _scores(f, bias, "exact")
     users = np.arange(n_users) % N_USERS

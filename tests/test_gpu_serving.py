@@ -1,7 +1,7 @@
 """The kernels behind the numbers a user reads -- predict, rank, the MSE of early stopping, Recall@N -- one entry point at a time
 through the C ABI, per element, at every width class (csrc/wmf_eval.hip, csrc/wmf_rank.hip, the tail of csrc/wmf_solve.hip).
 
-pair_score / rank_pair_score walk a row in 16-byte pieces, 16 lanes wide: one trip up to f = 64, five at f = 260; the MFMA tile
+wmf_pair_score (csrc/wmf_common.h) walks a row in 16-byte pieces, 16 lanes wide: one trip up to f = 64, five at f = 260; the MFMA tile
 kernel of the batched rank pads the piece count to a multiple of 4.  WIDTHS has every trip count, every piece count modulo 4
 and every bench width, each with and without the bias column, a handful also with a wider leading dimension.
 
@@ -313,7 +313,7 @@ def test_hit_counts(f, bias, extra):
     one = np.zeros(1, dtype=np.int32)
     assert _hits(Ud, Id, f, ld, bias, one, one, one, one[None, :], one, [1, 2, 3], prefill=-99, n_pairs=0).tolist() == [0, 0, 0]
     # rounded class: the counts the host derives from wmf_predict_pairs scores of the same pairs -- exactly, which holds only
-    # while rank_pair_score (csrc/wmf_rank.hip) and pair_score (csrc/wmf_eval.hip) are the same arithmetic
+    # because hit_kernel (csrc/wmf_rank.hip) and predict_kernel (csrc/wmf_eval.hip) score with the one wmf_pair_score
     Ud, Id = _device(f, ld, "rounded")
     pu, pi, pr, cand, slot = _hit_case(rng, 60, 12, 101)
     s_true = _predict(Ud, Id, f, ld, bias, pu, pi)

@@ -6,8 +6,6 @@ The vocabulary of tests/test_gpu_recommend.py: the same widths, bias settings an
 dots are exact, the two float32 multiplications are repeated in NumPy) and equal scores are real ties, and ROUNDED, standard normal,
 held to the derived bound B_cos(q, j).  A catalogue of 300 rows and 40 queries that are rows of it."""
 import functools
-import os
-import re
 
 import numpy as np
 import pytest
@@ -16,46 +14,21 @@ import torch
 import recommend_ref as rref
 import serving_ref as ref
 import similar_ref as sref
-from conftest import ROOT, record_error
+from conftest import record_error
+from scan_cases import N_PATTERNS, _api, _check_rounded_order, _constant, _dev, _ld, _seen_rows, case
 
 pytestmark = pytest.mark.gpu
 
-WIDTHS = (1, 4, 5, 16, 63, 64, 65, 100, 128, 129, 144, 192, 193, 256, 257, 260)
-LD_EXTRA = {5: 4, 64: 4, 100: 8, 129: 4, 257: 4, 260: 12}
-CASES = [(f, b, 0) for f in WIDTHS for b in (0, 1) if f >= 2 or not b] + [(f, b, e) for f, e in LD_EXTRA.items() for b in (0, 1)]
-case = pytest.mark.parametrize("f,bias,extra", CASES, ids=[f"f{f}-b{b}" + (f"-ld+{e}" if e else "") for f, b, e in CASES])
 N_QUERIES, N_ROWS = 40, 300
 GRID_QUERIES, GRID_ROWS, GRID_TOPN, GRID_SLICES = (1, 15, 16, 17, 33, 40), (1, 15, 16, 17, 255, 256, 257, 300), (1, 2, 10, 64, 128), (0, 1, 2, 3, 7, 64)
 GRID_CASES = ((129, 1), (64, 0))
 SENTINEL = -12345.0
-N_PATTERNS = 8
 # row 0, the last row, the rows around a wave's 16, row 2 twice (batch positions 2 and 9); the rest spread over the catalogue
 QUERIES = np.array([0, N_ROWS - 1, 2, 15, 16, 17, 31, 32, 33, 2] + [(37 * b + 5) % N_ROWS for b in range(10, N_QUERIES)])
 assert len(QUERIES) == N_QUERIES and len(np.unique(QUERIES)) == N_QUERIES - 1
 
 
 # ------------------------------------------------------------------------------------------------------------------ helpers
-def _api():
-    from recmodel_amd import _lib
-    from recmodel_amd.engine import _ptr, _stream
-    return _lib, _lib.load(), _ptr, _stream
-
-
-def _dev(a, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
-
-
-def _ld(f, extra=0):
-    ld = _api()[1].wmf_ld_for(f) + extra
-    assert ld % 4 == 0 and f <= ld <= 272
-    return ld
-
-
-def _launcher_constant(name, source="wmf_similar.hip"):
-    text = open(os.path.join(ROOT, "recmodel_amd", "csrc", source)).read()
-    return int(re.search(rf"#define\s+{name}\s+(\d+)", text).group(1))
-
-
 @functools.lru_cache(maxsize=None)
 def _catalogue(f, cls):
     """The catalogue of a width; in the EXACT class the queries include all-zero rows (inverse norm 0: every cosine ties at 0)."""
@@ -157,46 +130,6 @@ def _check_exact(got, S, query_rows, exclude_self, excl, n_rows, topn, what):
         assert (sc[~valid] == -np.inf).all() and np.array_equal(sc[valid].view(np.uint32), want_sc.view(np.uint32)), what
 
 
-def _excl_rows(rng, scores, n_rows, shift):
-    """One exclusion row per batch position, every pattern of the recommend tests in turn: 0 nothing, 1 everything, 2 all but
-    three, 3 one whole 16-row tile, 4 exactly the 50 best-scoring rows, 5 duplicated ids, 6 the last row (and a few more), 7 a random
-    subset.  Ascending."""
-    rows, everything = [], np.arange(n_rows)
-    for b, s in enumerate(scores):
-        p = (b + shift) % N_PATTERNS
-        if p == 0:
-            row = everything[:0]
-        elif p == 1:
-            row = everything
-        elif p == 2:
-            row = np.delete(everything, rng.choice(n_rows, min(3, n_rows), replace=False))
-        elif p == 3:
-            t = int(rng.integers(0, (n_rows + 15) // 16))
-            row = everything[16 * t: 16 * t + 16]
-        elif p == 4:
-            row = np.sort(ref.stable_topn(s[:n_rows], min(50, n_rows)))
-        elif p == 5:
-            row = np.sort(np.repeat(rng.integers(0, n_rows, 9), rng.integers(1, 4, 9)))
-        elif p == 6:
-            row = np.unique(np.append(rng.integers(0, n_rows, 4), n_rows - 1))
-        else:
-            row = np.flatnonzero(rng.random(n_rows) < 0.3)
-        rows.append(row.astype(np.int64))
-    return rows
-
-
-def _check_rounded_order(pos, ref_scores, bound, what):
-    """The rule of tests/test_gpu_serving.py: positions are unique and the reference score of the k-th returned candidate is
-    within B of the k-th best reference score (B of whichever of the two has the larger one).  Returns the worst ratio."""
-    assert len(np.unique(pos)) == len(pos) and pos.min() >= 0 and pos.max() < len(ref_scores), what
-    best = ref.stable_topn(ref_scores, len(pos))
-    gap = np.abs(ref_scores[pos] - ref_scores[best])
-    allowed = np.maximum(bound[pos], bound[best])
-    ratio = float((gap / allowed).max())
-    assert ratio <= 1.0, (what, ratio)
-    return ratio
-
-
 # -------------------------------------------------------------------------------------------------------- 1. inverse norms
 def _norm_rows(n, f, bias, seed):
     """[n, f]: by row number modulo 8 -- ROUNDED, EXACT, zero, only the bias column, ROUNDED x 2^60, ROUNDED x 2^-60, small float32
@@ -219,7 +152,7 @@ def _norm_rows(n, f, bias, seed):
 def test_row_inv_norms(f, bias, extra):
     _lib, lib, _ptr, _stream = _api()
     ld = _ld(f, extra)
-    cap, per = _launcher_constant("WMF_NORMS_GRID"), _launcher_constant("WMF_NORMS_ROWS")
+    cap, per = (_constant(name, "recmodel_amd/csrc/wmf_similar.hip") for name in ("WMF_NORMS_GRID", "WMF_NORMS_ROWS"))
     n_max = cap * per + 1
     M, kind = _norm_rows(n_max, f, bias, 100 * f + bias)
     P = ref.padded(M, ld)
@@ -320,7 +253,7 @@ def test_similar_topn_exclusion_lists(f, bias):
     sim = _Similar(C, C, f, ld, bias, QUERIES, scales)
     rng = np.random.default_rng(4000 + 2 * f + bias)
     for shift in range(0, N_PATTERNS, 3):
-        base = _excl_rows(rng, S, N_ROWS, shift)
+        base = _seen_rows(rng, S, N_ROWS, shift)                     # (exclusion rows: the seen-row patterns of the recommend tests)
         without = [row[row != q] for row, q in zip(base, QUERIES)]
         with_self = [np.sort(np.append(row, q)) for row, q in zip(without, QUERIES)]
         for excl in (without, with_self):
