@@ -206,7 +206,7 @@ __global__ __launch_bounds__(256) void gram64v2_reduce_kernel(const double* __re
 }
 
 // ---- one row system per TEAM, in registers from the first gathered entry to the solution ---------------------------------
-// TEAM = 256: the whole workgroup works on one row (barriers are __syncthreads).  TEAM = 64 (f <= 68: at most three blocks per
+// TEAM = 256: the whole workgroup works on one row (barriers are __syncthreads).  TEAM = 64 (f <= 72: at most three blocks per
 // lane): every WAVE of the workgroup has its own row and its own slice of LDS, and the steps below are ordered by the wave's
 // lockstep execution (a wave-scope fence instead of a workgroup barrier) -- four rows in flight per workgroup where a narrow
 // system would leave most of 256 threads without a block and every step waiting on a barrier.
@@ -1085,7 +1085,7 @@ int wmf_launch_half_step_f64(const double* Y, int64_t m, int f, int bias, const 
         };
         const bool waves = !(wmf_debug_flags & WMF_DBG_F64_TEAMS);     // WMF_DBG_F64_TEAMS, 67108864 (timing experiments, lab builds): workgroup teams at every width
         if (!waves && nblk <= 256) solve(wmf_int<1>{}, wmf_int<256>{}, wmf_int<16>{});
-        else if (nblk <= 64) solve(wmf_int<1>{}, wmf_int<64>{}, wmf_int<8>{});            // one WAVE per row while a lane holds at most three blocks (f <= 68)
+        else if (nblk <= 64) solve(wmf_int<1>{}, wmf_int<64>{}, wmf_int<8>{});            // one WAVE per row while a lane holds at most three blocks (f <= 72)
         else if (nblk <= 128) solve(wmf_int<2>{}, wmf_int<64>{}, wmf_int<8>{});
         else if (nblk <= 192) solve(wmf_int<3>{}, wmf_int<64>{}, wmf_int<8>{});
         else if (nblk <= 256) solve(wmf_int<1>{}, wmf_int<256>{}, wmf_int<16>{});         // one workgroup per row beyond

@@ -1,12 +1,14 @@
 """Randomised sweep of the float64 half step (wmf_recompute_factors_f64_host: Gramian, low-rank rows, direct rows, LU fallback)
-against the NumPy oracle in float64: random widths (every block count per thread, wave and workgroup teams), biases with and
+against tests/f64_ref.py PER ROW (1e-10; 1e-8 for a row with a weight below zero, on the rows with cond_2 <= 1e6, which must be
+>= 95 % of a case's rows; every output finite; a row without entries is exactly zero): random widths (every block count per thread, wave and workgroup teams), biases with and
 without negative weights, degree laws on both sides of the low-rank switch (a quarter of the rows with 1 .. 32 entries).
 Usage: python tests/scale/fuzz_f64.py [cases] [seed]"""
-import sys, time
+import os, sys, time
 import numpy as np, scipy.sparse as sp
 sys.path.insert(0, '.')
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 from recmodel_amd import WMF
-from oracle import wmf_oracle as orc
+import f64_ref
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
@@ -40,14 +42,18 @@ for case in range(cases):
         Y[:, 0] = np.linspace(-5, 30, m) if neg else 0.5 * Y[:, 0]   # neg: about a third of the weights go negative -> LU rows
     fn = model.recompute_factors_bias_par if bias else model.recompute_factors_par
     got = fn(Y, C, 0.1)
-    want = (orc.recompute_factors_bias if bias else orc.recompute_factors)(Y, C, 0.1, dtype="float64")
-    ok = np.linalg.norm(want, axis=1) < 1e3 if neg else np.ones(n, dtype=bool)
-    err = np.linalg.norm(got[ok] - want[ok]) / max(np.linalg.norm(want[ok]), 1e-30)
-    tol = 1e-8 if neg else 1e-10
-    flag = "" if err <= tol and np.isfinite(got).all() else "   <-- ABOVE TOLERANCE"
-    worst = max(worst, err / tol if np.isfinite(err) else 1e9)
+    ref = f64_ref.half_step(Y, bias, 0.1, C.indptr, C.indices, C.data, want_cond="neg")
+    err = f64_ref.row_errors(got, ref["x"])
+    tame = ~(ref["cond"] > 1e6)                                     # (nan -- no weight below zero -- counts as tame)
+    gate = np.where(ref["neg"], 1e-8, 1e-10)
+    ratio = float((err[tame] / gate[tame]).max()) if tame.any() else 0.0
+    share = float(tame.mean())
+    good = ratio <= 1.0 and share >= 0.95 and np.isfinite(got).all()
+    flag = "" if good else "   <-- ABOVE TOLERANCE"
+    worst = max(worst, ratio if good or (np.isfinite(ratio) and ratio > 1.0) else 1e9)
     empty = np.diff(C.indptr) == 0
     assert not got[empty].any(), "rows without entries must be exactly zero"
-    print(f"case {case:3d}: f={f:3d} bias={int(bias)} neg={int(neg)} n={n:3d} m={m:4d} law={law:6s} nnz={C.nnz:6d} rel.err {err:.2e}{flag}")
-print(f"{cases} cases in {time.perf_counter() - t0:.1f} s; worst error / tolerance = {worst:.2f}")
+    print(f"case {case:3d}: f={f:3d} bias={int(bias)} neg={int(neg)} n={n:3d} m={m:4d} law={law:6s} nnz={C.nnz:6d} worst row / gate {ratio:.2e}"
+          f" (row {int(np.argmax(np.where(tame, err / gate, 0)))}, {share:.0%} rows gated){flag}")
+print(f"{cases} cases in {time.perf_counter() - t0:.1f} s; worst row error / gate = {worst:.2f}")
 sys.exit(0 if worst <= 1.0 else 1)
