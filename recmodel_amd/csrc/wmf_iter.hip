@@ -707,8 +707,10 @@ __global__ __launch_bounds__(64 * NW, OCC) void solve_iter_kernel(const int32_t*
 // ---- host side ----------------------------------------------------------------------------------------------------
 // Geometry per width: waves per row NW, features per lane FPL (16 FPL floats of a gathered row), slots NS (a workgroup holds
 // 4 NW NS entries), waves per SIMD OCC.  The split layout's extra registers (border value, pair) cost a slot or a workgroup.
-//   ldv <=  64: 4 waves, FPL  4, 16 slots (256 entries), 3 workgroups per CU;  split: 12 slots (192 entries)
-//   ldv <= 128: 4 waves, FPL  8,  9 slots (144 entries), 3 workgroups per CU;  split:  8 slots (128 entries)   (k = 128 +- biases)
+//   ldv <=  64: 4 waves, FPL  4, 16 slots (256 entries), 2 workgroups per CU, split or not      (lab builds only: WMF_ITER_MIN_LDV)
+//   ldv <  128: 4 waves, FPL  8,  9 slots (144 entries), 3 workgroups per CU;  split:  9 slots too, 2 workgroups per CU
+//   ldv  = 128: 2 waves, FPL  8, 16 slots (128 entries), 4 workgroups per CU, Neumann series only, then over what it hands on
+//               4 waves, FPL  8,  8 slots (128 entries), 2 workgroups per CU, the LDS-DMA ring                 (k = 128 +- biases)
 //   ldv <= 192: 8 waves, FPL 12,  8 slots (256 entries), 1 workgroup per CU
 //   ldv <= 256: 8 waves, FPL 16,  8 slots (256 entries), 1 workgroup per CU                                     (k = 256)
 //   ldv <= 320: 8 waves, FPL 20,  6 slots (192 entries), 1 workgroup per CU                                     (f up to 272)
