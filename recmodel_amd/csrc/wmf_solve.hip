@@ -26,16 +26,20 @@ __device__ __forceinline__ float readlane_f(float v, int lane) {
 // One Gauss-Jordan step on pivot K (compile time, so register indices and the DPP control are
 // static).  Row j is spread over the 4 lanes (r, q = 0..3); column K lives in lanes q = (K & 15) >> 2,
 // register (K >> 4) * 4 + (K & 3).
+// The pivot row is NOT normalised inside the sweep (as gj_inv_step, wmf_common.h): it stays at piv_K times its final value -- the
+// later steps are linear in the row, so the factor rides along --, the lanes of row K remember 1 / piv in dsc, and the caller
+// multiplies p by dsc once at the end.  The in-place form  row_K += ((1 - piv) / piv) row_K  rounds its multiplier at 2^-24 of
+// ONE, not of 1 / piv: a relative error of 6e-8 piv in the row and in c_K -- 1e-2 and more at w |v|^2 ~ 1e5, a few ulp already at
+// the pivots of 10 .. 30 of ordinary rows (tests/test_gpu_low_rows.py).
 template <int K, int NSETS>
-__device__ __forceinline__ void gj_step(float (&m)[NSETS][NSETS * 4], float (&p)[NSETS], const int (&baddr)[4], int r) {
+__device__ __forceinline__ void gj_step(float (&m)[NSETS][NSETS * 4], float (&p)[NSETS], float (&dsc)[NSETS], const int (&baddr)[4], int r) {
     constexpr int ks = K >> 4, kk = K & 15, kq = kk >> 2, kreg = ks * 4 + (kk & 3);
     const float piv = readlane_f(m[ks][kreg], kk + 16 * kq);
     const float inv = __builtin_amdgcn_rcpf(piv);
     const float pkv = readlane_f(p[ks], kk);
     // multiplier -M[j][K] / piv per row (M[j][K] sits in lane (r, kq): one ds_bpermute with a precomputed
-    // address); for the pivot row itself -(piv - 1) / piv, which turns row - f * row into row / piv (the
-    // normalised pivot row) without a select per element.  The other set goes first: it must read the
-    // pivot row before that row is rewritten.
+    // address); for the pivot row itself 0 (see above).  The other set goes first, as it did when the
+    // pivot row was rewritten in its step.
     if constexpr (NSETS == 2) {
         constexpr int so = 1 - ks;
         const float fo = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(baddr[kq], __builtin_bit_cast(int, m[so][kreg])));
@@ -48,12 +52,13 @@ __device__ __forceinline__ void gj_step(float (&m)[NSETS][NSETS * 4], float (&p)
     }
     {
         const float fk = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(baddr[kq], __builtin_bit_cast(int, m[ks][kreg])));
-        // nf = (e_K - f) / piv with e_K = [r == kk] as a constant lane mask shifted into place next to its use (three
-        // instructions where  r == kk ? piv - 1 : f  and the product take four; see gj_inv_step_lean, wmf_common.h)
+        // nf = (e_K f - f) / piv with e_K = [r == kk] as a constant lane mask shifted into place next to its use: 0 in the pivot
+        // row, -f / piv elsewhere; the same mask latches 1 / piv into dsc on the pivot row's lanes (gj_inv_step_lean, wmf_common.h)
         float eK;
         unsigned long long tmp;
-        asm volatile("s_lshl_b64 %1, %2, %3\n\tv_cndmask_b32 %0, 0, 1.0, %1" : "=v"(eK), "=&s"(tmp) : "s"(0x0001000100010001ull), "n"(kk) : "scc");
-        const float nf = (eK - fk) * inv;
+        asm volatile("s_lshl_b64 %1, %3, %4\n\tv_cndmask_b32 %0, 0, 1.0, %1\n\tv_cndmask_b32 %2, %2, %5, %1"
+                     : "=&v"(eK), "=&s"(tmp), "+v"(dsc[ks]) : "s"(0x0001000100010001ull), "n"(kk), "v"(inv) : "scc");
+        const float nf = __builtin_fmaf(eK, fk, -fk) * inv;
 #pragma unroll
         for (int c4 = 0; c4 < NSETS; ++c4)
             fmac_bcast4_self<kk>(m[ks][4 * c4], m[ks][4 * c4 + 1], m[ks][4 * c4 + 2], m[ks][4 * c4 + 3], nf);
@@ -64,19 +69,24 @@ __device__ __forceinline__ void gj_step(float (&m)[NSETS][NSETS * 4], float (&p)
 // Steps run in groups of four under one scalar branch.  A step past the row's last entry is a no-op
 // (its pivot row is an identity row, its column is zero everywhere else), so at most three are wasted.
 template <int G, int NSETS>
-__device__ __forceinline__ void gj_group(float (&m)[NSETS][NSETS * 4], float (&p)[NSETS], int d, const int (&baddr)[4],
-                                         int r) {
+__device__ __forceinline__ void gj_group(float (&m)[NSETS][NSETS * 4], float (&p)[NSETS], float (&dsc)[NSETS], int d,
+                                         const int (&baddr)[4], int r) {
     if (4 * G < d) {                                // d is wave-uniform (SGPR)
-        gj_step<4 * G, NSETS>(m, p, baddr, r);
-        gj_step<4 * G + 1, NSETS>(m, p, baddr, r);
-        gj_step<4 * G + 2, NSETS>(m, p, baddr, r);
-        gj_step<4 * G + 3, NSETS>(m, p, baddr, r);
+        gj_step<4 * G, NSETS>(m, p, dsc, baddr, r);
+        gj_step<4 * G + 1, NSETS>(m, p, dsc, baddr, r);
+        gj_step<4 * G + 2, NSETS>(m, p, dsc, baddr, r);
+        gj_step<4 * G + 3, NSETS>(m, p, dsc, baddr, r);
     }
 }
 template <int NSETS, int... Gs>
 __device__ __forceinline__ void gj_sweep(float (&m)[NSETS][NSETS * 4], float (&p)[NSETS], int d, const int (&baddr)[4],
                                          int r, std::integer_sequence<int, Gs...>) {
-    (gj_group<Gs, NSETS>(m, p, d, baddr, r), ...);
+    float dsc[NSETS];
+#pragma unroll
+    for (int s = 0; s < NSETS; ++s) dsc[s] = 1.f;
+    (gj_group<Gs, NSETS>(m, p, dsc, d, baddr, r), ...);
+#pragma unroll
+    for (int s = 0; s < NSETS; ++s) p[s] *= dsc[s];   // (a row no step took as its pivot row is an identity row: 1)
 }
 
 // ------------------------------------------------------------------------------ low-degree rows
@@ -518,10 +528,12 @@ __global__ __launch_bounds__(256, NCH <= 9 ? 6 : 1) void solve_pair_kernel(const
     float m[1][4];
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) m[0][reg] = w[0] * keep * (a0[reg] + a1[reg]) + ((r == 4 * q + reg) ? 1.f : 0.f);
-    if (0 < dA) { gj_step<0, 1>(m, p, baddr, r); gj_step<1, 1>(m, p, baddr, r); gj_step<2, 1>(m, p, baddr, r); gj_step<3, 1>(m, p, baddr, r); }
-    if (4 < dA) { gj_step<4, 1>(m, p, baddr, r); gj_step<5, 1>(m, p, baddr, r); gj_step<6, 1>(m, p, baddr, r); gj_step<7, 1>(m, p, baddr, r); }
-    if (0 < dB) { gj_step<8, 1>(m, p, baddr, r); gj_step<9, 1>(m, p, baddr, r); gj_step<10, 1>(m, p, baddr, r); gj_step<11, 1>(m, p, baddr, r); }
-    if (4 < dB) { gj_step<12, 1>(m, p, baddr, r); gj_step<13, 1>(m, p, baddr, r); gj_step<14, 1>(m, p, baddr, r); gj_step<15, 1>(m, p, baddr, r); }
+    float dsc[1] = {1.f};                            // 1 / piv of this lane's row (gj_step: the sweep leaves pivot rows un-normalised)
+    if (0 < dA) { gj_step<0, 1>(m, p, dsc, baddr, r); gj_step<1, 1>(m, p, dsc, baddr, r); gj_step<2, 1>(m, p, dsc, baddr, r); gj_step<3, 1>(m, p, dsc, baddr, r); }
+    if (4 < dA) { gj_step<4, 1>(m, p, dsc, baddr, r); gj_step<5, 1>(m, p, dsc, baddr, r); gj_step<6, 1>(m, p, dsc, baddr, r); gj_step<7, 1>(m, p, dsc, baddr, r); }
+    if (0 < dB) { gj_step<8, 1>(m, p, dsc, baddr, r); gj_step<9, 1>(m, p, dsc, baddr, r); gj_step<10, 1>(m, p, dsc, baddr, r); gj_step<11, 1>(m, p, dsc, baddr, r); }
+    if (4 < dB) { gj_step<12, 1>(m, p, dsc, baddr, r); gj_step<13, 1>(m, p, dsc, baddr, r); gj_step<14, 1>(m, p, dsc, baddr, r); gj_step<15, 1>(m, p, dsc, baddr, r); }
+    p[0] *= dsc[0];
     if (__any(!(fabsf(p[0]) < 3.0e38f))) { bounce(); return; }
 
     // ---- g = V_u^T c per row: sums over the 8 lanes of a half, lanes r = 0 and r = 8 store
