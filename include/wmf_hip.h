@@ -114,6 +114,31 @@ int wmf_row_transform(const float* in, int64_t m, int f, int ld, const float* W,
  * ld, or f - 1 for the split layout above (0: f, ld not supported). */
 int wmf_whitened_row_floats(int f, int ld, int bias);
 
+/* ---- CHAINED WHITENING of a side that was just solved (f = 97 .. 144) ----
+ * The factors X = g . U (U = the W_unwhite that un-whitens g) are an exact linear image of g, so the Gramian and the whitened
+ * rows the NEXT half step needs of this side follow from g and two small matrices, without X being written or read.  With
+ * a = [g, 1] (bias != 0; the one at position f of a row, which ld >= f + 1 has room for) or a = g, and T the (f + bias) x f
+ * matrix with rows 0 .. f - 1 = U, column 0 zeroed, and row f = e0^T (T = U without biases):
+ *     in~ = a . T,   G~ = T^T (a^T a) T = wmf_gram(X, bias),   V = a . (T . W_white),   bias = g . U[:, 0].
+ * All three calls take a workspace of wmf_gram_workspace_bytes(f + 1).  g's padding columns are not read as data.
+ * wmf_chained_supported: non-zero where the three are implemented -- f = 97 .. 144 with f + bias <= 144 and ld >= f + bias. */
+int wmf_chained_supported(int f, int ld, int bias);
+/* G_aug[(f + bias)^2] (fp64, row-major) = a^T a over the m rows of g (g in rolled coordinates or not: positions). */
+int wmf_gram_whitened(const float* g, int64_t m, int f, int ld, int bias,
+                      double* G_aug, void* workspace, void* stream);
+/* On the device, fp64, no host synchronisation: G~ = T^T G_aug T, then wmf_factorize(G~, lambda) -> W_white, W_unwhite, info
+ * (its semantics and rounding), then N_ext [(f + bias), ld] fp32 = [T . W_white | U[:, 0]] (column f: the bias; padding zero).
+ * rolled != 0 (wmf_rolled_layout_supported): g came from wmf_solve_rows_ex(WMF_SOLVE_ROLLED) and the whitened side is wanted
+ * in rolled coordinates -- row p of N_ext belongs to position p of g, column n to position n of the whitened row.
+ * U [f, ld] may not alias W_white / W_unwhite. */
+int wmf_compose_whitening(const double* G_aug, const float* U, int f, int ld, int bias, int rolled, double lambda,
+                          float* W_white, float* W_unwhite, float* N_ext, int32_t* info,
+                          void* workspace, void* stream);
+/* out / col0_out = a . N_ext in exactly the layout wmf_row_transform(X, W_white, set_col0_one = bias, or 3 when rolled)
+ * writes: plain rows and the bias vector, the split layout, or the rolled split layout with the bias bits in the body. */
+int wmf_row_transform_chained(const float* g, int64_t m, int f, int ld, int bias, const float* N_ext, int rolled,
+                              float* out, float* col0_out, void* stream);
+
 /* Degree-binned schedule for the rows of one CSR matrix (built once per matrix, host indptr).  Allocates (and
  * synchronously fills) the plan's device memory, including everything wmf_solve_rows will need: the row lists, the
  * segment table of rows with more than 4096 entries, with bias != 0 the bias-adjusted weights (one float per stored

@@ -253,6 +253,62 @@ int wmf_row_transform(const float* in, int64_t m, int f, int ld, const float* W,
     return check_launch("wmf_row_transform");
 }
 
+// ---- chained whitening: the workspace is wmf_gram_workspace_bytes(f + 1), laid out for f + 1 columns ----
+int wmf_chained_supported(int f, int ld, int bias) {
+    if (check_shape(f, ld)) return 0;
+    const int f1 = f + (bias ? 1 : 0);
+    return (f >= 97 && f1 <= 144 && ld >= f1 && f + 1 <= WMF_MAX_F) ? 1 : 0;
+}
+static int check_chained(const char* what, int f, int ld, int bias) {
+    if (wmf_chained_supported(f, ld, bias)) return WMF_OK;
+    wmf_set_error("%s: unsupported f=%d, ld=%d, bias=%d (wmf_chained_supported)", what, f, ld, bias);
+    return WMF_EINVAL;
+}
+
+int wmf_gram_whitened(const float* g, int64_t m, int f, int ld, int bias, double* G_aug, void* workspace, void* stream) {
+    if (check_chained("wmf_gram_whitened", f, ld, bias)) return WMF_EINVAL;
+    if (!g || !G_aug || !workspace || m < 0) { wmf_set_error("wmf_gram_whitened: null pointer or negative m"); return WMF_EINVAL; }
+    {   // the partial tiles of this launch within the partials of a workspace laid out for f + 1 columns
+        const int f1 = f + (bias ? 1 : 0);
+        const int64_t nfb = (f1 + 15) / 16, nt = nfb * (nfb + 1) / 2;
+        if ((int64_t)wmf_gram_nwaves(m, f1) * nt * 256 * (int64_t)sizeof(float) > gram_partial_bytes(f + 1)) {
+            wmf_set_error("wmf_gram_whitened: workspace layout too small at f=%d", f);
+            return WMF_EINVAL;
+        }
+    }
+    if (wmf_launch_gram_aug(g, m, f, ld, bias, G_aug, (float*)workspace, (double*)((char*)workspace + gram_slices_off(f + 1)),
+                            (hipStream_t)stream)) {
+        wmf_set_error("wmf_gram_whitened: unsupported f=%d", f);
+        return WMF_EINVAL;
+    }
+    return check_launch("wmf_gram_whitened");
+}
+
+int wmf_compose_whitening(const double* G_aug, const float* U, int f, int ld, int bias, int rolled, double lambda, float* W_white,
+                          float* W_unwhite, float* N_ext, int32_t* info, void* workspace, void* stream) {
+    if (check_chained("wmf_compose_whitening", f, ld, bias)) return WMF_EINVAL;
+    if (!G_aug || !U || !W_white || !W_unwhite || !N_ext || !info || !workspace) { wmf_set_error("wmf_compose_whitening: null pointer"); return WMF_EINVAL; }
+    if (rolled && !(bias && wmf_rolled_layout(f, ld))) { wmf_set_error("wmf_compose_whitening: rolled needs wmf_rolled_layout_supported(f=%d, ld=%d) and bias", f, ld); return WMF_EINVAL; }
+    if (U == W_unwhite || U == W_white) { wmf_set_error("wmf_compose_whitening: U may not alias an output"); return WMF_EINVAL; }
+    // the two small products live where the Gramian kept its partial tiles (at least 1.8 MB)
+    wmf_launch_compose(G_aug, U, f, ld, bias, rolled, lambda, W_white, W_unwhite, N_ext, info, (double*)workspace,
+                       (double*)((char*)workspace + gram_a_off(f + 1)), (hipStream_t)stream);
+    return check_launch("wmf_compose_whitening");
+}
+
+int wmf_row_transform_chained(const float* g, int64_t m, int f, int ld, int bias, const float* N_ext, int rolled, float* out,
+                              float* col0_out, void* stream) {
+    if (check_chained("wmf_row_transform_chained", f, ld, bias)) return WMF_EINVAL;
+    if (!g || !N_ext || !out || m < 0) { wmf_set_error("wmf_row_transform_chained: null pointer or negative m"); return WMF_EINVAL; }
+    const int rc = wmf_launch_transform_chained(g, m, f, ld, bias, N_ext, rolled, out, col0_out, (hipStream_t)stream);
+    if (rc) {
+        if (rc == WMF_L_LAYOUT) wmf_set_error("wmf_row_transform_chained: f=%d, ld=%d: col0_out is required with biases and out may not alias g in the split layout", f, ld);
+        else wmf_set_error("wmf_row_transform_chained: unsupported f=%d, ld=%d, rolled=%d", f, ld, rolled);
+        return WMF_EINVAL;
+    }
+    return check_launch("wmf_row_transform_chained");
+}
+
 // ---- plan ---------------------------------------------------------------------------------------
 static int bin_of(int64_t d, int f) {
     if (d <= 16) return WMF_BIN_LOW16;

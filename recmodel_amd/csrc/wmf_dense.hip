@@ -101,7 +101,9 @@ typedef __bf16 gram_bf16x8 __attribute__((ext_vector_type(8)));
 // the row masks (x * 1.0f is x: the results are the same bits).
 // (Two named register sets with the loop unrolled by two, which would drop the copies, spill: the VALU addresses 256 of the 512
 // registers, and two raw chunks + the parts + their addresses need 270 of them; measured figures in DESIGN.md section 9.)
-template <int NFB>
+// AUG (the Gramian of a solved side's g, wmf_gram_whitened): `f` counts the augmented columns, position f - 1 reads as 1 when
+// `bias` is set (column 0 is read as stored), and columns past f are replaced, not multiplied away: g's padding is not trusted.
+template <int NFB, bool AUG = false>
 __device__ __forceinline__ void gram_body6(const float* __restrict__ Y, int64_t m, int f, int ld, int bias,
                                            float* __restrict__ partial, int64_t step_lo, int64_t step_hi) {
     constexpr int NT = NFB * (NFB + 1) / 2;
@@ -113,7 +115,8 @@ __device__ __forceinline__ void gram_body6(const float* __restrict__ Y, int64_t 
     for (int i = 0; i < NT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int last_col = min(16 * (NFB - 1) + r, ld - 1);
     const float col_mask_last = (16 * (NFB - 1) + r < f) ? 1.f : 0.f;
-    const bool bias_lane = bias && r == 0;
+    const bool bias_lane = bias && r == (AUG ? (f - 1) & 15 : 0);
+    constexpr int ONE_FB = AUG ? NFB - 1 : 0;                                   // the feature block of the column that reads as 1
     // chunks of 32 rows dealt round-robin over the waves (step_lo = this wave, step_hi = the number of waves): at any moment the
     // resident waves read one contiguous stretch of the matrix
     const int64_t stride = 32 * step_hi;
@@ -137,8 +140,8 @@ __device__ __forceinline__ void gram_body6(const float* __restrict__ Y, int64_t 
                 const float rmask = (!decltype(masked)::value || c0 + 8 * q + j < m) ? 1.f : 0.f;
                 float x = fr[j][fb];
                 if (decltype(masked)::value) x *= rmask;
-                if (fb == NFB - 1) x *= col_mask_last;
-                if (fb == 0 && bias_lane) x = rmask;                            // column 0 reads as 1 (wmf_model.py:331)
+                if (fb == NFB - 1) x = AUG ? (col_mask_last != 0.f ? x : 0.f) : x * col_mask_last;
+                if (fb == ONE_FB && bias_lane) x = rmask;                       // column 0 reads as 1 (wmf_model.py:331)
                 const __bf16 h = (__bf16)x;
                 const float r1 = x - (float)h;
                 const __bf16 md = (__bf16)r1;
@@ -201,6 +204,12 @@ template <int NFB>
 __global__ __launch_bounds__(64) void gram6_kernel(const float* __restrict__ Y, int64_t m, int f, int ld, int bias,
                                                    float* __restrict__ partial, int64_t steps_per_wave) {
     gram_body6<NFB>(Y, m, f, ld, bias, partial, blockIdx.x, gridDim.x);
+}
+
+template <int NFB>
+__global__ __launch_bounds__(64) void gram6_aug_kernel(const float* __restrict__ g, int64_t m, int f1, int ld, int bias,
+                                                       float* __restrict__ partial) {
+    gram_body6<NFB, true>(g, m, f1, ld, bias, partial, blockIdx.x, gridDim.x);
 }
 
 // NSPLIT = 4 (f > 144: 136 tiles do not fit one wave's registers): the tile quarters are the FOUR WAVES OF ONE WORKGROUP, which
@@ -308,6 +317,26 @@ int wmf_launch_gram(const float* Y, int64_t m, int f, int ld, int bias, double* 
     WMF_LAUNCH("gram_reduce1_kernel", gram_reduce1_kernel, dim3((f * f + 255) / 256, WMF_GRAM_SLICES), dim3(256), 0, st, partial,
                nwaves, f, nfb, slices);
     WMF_LAUNCH("gram_reduce2_kernel", gram_reduce2_kernel, dim3((f * f + 255) / 256), dim3(256), 0, st, slices, f, G_sum);
+    return WMF_L_OK;
+}
+
+// G_aug = a^T a over the rows of a solved side, a = [g, 1] (bias) or g: (f + bias)^2 doubles.  The workspace is laid out for
+// f + 1 columns (wmf_api.hip).
+int wmf_launch_gram_aug(const float* g, int64_t m, int f, int ld, int bias, double* G_aug, float* partial, double* slices,
+                        hipStream_t st) {
+    const int f1 = f + (bias ? 1 : 0), nfb = (f1 + 15) / 16;
+    if (nfb < 7 || nfb > 9) return WMF_L_NO_KERNEL;
+    if (m <= 0) return hipMemsetAsync(G_aug, 0, (size_t)f1 * f1 * sizeof(double), st) == hipSuccess ? WMF_L_OK : WMF_L_NO_KERNEL;
+    const int nwaves = wmf_gram_nwaves(m, f1);
+    if (const int rc = wmf_dispatch_nfb<7, 9>(nfb, [&](auto n) {
+            constexpr int NFB = decltype(n)::value;
+            static const char* nm = wmf_kname("gram6_aug_kernel<%d>", NFB);
+            WMF_LAUNCH(nm, (gram6_aug_kernel<NFB>), dim3(nwaves), dim3(64), 0, st, g, m, f1, ld, bias, partial);
+            return (int)WMF_L_OK;
+        })) return rc;
+    WMF_LAUNCH("gram_reduce1_kernel", gram_reduce1_kernel, dim3((f1 * f1 + 255) / 256, WMF_GRAM_SLICES), dim3(256), 0, st, partial,
+               nwaves, f1, nfb, slices);
+    WMF_LAUNCH("gram_reduce2_kernel", gram_reduce2_kernel, dim3((f1 * f1 + 255) / 256), dim3(256), 0, st, slices, f1, G_aug);
     return WMF_L_OK;
 }
 
@@ -936,4 +965,260 @@ int wmf_launch_transform(const float* in, int64_t m, int f, int ld, const float*
     }
     if ((set_col0_one == 2 || set_col0_one == 3) && (!col0_out || in == out)) return WMF_L_LAYOUT;
     return wmf_dispatch_nfb<1, 17>(nfb, [&](auto n) { return launch_transform_nfb<decltype(n)::value>(in, m, f, ld, W, set_col0_one, out, col0_out, st); });
+}
+
+// --------------------------------------------------------------------------------------- chained
+// The whitening of a side that was just solved, straight from its g ("chained whitening"): the factors
+// X = g . U are an exact linear image of g, so the next Gramian and the next whitened side are functions of g and two small
+// matrices, and the un-whitening pass leaves the training loop.  With a = [g, 1] (bias; a = g without) and T the (f + bias) x f
+// matrix whose rows 0 .. f - 1 are U with column 0 zeroed and whose row f is e0^T (T = U without biases):
+//   in~ = a . T,   G~ = T^T (a^T a) T,   V = a . (T . W_white),   bias = g . U[:, 0].
+// Row p of T and of N_ext belongs to POSITION p of a row of g and column n of N_ext to position n of the whitened row: in rolled
+// coordinates position p holds feature p + 1 (f - 1: feature 0) on both sides.
+__device__ __forceinline__ double compose_t(const float* __restrict__ U, int f, int ld, int bias, int rolled, int p, int j) {
+    if (p >= f) return j == 0 ? 1.0 : 0.0;                                      // the row of the constant one
+    if (bias && j == 0) return 0.0;
+    const int src = rolled ? (p + 1 == f ? 0 : p + 1) : p;
+    return (double)U[src * ld + j];
+}
+// The three small products (130^3 at cfg3): sixteen lanes per output element, each with every sixteenth term, summed in a fixed
+// order -- a thread per element was one dependent chain of 130 loads and took 40 - 50 us per product.
+template <class FA, class FB>
+__device__ __forceinline__ double compose_dot16(int n, FA a, FB b) {
+    double s = 0.0;
+#pragma unroll 3
+    for (int k = threadIdx.x & 15; k < n; k += 16) s += a(k) * b(k);
+#pragma unroll
+    for (int off = 8; off; off >>= 1) s += __shfl_xor(s, off, 16);
+    return s;
+}
+// H = G_aug . T, (f + bias) x f
+__global__ __launch_bounds__(256) void compose_h_kernel(const double* __restrict__ Gaug, const float* __restrict__ U, int f, int ld,
+                                                        int bias, int rolled, double* __restrict__ H) {
+    const int f1 = f + (bias ? 1 : 0);
+    const int e0 = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    const bool live = e0 < f1 * f;
+    const int e = live ? e0 : 0;                                                // (whole groups of sixteen: all of them shuffle)
+    const int p = e / f, j = e - p * f;
+    const double s = compose_dot16(f1, [&](int k) { return Gaug[p * f1 + k]; }, [&](int k) { return compose_t(U, f, ld, bias, rolled, k, j); });
+    if (live && (threadIdx.x & 15) == 0) H[e] = s;
+}
+// G~ = T^T . H, f x f; element (i, j) and (j, i) are the same sum (the factorisation reads one triangle)
+__global__ __launch_bounds__(256) void compose_g_kernel(const double* __restrict__ H, const float* __restrict__ U, int f, int ld,
+                                                        int bias, int rolled, double* __restrict__ Gt) {
+    const int f1 = f + (bias ? 1 : 0);
+    const int e0 = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    const bool live = e0 < f * f;
+    const int e = live ? e0 : 0;
+    int i = e / f, j = e - i * f;
+    if (i > j) { const int t = i; i = j; j = t; }
+    const double s = compose_dot16(f1, [&](int p) { return compose_t(U, f, ld, bias, rolled, p, i); }, [&](int p) { return H[p * f + j]; });
+    if (live && (threadIdx.x & 15) == 0) Gt[e] = s;
+}
+// N_ext = [T . W_white | U[:, 0]] on an ld-strided image of f + bias rows, columns in the whitened side's positions
+__global__ __launch_bounds__(256) void compose_n_kernel(const float* __restrict__ U, const float* __restrict__ Ww, int f, int ld,
+                                                        int bias, int rolled, float* __restrict__ N) {
+    const int f1 = f + (bias ? 1 : 0);
+    const int e0 = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    const bool live = e0 < f1 * ld;
+    const int e = live ? e0 : 0;
+    const int p = e / ld, n = e - p * ld;
+    const int col = n >= f ? 0 : rolled ? (n + 1 == f ? 0 : n + 1) : n;
+    double s = compose_dot16(f, [&](int j) { return compose_t(U, f, ld, bias, rolled, p, j); }, [&](int j) { return (double)Ww[j * ld + col]; });
+    if (n >= f) s = (n == f && bias && p < f) ? (double)U[(rolled ? (p + 1 == f ? 0 : p + 1) : p) * ld] : 0.0;   // the bias X[:, 0] = g . U[:, 0]; padding
+    if (live && (threadIdx.x & 15) == 0) N[e] = (float)s;
+}
+
+// scratch: (f + bias) * f + f * f doubles (the Gramian's partial tiles are free by now)
+int wmf_launch_compose(const double* G_aug, const float* U, int f, int ld, int bias, int rolled, double lambda, float* Wwhite,
+                       float* Wunwhite, float* N_ext, int32_t* info, double* scratch, double* gA, hipStream_t st) {
+    const int f1 = f + (bias ? 1 : 0);
+    double* H = scratch;
+    double* Gt = scratch + (size_t)f1 * f;
+    WMF_LAUNCH("compose_h_kernel", compose_h_kernel, dim3((f1 * f + 15) / 16), dim3(256), 0, st, G_aug, U, f, ld, bias, rolled, H);
+    WMF_LAUNCH("compose_g_kernel", compose_g_kernel, dim3((f * f + 15) / 16), dim3(256), 0, st, H, U, f, ld, bias, rolled, Gt);
+    wmf_launch_factorize(Gt, f, ld, lambda, Wwhite, Wunwhite, info, gA, st);
+    WMF_LAUNCH("compose_n_kernel", compose_n_kernel, dim3((f1 * ld + 15) / 16), dim3(256), 0, st, U, Wwhite, f, ld, bias, rolled, N_ext);
+    return WMF_L_OK;
+}
+
+// out = a . N_ext in the layout wmf_row_transform(set_col0_one = mode) writes (0: plain, 1: bias to col0_out, 2: split layout,
+// 3: split layout in rolled coordinates with the bias bits in the body), a = [g, 1]: transform6_kernel's body with input
+// position f read as 1 and the bias of an output row taken from accumulator column f (the last column of N_ext) instead of
+// the input.  N_ext is dense (a lower- times an upper-triangular matrix): all 5 x 9 tile pairs are issued at f = 129.
+// Bytes per row: one row of g read (4 ld), one packed row (4 (f - 1)) and one pair (8) written.
+template <int NFB, int MODE>
+__global__ __launch_bounds__(512) void chain6_kernel(const float* __restrict__ in, int64_t m, int f, int ld,
+                                                     const float* __restrict__ W,
+                                                     float* __restrict__ out, float* __restrict__ col0_out,
+                                                     int64_t nblocks16) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    constexpr int NP = 16 * NFB;
+    constexpr int NKC = (NP + 31) / 32;
+    constexpr int KS = 176;                      // as transform6_kernel: 88 dwords per LDS row
+    static_assert(32 * NKC <= KS, "K does not fit the LDS row");
+    __bf16* Wt = reinterpret_cast<__bf16*>(smem_raw);             // [3][NP][KS]
+    __shared__ int nz[NKC * NFB];
+    const int tid = threadIdx.x;
+    constexpr bool bias = MODE != 0;
+    const int f1 = f + (bias ? 1 : 0);                            // rows and columns of N_ext
+    for (int e = tid; e < NKC * NFB; e += 512) nz[e] = 0;
+    __syncthreads();
+    typedef __bf16 stage_bf16x8 __attribute__((ext_vector_type(8)));
+    stage_bf16x8* Ws = reinterpret_cast<stage_bf16x8*>(Wt);
+    for (int it = tid; it < NP * (KS / 8); it += 512) {
+        const int k8 = it / NP, n = it - k8 * NP;
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int k = 8 * k8 + j;
+            const bool in_w = k < f1 && n < f1;
+            v[j] = W[in_w ? k * ld + n : 0];
+            if (!in_w) v[j] = 0.f;
+        }
+        stage_bf16x8 ph, pm, pl;
+        bool any = false;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const __bf16 h = (__bf16)v[j];
+            const float r1 = v[j] - (float)h;
+            const __bf16 md = (__bf16)r1;
+            ph[j] = h; pm[j] = md; pl[j] = (__bf16)(r1 - (float)md);
+            any |= v[j] != 0.f;
+        }
+        const int at = (n * KS + 8 * k8) / 8;
+        Ws[at] = ph;
+        Ws[NP * KS / 8 + at] = pm;
+        Ws[2 * NP * KS / 8 + at] = pl;
+        if (any) nz[(k8 >> 2) * NFB + (n >> 4)] = 1;               // benign race: every writer stores 1 (k8 >> 2 < NKC: k < f1 there)
+    }
+    __syncthreads();
+    const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 15, q = lane >> 4;
+    const int nch = ld >> 2;
+    unsigned cmask[NKC];
+#pragma unroll
+    for (int c = 0; c < NKC; ++c) {
+        unsigned mk = 0;
+#pragma unroll
+        for (int nb = 0; nb < NFB; ++nb) mk |= nz[c * NFB + nb] ? (1u << nb) : 0u;
+        cmask[c] = __builtin_amdgcn_readfirstlane(mk);
+    }
+    typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+    const bf16x8_t* Wl = reinterpret_cast<const bf16x8_t*>(Wt);
+    const int64_t stride = (int64_t)gridDim.x * 8;
+    auto request = [&](int64_t blk, float4 (&x)[2 * NKC]) {
+        const int64_t row = blk * 16 + r;
+        const float4* irow = reinterpret_cast<const float4*>(in + (row < m ? row : 0) * (int64_t)ld);   // loads are unconditional
+#pragma unroll
+        for (int c = 0; c < NKC; ++c) {
+            x[2 * c] = irow[min(8 * c + 2 * q, nch - 1)];
+            x[2 * c + 1] = irow[min(8 * c + 2 * q + 1, nch - 1)];
+        }
+    };
+    constexpr bool sp = MODE == 2 || MODE == 3;                         // split layout: packed body rows of f - 1 floats + the pairs
+    const int fcol = f & 15;                                         // accumulator column f (the bias) is column fcol of block NFB - 1
+    auto block = [&](int64_t blk, float4 (&xc)[2 * NKC]) {
+        f32x4 acc[NFB];
+#pragma unroll
+        for (int nb = 0; nb < NFB; ++nb) acc[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < NKC; ++c) {
+            const int k0 = 32 * c + 8 * q;
+            float xe[8] = {xc[2 * c].x, xc[2 * c].y, xc[2 * c].z, xc[2 * c].w, xc[2 * c + 1].x, xc[2 * c + 1].y, xc[2 * c + 1].z, xc[2 * c + 1].w};
+            // f >= 16 (NFB - 1) in every launch: only the last chunk can hold positions past the f solved features -- the one,
+            // then nothing (g's padding columns are not trusted: replaced, not multiplied)
+            if (32 * c + 32 > 16 * (NFB - 1)) {                  // (a constant once the chunk loop is unrolled)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) if (!(k0 + e < f)) xe[e] = (bias && k0 + e == f) ? 1.f : 0.f;
+            }
+            bf16x8_t ah, am, al;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const __bf16 h = (__bf16)xe[e];
+                const float r1 = xe[e] - (float)h;
+                const __bf16 md = (__bf16)r1;
+                ah[e] = h; am[e] = md; al[e] = (__bf16)(r1 - (float)md);
+            }
+            unsigned mv = cmask[c];
+            asm volatile("" : "+v"(mv));
+            const unsigned mk = __builtin_amdgcn_readfirstlane(mv);
+#pragma unroll
+            for (int nb = 0; nb < NFB; ++nb) {
+                if (!(mk & (1u << nb))) continue;
+                const int at = ((16 * nb + r) * KS + 32 * c + 8 * q) / 8;
+                const bf16x8_t bh = Wl[at], bm = Wl[NP * KS / 8 + at], bl = Wl[2 * NP * KS / 8 + at];
+                f32x4 cc = acc[nb];
+                cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, cc, 0, 0, 0);
+                cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bm, cc, 0, 0, 0);
+                cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, cc, 0, 0, 0);
+                cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bh, cc, 0, 0, 0);
+                cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm, cc, 0, 0, 0);
+                cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, cc, 0, 0, 0);
+                acc[nb] = cc;
+            }
+        }
+        // acc[nb][reg] = out[blk*16 + 4q + reg][16 nb + r]; the stores are transform6_kernel's, but the bias of output row
+        // 4 q + reg is acc[NFB - 1][reg] of lane 16 q + fcol, and the padding columns [f, ld) of a plain row are written as zero
+        const int wid = sp ? f - 1 : ld;
+        const bool stuff = MODE == 3 && (r & 7) < 2;
+        const int stuff_sh = 2 * (r >> 3) + (r & 7);
+        auto store_rows = [&](auto full) {
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int64_t orow = blk * 16 + 4 * q + reg;
+                const float bias_src = acc[NFB - 1][reg];        // (a copy: a bit cast of the vector element itself reads element 0)
+                const unsigned bbits = MODE == 3 ? (unsigned)__builtin_amdgcn_ds_bpermute((16 * q + fcol) * 4, __builtin_bit_cast(int, bias_src)) : 0u;
+                if (decltype(full)::value || orow < m) {
+                    float* o = out + orow * (int64_t)wid;
+#pragma unroll
+                    for (int nb = 0; nb < NFB; ++nb) {
+                        const int col = 16 * nb + r;
+                        float v = acc[nb][reg];
+                        if (MODE == 3 && 16 * nb < 128) {
+                            const unsigned vb = __builtin_bit_cast(unsigned, v);
+                            v = __builtin_bit_cast(float, stuff ? ((vb & ~1u) | ((bbits >> (4 * nb + stuff_sh)) & 1u)) : vb);
+                        }
+                        if (nb < NFB - 1) { o[col] = v; continue; }
+                        if (col < wid) o[col] = col < f ? v : 0.f;
+                        else if (sp && col == f - 1) col0_out[2 * orow] = v;
+                        if (bias && col == f) col0_out[sp ? 2 * orow + 1 : orow] = v;
+                    }
+                }
+            }
+        };
+        if (blk * 16 + 16 <= m) store_rows(std::true_type{});
+        else store_rows(std::false_type{});
+    };
+    float4 xa[2 * NKC];
+    for (int64_t blk = (int64_t)blockIdx.x * 8 + wv; blk < nblocks16; blk += stride) {
+        request(blk, xa);
+        block(blk, xa);
+    }
+}
+
+int wmf_launch_transform_chained(const float* g, int64_t m, int f, int ld, int bias, const float* N_ext, int rolled, float* out,
+                                 float* col0_out, hipStream_t st) {
+    if (m <= 0) return WMF_L_OK;
+    const int f1 = f + (bias ? 1 : 0), nfb = (f1 + 15) / 16;
+    if (nfb < 7 || nfb > 9) return WMF_L_NO_KERNEL;
+    if (rolled && !(bias && wmf_rolled_layout(f, ld))) return WMF_L_NO_KERNEL;
+    const int mode = !bias ? 0 : rolled ? 3 : wmf_split_layout(f, ld) ? 2 : 1;          // the layout wmf_row_transform would write
+    if (bias && !col0_out) return WMF_L_LAYOUT;
+    if (g == out && mode >= 2) return WMF_L_LAYOUT;
+    const int64_t nblk = (m + 15) / 16;
+    int64_t grid = (nblk + 7) / 8;
+    if (grid > wmf_cu_count()) grid = wmf_cu_count();              // one workgroup per CU stages N_ext once (launch_transform6)
+    if (grid < 1) grid = 1;
+    return wmf_dispatch_nfb<7, 9>(nfb, [&](auto n) {
+        constexpr int NFB = decltype(n)::value;
+        return wmf_dispatch_nfb<0, 3>(mode, [&](auto md) {
+            constexpr int MODE = decltype(md)::value;
+            constexpr size_t lds = (size_t)3 * 16 * NFB * 176 * 2;
+            static const char* nm = wmf_kname("chain6_kernel<%d, %d>", NFB, MODE);
+            WMF_LAUNCH_LDS(nm, (chain6_kernel<NFB, MODE>), lds, dim3((unsigned)grid), dim3(512), lds, st, g, m, f, ld, N_ext, out,
+                           col0_out, nblk);
+            return (int)WMF_L_OK;
+        });
+    });
 }

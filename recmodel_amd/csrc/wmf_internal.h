@@ -70,6 +70,13 @@ int wmf_launch_factorize(const double* G_sum, int f, int ld, double lambda, floa
                          int32_t* info, double* gA, hipStream_t st);
 int wmf_launch_transform(const float* in, int64_t m, int f, int ld, const float* W, int set_col0_one, float* out,
                          float* col0_out, hipStream_t st);
+// the chained whitening of a solved side (wmf_dense.hip, "chained")
+int wmf_launch_gram_aug(const float* g, int64_t m, int f, int ld, int bias, double* G_aug, float* partial, double* slices,
+                        hipStream_t st);
+int wmf_launch_compose(const double* G_aug, const float* U, int f, int ld, int bias, int rolled, double lambda, float* Wwhite,
+                       float* Wunwhite, float* N_ext, int32_t* info, double* scratch, double* gA, hipStream_t st);
+int wmf_launch_transform_chained(const float* g, int64_t m, int f, int ld, int bias, const float* N_ext, int rolled, float* out,
+                                 float* col0_out, hipStream_t st);
 
 // ---- how a launch is routed ("How a launch is routed") --------------------------------------------------------------
 // What a launcher answers; wmf_api.hip (launch_error) turns it into WMF_E* and the message.

@@ -117,6 +117,21 @@ class HipKernels:
         _lib.check(self.lib.wmf_row_transform(_ptr(inp), m, f, ld, _ptr(W), int(set_col0_one), _ptr(out), _ptr(col0_out),
                                               _stream()))
 
+    # the chained whitening of a solved side (include/wmf_hip.h): workspace of gram_workspace_bytes(f + 1)
+    def chained_supported(self, f, ld, bias):
+        return bool(self.lib.wmf_chained_supported(f, ld, int(bias)))
+
+    def gram_whitened(self, g, m, f, ld, bias, G_aug, ws):
+        _lib.check(self.lib.wmf_gram_whitened(_ptr(g), m, f, ld, int(bias), _ptr(G_aug), _ptr(ws), _stream()))
+
+    def compose_whitening(self, G_aug, U, f, ld, bias, rolled, lam, W_white, W_unwhite, N_ext, info, ws):
+        _lib.check(self.lib.wmf_compose_whitening(_ptr(G_aug), _ptr(U), f, ld, int(bias), int(rolled), float(lam), _ptr(W_white),
+                                                  _ptr(W_unwhite), _ptr(N_ext), _ptr(info), _ptr(ws), _stream()))
+
+    def row_transform_chained(self, g, m, f, ld, bias, N_ext, rolled, out, col0_out):
+        _lib.check(self.lib.wmf_row_transform_chained(_ptr(g), m, f, ld, int(bias), _ptr(N_ext), int(rolled), _ptr(out),
+                                                      _ptr(col0_out), _stream()))
+
     def plan_create(self, indptr_host, n, f, bias):
         handle = ctypes.c_void_p()
         _lib.check(self.lib.wmf_plan_create(indptr_host.ctypes.data_as(ctypes.c_void_p), n, f, int(bool(bias)), ctypes.byref(handle)))
@@ -418,11 +433,38 @@ def gathered_positions(ids, world, rows_per_rank, chunk_len, owner=None, local=N
     return world * s_c + r * len_c + (j - s_c)
 
 
+class _SideBuffers(dict):
+    """The per-side factor buffers of an engine as readers see them: taking a side's buffer first writes the factors the
+    engine still owes it (AlsEngine._materialize: the chained whitening keeps a solved side as its g).  The engine's own
+    chained path reads the buffers through raw().  The buffers are for reading: factors are loaded with set_factors(), which
+    also tells the engine that the side's g no longer defines them."""
+
+    def __init__(self, engine, data):
+        super().__init__(data)
+        self._engine = engine
+
+    def raw(self, side):
+        return dict.__getitem__(self, side)
+
+    def __getitem__(self, side):
+        self._engine._materialize(side)
+        return dict.__getitem__(self, side)
+
+    def get(self, side, default=None):
+        return self[side] if side in self else default
+
+    def values(self):
+        return [self[s] for s in self]
+
+    def items(self):
+        return [(s, self[s]) for s in self]
+
+
 class AlsEngine:
     """Weighted-ALS state of one rank: factor blocks, whitened gathers, CSR shards."""
 
     def __init__(self, n_users, n_items, dim, bias, gamma, device=None, group=None, kernels=None, chunks=None,
-                 reduce_mode=None, pipe_mode=None, force_exchange=None, sparse_mode=None):
+                 reduce_mode=None, pipe_mode=None, force_exchange=None, sparse_mode=None, chained=True):
         self.K = kernels if kernels is not None else HipKernels()     # raises without a GPU / built library
         self.lib = getattr(self.K, "lib", None)
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
@@ -445,6 +487,12 @@ class AlsEngine:
         self.f = self.dim + 1 if self.bias else self.dim
         self.ld = self.K.ld_for(self.f)
         self.pr = self.K.partial_row_floats(self.f) if hasattr(self.K, "partial_row_floats") else 0
+        self._fixed_from_g = False                   # the last prepare() took the chained route
+        # Chained whitening: one rank without the exchange machinery keeps a solved side as its g and
+        # whitens it for the next half step straight from there; the factors are written when somebody reads them.
+        # chained=False: every half step un-whitens, as the exchange modes must (they publish the factors).
+        self.chained = bool(chained and not self.exchange and hasattr(self.K, "row_transform_chained")
+                            and self.K.chained_supported(self.f, self.ld, self.bias))
         self._reduce_arg, self.pipe_mode, self._chunks_arg, self._sparse_arg = reduce_mode, pipe_mode, chunks, sparse_mode
         self.csr = {}          # "users": shard with local user rows, "items": shard with local item rows
         self.csr_chunks = {}   # the same rows as one Csr (own row plan) per chunk
@@ -498,10 +546,13 @@ class AlsEngine:
         dev, f32 = self.device, torch.float32
         z = lambda *shape, dtype=f32: torch.zeros(*shape, dtype=dtype, device=dev)  # noqa: E731
         # local factor blocks [rows_per_rank, ld]; rows >= n_local are padding and stay zero
-        self.factors = {s: z(self.rpr[s], self.ld) for s in self.n}
+        # (readers of factors / X get a side's factors written first where the chained whitening still owes them)
+        self._owed = {s: False for s in self.n}                 # factors[s] = g[s] . U[s] not written yet
+        self.g_valid = {s: False for s in self.n}               # g[s] holds the solutions that define the side's current factors
+        self.factors = _SideBuffers(self, {s: z(self.rpr[s], self.ld) for s in self.n})
         self.g = {s: z(self.rpr[s], self.ld) for s in self.n}
         # gathered factors of all ranks (chunk-major positions); with one rank the local block itself
-        self.X = {s: (z(W * self.rpr[s], self.ld) if self.exchange else self.factors[s]) for s in self.n}
+        self.X = _SideBuffers(self, {s: (z(W * self.rpr[s], self.ld) if self.exchange else self.factors.raw(s)) for s in self.n})
         self._pending = {s: [] for s in self.n}                            # all-gathers in flight
         # whitened gathered factors / bias of the fixed side [W * rows_per_rank, ld] -- or, where the library writes its
         # split layout (include/wmf_hip.h, wmf_row_transform: k = 16 m with biases), a packed body [.., f - 1] and the
@@ -521,7 +572,12 @@ class AlsEngine:
         self.W_white, self.W_unwhite = z(self.f, self.ld), z(self.f, self.ld)
         self.info = z(4, dtype=torch.int32)
         self.fail = z(4, dtype=torch.int32)
-        self.ws = torch.empty(self.K.gram_workspace_bytes(self.f), dtype=torch.uint8, device=dev)
+        self.ws = torch.empty(self.K.gram_workspace_bytes(self.f + 1 if self.chained else self.f), dtype=torch.uint8, device=dev)
+        if self.chained:
+            f1 = self.f + (1 if self.bias else 0)
+            self.U = {s: z(self.f, self.ld) for s in self.n}      # the W_unwhite that un-whitens g[s] (the shared one moves on)
+            self.G_aug = z(f1 * f1, dtype=torch.float64)
+            self.N_ext = z(f1, self.ld)
         self.eval_ws = torch.empty(self.K.eval_workspace_bytes(), dtype=torch.uint8, device=dev)
         self.eval_out = z(3, dtype=torch.float64)
         self.pipe = {s: False for s in self.n}               # pipelined gather mode, decided in set_interactions (needs the degrees)
@@ -801,6 +857,7 @@ class AlsEngine:
         full = torch.as_tensor(full, dtype=torch.float32)
         sh = self.shard[side]
         mine = (full[self.rank::self.world] if sh.owner is None else full[sh.my_ids(full.device)]).to(self.device)
+        self._invalidate(side)
         blk = self.factors[side]
         blk.zero_()
         blk[: mine.shape[0], : self.f] = mine
@@ -874,10 +931,37 @@ class AlsEngine:
         self._pending[side] = []
 
     # ---------------------------------------------------------------- one half step
+    def _invalidate(self, side):
+        """factors[side] are about to be written by another route than update(): g[side] no longer defines them."""
+        self.g_valid[side] = self._owed[side] = False
+
+    def _materialize(self, side):
+        """Write the factors the chained path owes ``side``: the un-whitening update() did not launch."""
+        if self._owed[side]:
+            self._owed[side] = False
+            self.K.row_transform(self.g[side], self.n_local[side], self.f, self.ld, self.U[side], self.unwhite_mode,
+                                 self.factors.raw(side), None)
+
+    def _prepare_chained(self, fixed):
+        """prepare() of a side whose g is valid: Gramian, factorisation and whitened rows straight from g (the route depends
+        on g_valid alone, never on whether the factors happen to have been written: the same bits either way)."""
+        K, n = self.K, self.n_local[fixed]
+        K.gram_whitened(self.g[fixed], n, self.f, self.ld, self.bias, self.G_aug, self.ws)
+        K.compose_whitening(self.G_aug, self.U[fixed], self.f, self.ld, self.bias, self.rolled, self.gamma, self.W_white,
+                            self.W_unwhite, self.N_ext, self.info, self.ws)
+        K.row_transform_chained(self.g[fixed], n, self.f, self.ld, self.bias, self.N_ext, self.rolled, self.V[fixed],
+                                self.bias_vec[fixed] if self.bias else None)
+
     def prepare(self, fixed):
         """Gramian of the fixed side, its Cholesky factor, and the gathered whitened factors.
         wmf_model.py:215 / :328-332."""
         K = self.K
+        # (update() leaves the factors owed only behind a chained prepare: the first half step after factors were loaded
+        # un-whitens at once, as a lone half step always did -- the launches tests/test_gpu_routing.py pins -- and the loop
+        # is chained from the second half step on)
+        self._fixed_from_g = self.chained and self.g_valid[fixed]
+        if self._fixed_from_g:
+            return self._prepare_chained(fixed)
         blk = self.factors[fixed]
         K.gram(blk, self.n_local[fixed], self.f, self.ld, self.bias, self.G, self.ws)
         if self.exchange:
@@ -908,13 +992,20 @@ class AlsEngine:
         fixed = self._other(side)
         bvec = self.bias_vec[fixed] if self.bias else None
         self._wait(side)                             # nobody may still be reading the block that is about to be rewritten
+        self._invalidate(side)
         for c, ((lo, ln), csr) in enumerate(zip(self.chunk_bounds[side], self.csr_chunks[side])):
             g = self.g[side][lo: lo + ln]
             K.solve_rows(csr._plan, self.V[fixed], bvec, csr.indptr, csr.indices, csr.values, ln, self.f, self.ld, g, self.fail,
                          self.solve_flags)
+            if self.chained and self._fixed_from_g:
+                continue                             # the factors stay owed: g and U define them (_materialize)
             real = max(0, min(ln, self.n_local[side] - lo))
-            K.row_transform(g, real, self.f, self.ld, self.W_unwhite, self.unwhite_mode, self.factors[side][lo: lo + ln], None)
+            K.row_transform(g, real, self.f, self.ld, self.W_unwhite, self.unwhite_mode, self.factors.raw(side)[lo: lo + ln], None)
             self._publish(side, c)
+        if self.chained:
+            self.U[side].copy_(self.W_unwhite)
+            self.g_valid[side] = True
+            self._owed[side] = self._fixed_from_g
         self.has_factors[side] = True
 
     def half_step(self, side):
@@ -1045,6 +1136,7 @@ class AlsEngine:
         fixed = self._other(side)
         self.prepare(fixed)
         c = self.csr[side]
+        self._invalidate(side)
         K.spmm_rows(self.V[fixed], c.indptr, c.indices, c.values, c.n_rows, self.f, self.ld, self.g[side])
         K.row_transform(self.g[side], self.n_local[side], self.f, self.ld, self.W_unwhite, self.unwhite_mode, self.factors[side], None)
         self.has_factors[side] = True

@@ -1,6 +1,8 @@
 """Timing lab for the dense shared-work kernels on a real GPU (not a test): Gramian and row transform of an [m, f] factor
 block.  Usage: python tools/dense_lab.py m k bias reps [flags,...]
-(flags: numbers or names, e.g. 0,F32_GRAM; recmodel_amd/_lib.py DEBUG_FLAGS)"""
+(flags: numbers or names, e.g. 0,F32_GRAM; recmodel_amd/_lib.py DEBUG_FLAGS)
+A library with the chained whitening (wmf_chained_supported) is also timed on it: the Gramian of g and the chained pass with a
+dense N_ext, next to the Gramian, the whitening and the un-whitening they replace."""
 import sys
 import torch
 sys.path.insert(0, '.')
@@ -50,3 +52,36 @@ for fl in flags:
     else:
         print(f"    gram vs flags={flags[0]}: {float((G - Gref).abs().max() / Gref.abs().max()):.2e}")
 lib.wmf_debug_set_flags(0)
+
+# ---- the chained whitening: gram_whitened + row_transform_chained on g against gram + whitening + un-whitening ----
+if hasattr(K, "chained_supported") and K.chained_supported(f, ld, bias):
+    rolled = bool(bias and ldv != ld and K.rolled_layout_supported(f, ld))
+    f1 = f + (1 if bias else 0)
+    ws1 = torch.empty(K.gram_workspace_bytes(f + 1), dtype=torch.uint8, device=dev)
+    Gaug = torch.zeros(f1 * f1, dtype=torch.float64, device=dev)
+    N = torch.zeros(f1, ld, device=dev)
+    N[:, :f1] = torch.randn(f1, f1, device=dev) * 0.05          # dense: a lower- times an upper-triangular matrix
+    Wl = torch.tril(torch.randn(f, ld, device=dev) * 0.05)
+    Wl[:, f:] = 0
+
+    def chained_trip():
+        K.gram_whitened(X, m, f, ld, bias, Gaug, ws1)
+        K.row_transform_chained(X, m, f, ld, bias, N, rolled, V, pairs if bias else None)
+
+    def eager_trip():
+        K.row_transform(X, m, f, ld, Wl, 4 if rolled else False, out2, None)
+        K.gram(out2, m, f, ld, bias, G, ws)
+        K.row_transform(out2, m, f, ld, W, (3 if rolled else bias), V, pairs if bias else None)
+
+    for name, trip in (("eager", eager_trip), ("chained", chained_trip)):
+        trip()
+        torch.cuda.synchronize()
+        lib.wmf_profile_enable(1)
+        for _ in range(reps):
+            trip()
+        torch.cuda.synchronize()
+        lib.wmf_profile_enable(0)
+        tab = _lib.profile_table(lib)
+        print(f"{name} (rolled={int(rolled)}): " + ", ".join(f"{nm}={ms / max(n, 1):.3f}ms x{n // reps}" for nm, _, ms, n, _, _ in tab)
+              + f"; sum per trip {sum(ms for _, _, ms, _, _, _ in tab) / reps:.3f} ms")
+        lib.wmf_profile_reset()
