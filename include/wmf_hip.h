@@ -225,6 +225,43 @@ int wmf_half_step_audit_f64(const double* X, const double* Y, int f, int bias,
                             const double* dense, double* out_sums, double* out_rows,
                             void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- why this item: the contributions of a row's stored entries to the scores of target items ------------------------------
+ * For row u of a CSR (a user's history against the fixed side Y, the items) and a target item i, the score of i with the row
+ * folded in -- predict with x_u = recompute_factors[_bias](Y, C_u, lambda), wmf_model.py:213-240 / :311-351 -- is a sum with one
+ * term per stored entry.  With y~_j = row j of Y with column 0 read as 1 when bias != 0, beta_j = Y[j, 0] when bias != 0, else 0,
+ * w_e = c_e - beta_j for the stored entry e = (j, c_e) (wmf_model.py:343), and A_u = G~ + lambda I + sum_e w_e y~_j y~_j^T, x_u =
+ * A_u^-1 sum_e (w_e + 1) y~_j of wmf_model.py:231-239 and :343-350:
+ *     contrib(u, i, e) = (w_e + 1) y~_i^T A_u^-1 y~_j,        total(u, i) = sum_e contrib(u, i, e) + beta_i = y~_i . x_u + beta_i.
+ * With a bias model the row's own bias x_u[0] is part of x_u and so is shared out over the entries.  The row is read as stored:
+ * stored zeros count, duplicates are separate entries.  Solved in whitened coordinates q = y~ W_white, where A_u becomes
+ * I + E_u, E_u = sum_e w_e q_j q_j^T, with a condition number of at most 1 + max w: float32 Cholesky, one workgroup per row, the
+ * row's system in LDS at every width f = 1 .. WMF_MAX_F.
+ * Inputs: all arrays on the device.  Y [m, ld] is the UN-whitened fixed side in the library's layout, W_white [f, ld] what
+ *   wmf_factorize returns for wmf_gram(Y, bias) and lambda (upper triangular: the entries below the diagonal are not read).
+ *   The kernel whitens what it gathers; no whitened copy of Y is made or needed.  indptr is int64[n + 1] and may be a window into
+ *   longer arrays (indices and values are then the whole arrays); values are confidences.  targets is int32 [n, n_targets]: item
+ *   ids in [0, m), or -1 for an empty slot; an item may occur several times in a row (its columns then hold the same bits).
+ * Outputs: out_contrib[p * n_targets + t] = the contribution of the stored entry at absolute position p to target t of its row
+ *   (the pointer indexes like indices).  out_total [n, n_targets] = the row's contributions added one by one in stored order in
+ *   float32, starting from 0, and then + beta_i; an empty row gives beta_i.  A -1 slot writes 0 to every output of that slot.
+ *   Every output element is written.
+ * Failures: a row whose I + E_u is not positive definite (a pivot <= 0 or not finite: only possible with effective weights <= -1)
+ *   gets NaN in every contribution and total of its non-empty slots and is counted once in fail_count (device int32, the caller
+ *   zeroes it, as for wmf_solve_rows).
+ * Limits: 1 <= n_targets <= WMF_EXPLAIN_MAX_TARGETS (split longer lists; WMF.explain does), 1 <= m < 2^31, 0 <= n < 2^31; n == 0
+ *   is a no-op.  workspace: wmf_explain_workspace_bytes(n, f, n_targets) bytes of device memory (a small constant: reserved, not
+ *   written -- every width fits LDS).
+ * The call only enqueues.  WMF_EINVAL, before any HIP call, for a bad shape, a null pointer, n_targets out of range or a workspace
+ * that is too small.  No floating-point atomics and fixed reduction orders: two runs give the same bits, a row's outputs do not
+ * depend on the other rows of the launch, a target's column does not depend on the other targets of its row. */
+#define WMF_EXPLAIN_MAX_TARGETS 16
+int64_t wmf_explain_workspace_bytes(int64_t n, int f, int32_t n_targets);
+int wmf_explain_rows(const float* Y, int64_t m, int f, int ld, int bias, const float* W_white,
+                     const int64_t* indptr, const int32_t* indices, const float* values, int64_t n,
+                     const int32_t* targets, int32_t n_targets,
+                     float* out_contrib, float* out_total, int32_t* fail_count,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+
 /* out[p] = predict(users_idx[p], items_idx[p])   wmf_model.py:205-211.
  * n_u == 1 or n_i == 1 broadcasts that index (the reference's one-user / one-item form).
  * An empty side (n_u == 0 or n_i == 0, the other 0 or 1) has no pairs: WMF_OK, nothing is read or written. */

@@ -47,6 +47,9 @@ SIGNATURES = {
     "wmf_audit_workspace_bytes": (c_i64, [c_i64]),
     "wmf_half_step_audit": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "wmf_half_step_audit_f64": (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "wmf_explain_workspace_bytes": (c_i64, [c_i64, c_int, c_int]),
+    "wmf_explain_rows": (c_int, [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                 c_vp]),
     "wmf_predict_pairs": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "wmf_partial_row_floats": (c_i64, [c_int]),
     "wmf_accumulate_rows": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp]),

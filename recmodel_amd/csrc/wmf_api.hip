@@ -544,6 +544,32 @@ int wmf_half_step_audit_f64(const double* X, const double* Y, int f, int bias, c
                                              (hipStream_t)stream), "wmf_half_step_audit_f64", f, f, "");
 }
 
+int64_t wmf_explain_workspace_bytes(int64_t n, int f, int32_t n_targets) { return wmf_explain_ws_bytes(n, f, n_targets); }
+
+int wmf_explain_rows(const float* Y, int64_t m, int f, int ld, int bias, const float* W_white, const int64_t* indptr, const int32_t* indices,
+                     const float* values, int64_t n, const int32_t* targets, int32_t n_targets, float* out_contrib, float* out_total,
+                     int32_t* fail_count, void* workspace, int64_t workspace_bytes, void* stream) {
+    int rc = check_shape(f, ld);
+    if (rc) return rc;
+    if (!Y || !W_white || !indptr || !indices || !values || !targets || !out_contrib || !out_total || !fail_count || !workspace) {
+        wmf_set_error("wmf_explain_rows: null pointer");
+        return WMF_EINVAL;
+    }
+    if (m < 1 || m > 0x7fffffffLL || n < 0 || n > 0x7fffffffLL || n_targets < 1 || n_targets > WMF_EXPLAIN_MAX_TARGETS) {
+        wmf_set_error("wmf_explain_rows: need 1 <= m < 2^31, 0 <= n < 2^31, 1 <= n_targets <= %d (m=%lld, n=%lld, n_targets=%d)",
+                      WMF_EXPLAIN_MAX_TARGETS, (long long)m, (long long)n, (int)n_targets);
+        return WMF_EINVAL;
+    }
+    if (workspace_bytes < wmf_explain_ws_bytes(n, f, n_targets)) {
+        wmf_set_error("wmf_explain_rows: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
+                      (long long)wmf_explain_ws_bytes(n, f, n_targets));
+        return WMF_EINVAL;
+    }
+    if (n == 0) return WMF_OK;
+    return launch_error(wmf_launch_explain(Y, f, ld, bias != 0, W_white, indptr, indices, values, n, targets, n_targets, out_contrib, out_total,
+                                           fail_count, (hipStream_t)stream), "wmf_explain_rows", f, ld, "");
+}
+
 int wmf_predict_pairs(const float* users, const float* items, int f, int ld, int bias, const int32_t* users_idx,
                       int64_t n_u, const int32_t* items_idx, int64_t n_i, float* out, void* stream) {
     int rc = check_shape(f, ld);

@@ -35,6 +35,7 @@ F64_ROW_WEIGHT = 1024.0
 RECOMMEND_BATCH_USERS = 4096      # users per wmf_recommend_topn call of WMF.recommend (its workspace is 8 x 64 x topn bytes a user)
 RECOMMEND_MAX_TOPN = 128          # WMF_RECOMMEND_MAX_TOPN of include/wmf_hip.h: beyond it recommend() ranks user by user
 RANKPOS_MAX_TARGETS = 16          # WMF_RANKPOS_MAX_TARGETS of include/wmf_hip.h: rank_positions() splits longer rows
+EXPLAIN_MAX_TARGETS = 16          # WMF_EXPLAIN_MAX_TARGETS of include/wmf_hip.h: explain() splits longer target lists
 
 
 def _wrapped_ids(ids, n, what, dtype=np.int32):
@@ -146,6 +147,7 @@ class WMF(RecModel):
         self._engine = None
         self._dev = None           # (key, users_t, items_t, f, ld): device copies of the public arrays for predict() / rank()
         self._inv_norms = {}       # {"users" / "items": float32 [rows] on the device}: inverse feature norms of the copies in _dev
+        self._white = {}           # {gamma: W_white [f, ld] on the device}: whitening of the item copy in _dev (explain)
 
     # ------------------------------------------------------------------ engine plumbing
     def _new_engine(self):
@@ -170,6 +172,7 @@ class WMF(RecModel):
                 return t
             self._dev = (key, up(self.users), up(self.items), f, ld)
             self._inv_norms = {}
+            self._white = {}
         return self._dev[1:]
 
     def _device_inv_norms(self, side):
@@ -481,6 +484,7 @@ class WMF(RecModel):
         self._synced = (id(self.users), id(self.items))
         self._dev = None
         self._inv_norms = {}
+        self._white = {}
 
     def _pull(self, eng, sides=("users", "items")):
         for s in sides:
@@ -540,6 +544,127 @@ class WMF(RecModel):
             eng.set_interactions(indptr, indices, values)
             out = eng.audit(side, rows)
         return out.pop("eta").cpu().numpy() if rows else out
+
+    # ------------------------------------------------------------------ a15: explain
+    def _device_whitening(self):
+        """(users_t, items_t, f, ld, W_white of the item copy for the model's gamma): wmf_gram + wmf_factorize on the device copy
+        of ``items``, kept exactly as long as that copy is (as ``_device_inv_norms``) and per gamma."""
+        users_t, items_t, f, ld = dev = self._device_factors()
+        key = float(self.gamma)
+        if key not in self._white:
+            lib = _lib.load()
+            ws = torch.empty(int(lib.wmf_gram_workspace_bytes(f)), dtype=torch.uint8, device="cuda")
+            G = torch.empty(f * f, dtype=torch.float64, device="cuda")
+            W_white, W_unwhite = (torch.zeros(f, ld, dtype=torch.float32, device="cuda") for _ in range(2))
+            info = torch.zeros(4, dtype=torch.int32, device="cuda")
+            _lib.check(lib.wmf_gram(_ptr(items_t), items_t.shape[0], f, ld, int(self.bias is True), _ptr(G), _ptr(ws), _stream()))
+            _lib.check(lib.wmf_factorize(_ptr(G), f, ld, key, _ptr(W_white), _ptr(W_unwhite), _ptr(info), _ptr(ws), _stream()))
+            minor = int(info[0])
+            if minor:
+                raise _lib.WmfNumericError(f"Gramian + gamma*I is not positive definite (leading minor {minor})")
+            self._white[key] = W_white
+        return dev + (self._white[key],)
+
+    def explain(self, users, items, count_mat, topk=10, alpha=10, beta=1, pre_process_count='log'):
+        """Why these items: the score of each of ``items`` for each of ``users`` with the user's row of ``count_mat`` folded in
+        -- ``predict`` on ``recompute_factors[_bias](items, C_u, gamma)`` (wmf_model.py:213-240 / :311-351), which is the
+        model's own score right after a user half step -- split into one term per stored entry of the user's history:
+        contrib = (w_e + 1) y~_i^T A_u^-1 y~_j with the A_u of wmf_model.py:231-239 / :343-350, total = their sum + the item's
+        bias.  With a bias model the user's bias is part of the folded-in row and so is shared out over the entries.
+        ``users``: an int or a sequence of B ids (negative ids count from the end, as in ``recommend``).  ``items``: [B, T] or [B]
+        item ids, for an int user a 1-D list of T items; -1 is an empty slot, so the output of ``recommend`` can be passed
+        straight in.  ``count_mat``: the [users, items] count matrix of ``train``; the requested rows are read as stored and
+        transformed on the device as ``train`` does (wmf_model.py:119-123).
+        Returns, with ``topk`` set, ``(total float32 [B, T], history_items int64 [B, T, topk], contributions float32 [B, T,
+        topk])``: the largest contributions first, equal ones in stored order, padded with -1 / 0.  With ``topk=None``:
+        ``(total, indptr, indices, contributions [nnz, T])`` on the requested rows as stored.  An int user drops the B axis, 1-D
+        ``items`` for a sequence of users drop the T axis.  A row whose system is not positive definite (effective weights
+        <= -1) comes back as NaN.  One workgroup per row on the device (wmf_explain_rows); a float64 model is served from its
+        float32 copies, as ``recommend`` is."""
+        if self.weighted is not True:
+            raise ValueError("the contributions are those of the weighted branch (weighted=True)")
+        if pre_process_count not in ('log', 'linear'):
+            raise ValueError(f"Pre_process_count {pre_process_count} is not implement please use log or linear.")
+        if self.users is None:
+            raise ValueError("the model has no user factors yet: train it first")
+        n_users_model, n_items = self.users.shape[0], self.items.shape[0]
+        if not scipy.sparse.issparse(count_mat) or count_mat.shape != (n_users_model, n_items):
+            raise ValueError(f"count_mat must be a sparse matrix of shape {(n_users_model, n_items)}, got {getattr(count_mat, 'shape', None)}")
+        if topk is not None and int(topk) < 1:
+            raise ValueError(f"topk must be at least 1 or None, not {topk}")
+        one = np.ndim(users) == 0
+        u = _wrapped_ids(np.atleast_1d(np.asarray(users)).reshape(-1).astype(np.int64), n_users_model, "user", np.int64)
+        tg = np.asarray(items)
+        if tg.size and tg.dtype.kind not in "iu":
+            raise ValueError(f"items must be integer ids, not {tg.dtype}")
+        flat = tg.ndim == 1 and not one
+        if one and tg.ndim == 1:
+            tg = tg.reshape(1, -1)
+        elif flat and tg.shape[0] == len(u):
+            tg = tg.reshape(-1, 1)
+        if tg.ndim != 2 or tg.shape[0] != len(u) or tg.shape[1] < 1:
+            raise ValueError(f"items must have shape [{len(u)}, T] or [{len(u)}] (an int user: [T]), got {np.shape(items)}")
+        tg = tg.astype(np.int64)
+        if tg.size and (tg.min() < -1 or tg.max() >= n_items):
+            raise ValueError(f"items must be ids in [0, {n_items}) or -1 for an empty slot")
+        _lib.require_gpu()
+        # the requested rows exactly as stored (stored zeros, duplicates and their order are kept)
+        mat = count_mat if scipy.sparse.isspmatrix_csr(count_mat) else scipy.sparse.csr_matrix(count_mat)
+        lens = (mat.indptr[u + 1] - mat.indptr[u]).astype(np.int64)
+        indptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        pos = np.repeat(mat.indptr[u].astype(np.int64) - indptr[:-1], lens) + np.arange(indptr[-1], dtype=np.int64)
+        indices = mat.indices[pos].astype(np.int64)
+        B, T, nnz = len(u), tg.shape[1], int(indptr[-1])
+        total = np.zeros((B, T), dtype=np.float32)
+        contrib = np.zeros((nnz, T), dtype=np.float32)
+        if B:
+            self._explain_rows(u, indptr, indices, np.asarray(mat.data[pos], dtype=np.float32), tg, alpha, beta,
+                               0 if pre_process_count == 'log' else 1, total, contrib)
+        if topk is None:
+            out = (total, indptr, indices, contrib)
+            if one:
+                out = (total[0],) + out[1:]
+            elif flat:
+                out = (total[:, 0], indptr, indices, contrib[:, 0])
+            return out
+        topk = int(topk)
+        hist = np.full((B, T, topk), -1, dtype=np.int64)
+        best = np.zeros((B, T, topk), dtype=np.float32)
+        for b in range(B):
+            lo, hi = indptr[b], indptr[b + 1]
+            keep = min(topk, hi - lo)
+            for t in np.nonzero(tg[b] >= 0)[0] if keep else ():
+                order = np.argsort(-contrib[lo:hi, t], kind="stable")[:keep]      # largest first, equal ones in stored order
+                hist[b, t, :keep] = indices[lo:hi][order]
+                best[b, t, :keep] = contrib[lo:hi, t][order]
+        out = (total, hist, best)
+        if one:
+            out = tuple(o[0] for o in out)
+        elif flat:
+            out = tuple(o[:, 0] for o in out)
+        return out
+
+    def _explain_rows(self, u, indptr, indices, counts, tg, alpha, beta, mode, total, contrib):
+        """wmf_explain_rows in batches of rows (_scan_batches) and slices of at most EXPLAIN_MAX_TARGETS targets; fills ``total``
+        [B, T] and ``contrib`` [nnz, T]."""
+        users_t, items_t, f, ld, W_white = self._device_whitening()
+        lib = _lib.load()
+        vals = torch.from_numpy(np.append(counts, np.float32(0))).cuda()          # (one spare element: never empty)
+        _lib.check(lib.wmf_confidence_transform(_ptr(vals), len(counts), float(alpha), float(beta), mode, _stream()))
+        fail = torch.zeros(1, dtype=torch.int32, device="cuda")
+        for t0 in range(0, tg.shape[1], EXPLAIN_MAX_TARGETS):
+            part = np.ascontiguousarray(tg[:, t0: t0 + EXPLAIN_MAX_TARGETS], dtype=np.int32)
+            tc = part.shape[1]
+            tg_d = torch.from_numpy(part).cuda()
+            total_d = torch.empty(len(u), tc, dtype=torch.float32, device="cuda")
+            contrib_d = torch.empty(len(counts) + 1, tc, dtype=torch.float32, device="cuda")
+            # (the pointers index the whole per-entry arrays, as they do the index array)
+            total[:, t0: t0 + tc], got = self._scan_batches(
+                u, [(indptr, indices)], lambda rows: lib.wmf_explain_workspace_bytes(rows, f, tc), [total_d, contrib_d],
+                lambda b0, nb, ids, csrs, *ws: lib.wmf_explain_rows(
+                    _ptr(items_t), items_t.shape[0], f, ld, int(self.bias is True), _ptr(W_white), *csrs[0], _ptr(vals), nb,
+                    _ptr(tg_d[b0:]), tc, _ptr(contrib_d), _ptr(total_d[b0:]), _ptr(fail), *ws))
+            contrib[:, t0: t0 + tc] = got[:len(counts)]
 
     # ------------------------------------------------------------------ a3 / a4: operator seam
     def recompute_factors(self, Y, C, lambda_reg):
