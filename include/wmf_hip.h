@@ -262,6 +262,35 @@ int wmf_explain_rows(const float* Y, int64_t m, int f, int ld, int bias, const f
                      float* out_contrib, float* out_total, int32_t* fail_count,
                      void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- fold a history in: the factors of rows that were never trained on -----------------------------------------------------
+ * For row u of a CSR (a history against the fixed side Y, the items) the row a user half step would give it:
+ *     X_out[u] = x_u = A_u^-1 sum_e (w_e + 1) y~_j,        A_u = G~ + lambda I + sum_e w_e y~_j y~_j^T
+ * over the stored entries e = (j, c_e) of the row, with y~_j, beta_j and w_e = c_e - beta_j as defined for wmf_explain_rows: row u
+ * of recompute_factors[_bias](Y, C, lambda), wmf_model.py:213-240 / :311-351 (the row system of :231-239 / :343-350).  It is the
+ * x_u of wmf_explain_rows: y~_i . x_u + beta_i is that call's total(u, i).  The row is read as stored: stored zeros count,
+ * duplicates are separate entries.  Solved in whitened coordinates q = y~ W_white: (I + E_u) g = b with E_u = sum_e w_e q_j q_j^T
+ * and b = sum_e (w_e + 1) q_j, x_u = W_white g; float32 Cholesky, one workgroup per row, the row's system in LDS at every width
+ * f = 1 .. WMF_MAX_F.
+ * Inputs: those of wmf_explain_rows -- all arrays on the device, Y [m, ld] the UN-whitened fixed side in the library's layout,
+ *   W_white [f, ld] what wmf_factorize returns for wmf_gram(Y, bias) and lambda (the entries below the diagonal are not read),
+ *   indptr int64[n + 1], possibly a window into longer indices / values arrays; values are confidences.
+ * Output: X_out [n, ld] in the library's layout: row u is a row of `users` -- with bias != 0 column 0 is the row's own bias, as in
+ *   the output of recompute_factors_bias -- and the padding columns [f, ld) are written as zeros, so the block can be handed to
+ *   wmf_recommend_topn, wmf_predict_pairs or wmf_similar_topn as it is.  An empty row gives zeros (wmf_model.py:274-276).  Every
+ *   element of the n rows is written.
+ * Failures: a row whose I + E_u is not positive definite (a pivot <= 0 or not finite: only possible with effective weights <= -1)
+ *   gets NaN in its f columns (zeros in its padding) and is counted once in fail_count (device int32, the caller zeroes it).
+ * Limits: 1 <= m < 2^31, 0 <= n < 2^31; n == 0 is a no-op.  workspace: wmf_foldin_workspace_bytes(n, f) bytes of device memory
+ *   (a small constant: reserved, not written -- every width fits LDS).
+ * The call only enqueues.  WMF_EINVAL, before any HIP call, for a bad shape, a null pointer or a workspace that is too small.  No
+ * floating-point atomics and fixed reduction orders: two runs give the same bits, a row's output does not depend on the other
+ * rows of the launch or on its position in it. */
+int64_t wmf_foldin_workspace_bytes(int64_t n, int f);
+int wmf_foldin_rows(const float* Y, int64_t m, int f, int ld, int bias, const float* W_white,
+                    const int64_t* indptr, const int32_t* indices, const float* values, int64_t n,
+                    float* X_out, int32_t* fail_count,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+
 /* out[p] = predict(users_idx[p], items_idx[p])   wmf_model.py:205-211.
  * n_u == 1 or n_i == 1 broadcasts that index (the reference's one-user / one-item form).
  * An empty side (n_u == 0 or n_i == 0, the other 0 or 1) has no pairs: WMF_OK, nothing is read or written. */

@@ -50,6 +50,8 @@ SIGNATURES = {
     "wmf_explain_workspace_bytes": (c_i64, [c_i64, c_int, c_int]),
     "wmf_explain_rows": (c_int, [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_i64,
                                  c_vp]),
+    "wmf_foldin_workspace_bytes": (c_i64, [c_i64, c_int]),
+    "wmf_foldin_rows": (c_int, [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "wmf_predict_pairs": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "wmf_partial_row_floats": (c_i64, [c_int]),
     "wmf_accumulate_rows": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp]),

@@ -570,6 +570,31 @@ int wmf_explain_rows(const float* Y, int64_t m, int f, int ld, int bias, const f
                                            fail_count, (hipStream_t)stream), "wmf_explain_rows", f, ld, "");
 }
 
+int64_t wmf_foldin_workspace_bytes(int64_t n, int f) { return wmf_foldin_ws_bytes(n, f); }
+
+int wmf_foldin_rows(const float* Y, int64_t m, int f, int ld, int bias, const float* W_white, const int64_t* indptr, const int32_t* indices,
+                    const float* values, int64_t n, float* X_out, int32_t* fail_count, void* workspace, int64_t workspace_bytes,
+                    void* stream) {
+    int rc = check_shape(f, ld);
+    if (rc) return rc;
+    if (!Y || !W_white || !indptr || !indices || !values || !X_out || !fail_count || !workspace) {
+        wmf_set_error("wmf_foldin_rows: null pointer");
+        return WMF_EINVAL;
+    }
+    if (m < 1 || m > 0x7fffffffLL || n < 0 || n > 0x7fffffffLL) {
+        wmf_set_error("wmf_foldin_rows: need 1 <= m < 2^31, 0 <= n < 2^31 (m=%lld, n=%lld)", (long long)m, (long long)n);
+        return WMF_EINVAL;
+    }
+    if (workspace_bytes < wmf_foldin_ws_bytes(n, f)) {
+        wmf_set_error("wmf_foldin_rows: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
+                      (long long)wmf_foldin_ws_bytes(n, f));
+        return WMF_EINVAL;
+    }
+    if (n == 0) return WMF_OK;
+    return launch_error(wmf_launch_foldin(Y, f, ld, bias != 0, W_white, indptr, indices, values, n, X_out, fail_count, (hipStream_t)stream),
+                        "wmf_foldin_rows", f, ld, "");
+}
+
 int wmf_predict_pairs(const float* users, const float* items, int f, int ld, int bias, const int32_t* users_idx,
                       int64_t n_u, const int32_t* items_idx, int64_t n_i, float* out, void* stream) {
     int rc = check_shape(f, ld);

@@ -20,8 +20,8 @@
 #include <math.h>
 #include "wmf_common.h"
 #include "wmf_internal.h"
+#include "wmf_rowgather.h"                  /* EX_CHUNK, ex_sum16, ex_whiten8, ex_load_row: shared with wmf_foldin.hip */
 
-#define EX_CHUNK 8                          /* stored entries gathered and whitened at a time */
 #define EX_SLOTS WMF_EXPLAIN_MAX_TARGETS    /* target slots of a row: one 16-lane group each */
 #define WMF_EXPLAIN_MAX_BLOCKS 1024
 #define WMF_EXPLAIN_WS_BYTES 256
@@ -34,35 +34,6 @@ __host__ __device__ static inline int ex_tri_floats(int f) {
     return t > r ? t : r;
 }
 static inline size_t ex_lds_bytes(int f) { return (size_t)(ex_tri_floats(f) + (EX_SLOTS + EX_CHUNK + 1) * f) * sizeof(float); }
-
-// sum over the 16 lanes of a group, the same bits on every lane
-__device__ __forceinline__ float ex_sum16(float v) {
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// out[e][b] = sum over a <= b of raw[e][a] W[a][b] for the 8 rows of raw (LDS, f floats each), a thread per column b; the rows
-// from cnt on are written as zero
-__device__ __forceinline__ void ex_whiten8(const float* raw, float* out, const float* __restrict__ W, int f, int ld, int cnt) {
-    for (int b = threadIdx.x; b < f; b += 256) {
-        float acc[EX_CHUNK];
-#pragma unroll
-        for (int e = 0; e < EX_CHUNK; ++e) acc[e] = 0.f;
-        for (int a = 0; a <= b; ++a) {
-            const float wv = W[(int64_t)a * ld + b];
-#pragma unroll
-            for (int e = 0; e < EX_CHUNK; ++e) acc[e] = fmaf(raw[e * f + a], wv, acc[e]);
-        }
-#pragma unroll
-        for (int e = 0; e < EX_CHUNK; ++e) out[e * f + b] = e < cnt ? acc[e] : 0.f;
-    }
-}
-
-// row `src` of the fixed side with column 0 read as 1 (bias), or zeros (src == NULL), into f floats of LDS: the 16 lanes of a group
-__device__ __forceinline__ void ex_load_row(const float* __restrict__ src, float* dst, int f, int bias, int g) {
-    for (int a = g; a < f; a += 16) dst[a] = !src ? 0.f : (bias && a == 0) ? 1.f : src[a];
-}
 
 __global__ __launch_bounds__(256) void explain_kernel(const float* __restrict__ Y, int f, int ld, int bias, const float* __restrict__ W,
                                                       const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,

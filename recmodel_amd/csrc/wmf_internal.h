@@ -220,6 +220,10 @@ int64_t wmf_explain_ws_bytes(int64_t n, int f, int32_t n_targets);
 int wmf_launch_explain(const float* Y, int f, int ld, int bias, const float* W, const int64_t* indptr, const int32_t* indices,
                        const float* values, int64_t n, const int32_t* targets, int n_targets, float* out_contrib, float* out_total,
                        int32_t* fail_count, hipStream_t st);
+// wmf_foldin.hip: the folded-in factors of a row's history (the x_u whose scores wmf_explain.hip splits up)
+int64_t wmf_foldin_ws_bytes(int64_t n, int f);
+int wmf_launch_foldin(const float* Y, int f, int ld, int bias, const float* W, const int64_t* indptr, const int32_t* indices,
+                      const float* values, int64_t n, float* X_out, int32_t* fail_count, hipStream_t st);
 int wmf_launch_predict(const float* users, const float* items, int f, int ld, int bias, const int32_t* ui, int64_t n_u,
                        const int32_t* ii, int64_t n_i, float* out, hipStream_t st);
 int wmf_launch_hits(const float* users, const float* items, int ld, int bias, const int32_t* pair_user,

@@ -666,6 +666,95 @@ class WMF(RecModel):
                     _ptr(tg_d[b0:]), tc, _ptr(contrib_d), _ptr(total_d[b0:]), _ptr(fail), *ws))
             contrib[:, t0: t0 + tc] = got[:len(counts)]
 
+    # ------------------------------------------------------------------ a16: fold_in, recommend_for
+    def fold_in(self, count_rows, alpha=10, beta=1, pre_process_count='log'):
+        """The factors of histories that need not be rows of the model: for each row of ``count_rows`` -- a SciPy sparse matrix
+        of shape [B, items] for any B, e.g. the counts of new visitors, or of known users whose history has changed since
+        ``train`` -- the row a user half step would give it against the model's items,
+        ``recompute_factors[_bias](items, C, gamma)`` (wmf_model.py:213-240 / :311-351).  The rows are read as stored (stored
+        zeros, duplicates and their order are kept) and transformed on the device as ``train`` transforms them
+        (wmf_model.py:119-123).  Returns float32 [B, f], a block of rows of ``users``: with a bias model column 0 is the row's own
+        bias.  An empty row gives zeros; a row whose system is not positive definite (effective weights <= -1) gives NaN.  One
+        workgroup per row on the device (wmf_foldin_rows), from the whitening ``explain`` keeps: neither a whitened copy of the
+        catalogue nor a plan is made.  A float64 model is served from its float32 copies, as ``recommend`` is."""
+        mat, mode = self._foldin_arguments(count_rows, pre_process_count)
+        f = self.items.shape[1]
+        _lib.require_gpu()
+        if mat.shape[0] == 0:
+            return np.zeros((0, f), dtype=np.float32)
+        X_d = self._fold_in_device(mat, alpha, beta, mode)[0]
+        return np.ascontiguousarray(X_d[:, :f].cpu().numpy())
+
+    def recommend_for(self, count_rows, topn=10, exclude_history=True, return_scores=False, alpha=10, beta=1,
+                      pre_process_count='log'):
+        """``recommend`` for histories instead of user ids: the rows of ``count_rows`` ([B, items], as for ``fold_in``) are
+        folded in and the ``topn`` best items of the whole catalogue are found for each, best first, equal scores in item order;
+        the factors never leave the device.  ``exclude_history``: the stored entries of a row (stored zeros too) are not
+        recommended to it.  Returns int64 [B, topn], padded with -1 where a row has fewer eligible items; with ``return_scores``
+        also the float32 scores, padded with -inf -- the items and scores of ``recommend`` on a model whose ``users`` are
+        ``fold_in(count_rows)``, bit for bit.  A row whose fold-in failed (NaN factors) is all -1 / -inf.  ``topn`` is at most
+        RECOMMEND_MAX_TOPN: a larger one is a ValueError."""
+        mat, mode = self._foldin_arguments(count_rows, pre_process_count)
+        topn = int(topn)
+        if topn < 1 or topn > RECOMMEND_MAX_TOPN:
+            raise ValueError(f"topn must be between 1 and {RECOMMEND_MAX_TOPN}, not {topn}")
+        _lib.require_gpu()
+        B = mat.shape[0]
+        out_items = np.full((B, topn), -1, dtype=np.int64)
+        out_scores = np.full((B, topn), -np.inf, dtype=np.float32)
+        if B:
+            X_d, items_t, f, ld = self._fold_in_device(mat, alpha, beta, mode)
+            seen = None
+            if exclude_history:
+                seen = mat.copy()                                  # the seen list as ``recommend`` prepares ``exclude``
+                seen.sort_indices()
+            lib = _lib.load()
+            items_d = torch.empty(B, topn, dtype=torch.int32, device="cuda")
+            scores_d = torch.empty(B, topn, dtype=torch.float32, device="cuda") if return_scores else None
+            got_items, got_scores = self._scan_batches(
+                np.arange(B, dtype=np.int64), [None if seen is None else (seen.indptr, seen.indices)],
+                lambda rows: lib.wmf_recommend_workspace_bytes(rows, topn, 0), [items_d, scores_d],
+                lambda b0, nb, ids, csrs, *ws: lib.wmf_recommend_topn(
+                    _ptr(X_d), _ptr(items_t), f, ld, int(self.bias is True), ids, nb, self.items.shape[0], *csrs[0], topn, 0,
+                    _ptr(items_d[b0:]), _ptr(scores_d[b0:]) if scores_d is not None else None, None, *ws))
+            good = ~torch.isnan(X_d[:, :f]).any(dim=1).cpu().numpy()
+            out_items[good] = got_items[good]
+            if return_scores:
+                out_scores[good] = got_scores[good]
+        return (out_items, out_scores) if return_scores else out_items
+
+    def _foldin_arguments(self, count_rows, pre_process_count):
+        """The checks ``fold_in`` and ``recommend_for`` share, before the GPU is asked for; returns (the rows as CSR, as stored, and
+        the transform's mode)."""
+        if self.weighted is not True:
+            raise ValueError("folding a history in is the half step of the weighted branch (weighted=True)")
+        if pre_process_count not in ('log', 'linear'):
+            raise ValueError(f"Pre_process_count {pre_process_count} is not implement please use log or linear.")
+        if self.items is None or self.users is None:               # (the device copies are of both matrices; as in explain)
+            raise ValueError("the model has no factors yet: train it, or assign users and items, before folding histories in")
+        n_items = self.items.shape[0]
+        if not scipy.sparse.issparse(count_rows) or count_rows.ndim != 2 or count_rows.shape[1] != n_items:
+            raise ValueError(f"count_rows must be a sparse matrix of shape [B, {n_items}], got {getattr(count_rows, 'shape', None)}")
+        mat = count_rows if scipy.sparse.isspmatrix_csr(count_rows) else scipy.sparse.csr_matrix(count_rows)
+        return mat, 0 if pre_process_count == 'log' else 1
+
+    def _fold_in_device(self, mat, alpha, beta, mode):
+        """wmf_foldin_rows in batches of rows (_scan_batches) on the rows of the CSR ``mat`` (at least one).  Returns (the folded
+        block [B, ld] on the device in the library's layout, items_t, f, ld)."""
+        users_t, items_t, f, ld, W_white = self._device_whitening()
+        lib = _lib.load()
+        B = mat.shape[0]
+        vals = torch.from_numpy(np.append(np.asarray(mat.data, dtype=np.float32), np.float32(0))).cuda()   # (one spare element: never empty)
+        _lib.check(lib.wmf_confidence_transform(_ptr(vals), len(mat.data), float(alpha), float(beta), mode, _stream()))
+        fail = torch.zeros(1, dtype=torch.int32, device="cuda")
+        X_d = torch.empty(B, ld, dtype=torch.float32, device="cuda")
+        self._scan_batches(
+            np.arange(B, dtype=np.int64), [(mat.indptr, mat.indices)], lambda rows: lib.wmf_foldin_workspace_bytes(rows, f), [],
+            lambda b0, nb, ids, csrs, *ws: lib.wmf_foldin_rows(
+                _ptr(items_t), items_t.shape[0], f, ld, int(self.bias is True), _ptr(W_white), *csrs[0], _ptr(vals), nb,
+                _ptr(X_d[b0:]), _ptr(fail), *ws))
+        return X_d, items_t, f, ld
+
     # ------------------------------------------------------------------ a3 / a4: operator seam
     def recompute_factors(self, Y, C, lambda_reg):
         """X_new for fixed factors Y and CSR C.  wmf_model.py:213-240 (host buffers in, host out)."""
