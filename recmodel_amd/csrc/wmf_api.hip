@@ -716,6 +716,36 @@ int wmf_recommend_topn(const float* users, const float* items, int f, int ld, in
                         "wmf_recommend_topn", f, ld, "");
 }
 
+// what a call's filter arguments break, or NULL (check_scan_call's `own`); n_items: the catalogue the mask covers
+static const char* filter_refusal(const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks, const int32_t* allow_idx, int64_t n_items,
+                                  const int32_t* cand_idx, int64_t n_cand) {
+    if (allow_bits && cand_idx) return "allow_bits and cand_idx: one form per call";
+    if (allow_bits && (n_masks < 1 || n_items < 1 || allow_words < (n_items + 31) / 32)) return "need n_masks >= 1 and allow_words >= ceil(n_items / 32)";
+    if (!allow_bits && allow_idx) return "allow_idx without allow_bits";
+    if (cand_idx && (n_cand < 1 || n_cand > n_items)) return "need 1 <= n_cand <= n_items";
+    return nullptr;
+}
+
+int wmf_recommend_topn_filtered(const float* users, const float* items, int f, int ld, int bias, const int32_t* user_idx, int64_t n_users,
+                                int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* allow_bits,
+                                int64_t allow_words, int32_t n_masks, const int32_t* allow_idx, const int32_t* cand_idx, int64_t n_cand,
+                                int64_t topn, int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+    int rc = check_shape(f, ld);
+    if (rc) return rc;
+    const char* own = filter_refusal(allow_bits, allow_words, n_masks, allow_idx, n_items, cand_idx, n_cand);
+    if ((rc = check_scan_call("wmf_recommend_topn_filtered", users, items, user_idx, out_items, workspace, "null pointer", own, "n_users", n_users,
+                              "n_items", n_items, &topn, n_slices, workspace_bytes, [&] { return wmf_recommend_ws_bytes(n_users, topn, n_slices); }))) return rc;
+    if (!allow_bits && !cand_idx)                                  // neither form: wmf_recommend_topn
+        return launch_error(wmf_launch_recommend(users, items, ld, bias, user_idx, n_users, n_items, seen_indptr, seen_indices, topn, n_slices,
+                                                 out_items, out_scores, out_count, workspace, (hipStream_t)stream),
+                            "wmf_recommend_topn_filtered", f, ld, "");
+    return launch_error(wmf_launch_recommend_filtered(users, items, ld, bias, user_idx, n_users, n_items, seen_indptr, seen_indices, allow_bits,
+                                                      allow_words, allow_idx, cand_idx, n_cand, topn, n_slices, out_items, out_scores, out_count,
+                                                      workspace, (hipStream_t)stream),
+                        "wmf_recommend_topn_filtered", f, ld, "");
+}
+
 int wmf_row_inv_norms(const float* M, int64_t n, int f, int ld, int bias, float* out, void* stream) {
     int rc = check_shape(f, ld);
     if (rc) return rc;
@@ -741,6 +771,30 @@ int wmf_similar_topn(const float* queries, const float* catalogue, int f, int ld
                                            excl_indptr, excl_indices, topn, n_slices, out_rows, out_scores, out_count, workspace,
                                            (hipStream_t)stream),
                         "wmf_similar_topn", f, ld, "");
+}
+
+int wmf_similar_topn_filtered(const float* queries, const float* catalogue, int f, int ld, int bias, const float* q_inv_norm,
+                              const float* c_inv_norm, const int32_t* query_idx, int64_t n_queries, int64_t n_rows, int32_t exclude_self,
+                              const int64_t* excl_indptr, const int32_t* excl_indices, const uint32_t* allow_bits, int64_t allow_words,
+                              int32_t n_masks, const int32_t* allow_idx, int64_t topn, int32_t n_slices, int32_t* out_rows, float* out_scores,
+                              int32_t* out_count, void* workspace, int64_t workspace_bytes, void* stream) {
+    int rc = check_shape(f, ld);
+    if (rc) return rc;
+    const char* own = (!q_inv_norm != !c_inv_norm || !excl_indptr != !excl_indices)
+                          ? "q_inv_norm and c_inv_norm, excl_indptr and excl_indices: both or neither"
+                          : filter_refusal(allow_bits, allow_words, n_masks, allow_idx, n_rows, nullptr, 0);
+    if ((rc = check_scan_call("wmf_similar_topn_filtered", queries, catalogue, query_idx, out_rows, workspace, "null pointer", own, "n_queries",
+                              n_queries, "n_rows", n_rows, &topn, n_slices, workspace_bytes,
+                              [&] { return wmf_recommend_ws_bytes(n_queries, topn, n_slices); }))) return rc;
+    if (!allow_bits)                                               // no mask: wmf_similar_topn
+        return launch_error(wmf_launch_similar(queries, catalogue, ld, bias, q_inv_norm, c_inv_norm, query_idx, n_queries, n_rows, exclude_self,
+                                               excl_indptr, excl_indices, topn, n_slices, out_rows, out_scores, out_count, workspace,
+                                               (hipStream_t)stream),
+                            "wmf_similar_topn_filtered", f, ld, "");
+    return launch_error(wmf_launch_similar_filtered(queries, catalogue, ld, bias, q_inv_norm, c_inv_norm, query_idx, n_queries, n_rows,
+                                                    exclude_self, excl_indptr, excl_indices, allow_bits, allow_words, allow_idx, topn, n_slices,
+                                                    out_rows, out_scores, out_count, workspace, (hipStream_t)stream),
+                        "wmf_similar_topn_filtered", f, ld, "");
 }
 
 int64_t wmf_rank_positions_workspace_bytes(int64_t n_rows, int64_t n_targets, int32_t n_slices) {

@@ -240,6 +240,11 @@ int64_t wmf_recommend_ws_bytes(int64_t n_users, int64_t topn, int32_t n_slices);
 int wmf_launch_recommend(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
                          int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, int64_t topn, int32_t n_slices,
                          int32_t* out_items, float* out_scores, int32_t* out_count, void* ws, hipStream_t st);
+// (... restricted by allow masks, or to a list of candidate rows: exactly one of allow_bits and cand_idx is given)
+int wmf_launch_recommend_filtered(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
+                                  int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* allow_bits,
+                                  int64_t allow_words, const int32_t* allow_idx, const int32_t* cand_idx, int64_t n_cand, int64_t topn,
+                                  int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* ws, hipStream_t st);
 // (the sorted partial lists of a scan with the top-n epilogue of wmf_topn.h, n_slices a row, merged into the outputs)
 void wmf_launch_topn_merge(const unsigned long long* partial, int64_t n_rows, int n_slices, int topn, int32_t* out_rows, float* out_scores,
                            int32_t* out_count, hipStream_t st);
@@ -251,6 +256,11 @@ int wmf_launch_similar(const float* queries, const float* catalogue, int ld, int
                        const int32_t* query_idx, int64_t n_queries, int64_t n_rows, int exclude_self, const int64_t* excl_indptr,
                        const int32_t* excl_indices, int64_t topn, int32_t n_slices, int32_t* out_rows, float* out_scores,
                        int32_t* out_count, void* ws, hipStream_t st);
+int wmf_launch_similar_filtered(const float* queries, const float* catalogue, int ld, int bias, const float* q_inv_norm, const float* c_inv_norm,
+                                const int32_t* query_idx, int64_t n_queries, int64_t n_rows, int exclude_self, const int64_t* excl_indptr,
+                                const int32_t* excl_indices, const uint32_t* allow_bits, int64_t allow_words, const int32_t* allow_idx,
+                                int64_t topn, int32_t n_slices, int32_t* out_rows, float* out_scores, int32_t* out_count, void* ws,
+                                hipStream_t st);
 // wmf_rankpos.hip: exact full-catalogue ranks of target items, seen items left out
 int64_t wmf_rank_positions_ws_bytes(int64_t n_rows);
 int wmf_launch_rank_positions(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_rows,

@@ -36,6 +36,28 @@ __global__ __launch_bounds__(64 * NW) void recommend_scan_kernel(const float* __
     wmf_catalogue_scan<NIT, TPS, NW>(users, items, ld, bias, user_idx, n_users, n_items, n_slices, tiles_per_slice, n_work, p);
 }
 
+// The filtered scans.  GATHER false, the mask form: the whole catalogue, an item inserted only where the row's allow mask has its
+// bit (RecTopN's MASK).  GATHER true, the list form: the positions of cand_idx (n_items of them) instead of the catalogue, keys and
+// seen lookups by the real id.  Either scores in the arithmetic of recommend_scan_kernel: a score does not depend on the item's
+// place in a tile, so both give the bits of that kernel with the ineligible items appended to every seen row.
+template <int NIT, int TPS, int NW, bool GATHER>
+__global__ __launch_bounds__(64 * NW) void recommend_scan_filtered_kernel(const float* __restrict__ users, const float* __restrict__ items, int ld,
+                                                                          int bias, const int32_t* __restrict__ user_idx, int64_t n_users,
+                                                                          int64_t n_items, const int64_t* __restrict__ seen_indptr,
+                                                                          const int32_t* __restrict__ seen_indices,
+                                                                          const uint32_t* __restrict__ allow_bits, int64_t allow_words,
+                                                                          const int32_t* __restrict__ allow_idx,
+                                                                          const int32_t* __restrict__ cand_idx, int topn, int cap, int n_slices,
+                                                                          int64_t tiles_per_slice, int64_t n_work,
+                                                                          unsigned long long* __restrict__ partial) {
+    extern __shared__ __align__(16) unsigned char wmf_scan_smem[];
+    RecTopN<NW, false, !GATHER> p{seen_indptr, seen_indices, n_users, topn, cap, n_slices, partial};
+    p.allow_bits = allow_bits; p.allow_words = allow_words; p.allow_idx = allow_idx;
+    wmf_catalogue_scan<NIT, TPS, NW, decltype(p), WmfModelScore, GATHER>(
+        users, items, ld, bias, user_idx, n_users, n_items, n_slices, tiles_per_slice, n_work, p, WmfModelScore(), cand_idx,
+        reinterpret_cast<int32_t*>(wmf_scan_smem + wmf_scan_stage_bytes(TPS, ld) + rec_lds_bytes(NW, cap)));
+}
+
 // keys of `list` (topn of them, descending, 0 = none) above `key`
 __device__ __forceinline__ int rec_count_above(const unsigned long long* __restrict__ list, int topn, unsigned long long key) {
     int lo = 0, hi = topn;
@@ -118,6 +140,39 @@ int wmf_launch_recommend(const float* users, const float* items, int ld, int bia
             WMF_LAUNCH_LDS(name, (recommend_scan_kernel<NIT, TPS, NW>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW),
                            wmf_scan_stage_bytes(TPS, ld) + rec_lds_bytes(NW, cap), st, a.users, a.items, a.ld, a.bias, a.user_idx, a.n_rows,
                            a.n_items, seen_indptr, seen_indices, n, cap, a.n_slices, a.tiles_per_slice, a.n_work, partial);
+            return (int)WMF_L_OK;
+        });
+    });
+    if (rc) return rc;
+    wmf_launch_topn_merge(partial, n_users, a.n_slices, n, out_items, out_scores, out_count, st);
+    return WMF_L_OK;
+}
+
+// allow_bits: the mask form; cand_idx: the list form (slices and tiles are cut from the n_cand positions); exactly one of the two
+int wmf_launch_recommend_filtered(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
+                                  int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* allow_bits,
+                                  int64_t allow_words, const int32_t* allow_idx, const int32_t* cand_idx, int64_t n_cand, int64_t topn,
+                                  int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* ws, hipStream_t st) {
+    const int64_t n_scan = cand_idx ? n_cand : n_items;
+    WmfScanArgs a = {users, items, ld, bias, user_idx, n_users, n_scan, wmf_recommend_slices(n_users, n_scan, topn, n_slices), st};
+    unsigned long long* partial = reinterpret_cast<unsigned long long*>(ws);
+    const int n = (int)topn, cap = rec_cap(topn);
+    const int rc = wmf_dispatch_scan(ld, [&](auto nit, auto tps) {
+        return wmf_dispatch_list<4, 2>(rec_waves(topn), [&](auto nw) {
+            constexpr int NIT = decltype(nit)::value, TPS = decltype(tps)::value, NW = decltype(nw)::value;
+            wmf_scan_geometry(a, NW);
+            const size_t lds = wmf_scan_stage_bytes(TPS, ld) + rec_lds_bytes(NW, cap);
+            if (cand_idx) {
+                static const char* name = wmf_kname("recommend_scan_list_kernel<%d, %d, %d>", NIT, TPS, NW);
+                WMF_LAUNCH_LDS(name, (recommend_scan_filtered_kernel<NIT, TPS, NW, true>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW),
+                               lds + (size_t)2 * TPS * 16 * 4, st, a.users, a.items, a.ld, a.bias, a.user_idx, a.n_rows, a.n_items, seen_indptr,
+                               seen_indices, nullptr, (int64_t)0, nullptr, cand_idx, n, cap, a.n_slices, a.tiles_per_slice, a.n_work, partial);
+            } else {
+                static const char* name = wmf_kname("recommend_scan_mask_kernel<%d, %d, %d>", NIT, TPS, NW);
+                WMF_LAUNCH_LDS(name, (recommend_scan_filtered_kernel<NIT, TPS, NW, false>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW),
+                               lds, st, a.users, a.items, a.ld, a.bias, a.user_idx, a.n_rows, a.n_items, seen_indptr, seen_indices, allow_bits,
+                               allow_words, allow_idx, nullptr, n, cap, a.n_slices, a.tiles_per_slice, a.n_work, partial);
+            }
             return (int)WMF_L_OK;
         });
     });

@@ -68,7 +68,8 @@ __device__ __forceinline__ float wmf_diag_score(const float4* __restrict__ urow,
 //   p.begin(lds, u0, sl)                  a unit starts: lds = the dynamic LDS past the stages, u0 = the wave's first batch position
 //                                         (waves past the batch are called too), sl = the slice
 //   p.score(reg, j, item, key, in_range)  the key of (row u0 + 4 q + reg, item = 16 tile + r) of the stage's j-th tile; in_range:
-//                                         the item exists (a row past the batch is a copy of the last one)
+//                                         the item exists (a row past the batch is a copy of the last one); with GATHER item is
+//                                         the id of list position 16 tile + r, and the key is built from that id
 //   p.tile(j)                             the four scores of the j-th tile are out
 //   p.end()                               the slice is done; score, tile and end only in waves with u0 < n_rows
 __host__ __device__ static inline size_t wmf_scan_stage_bytes(int tps, int ld) { return (size_t)2 * tps * 16 * ((ld >> 2) | 1) * 16; }
@@ -83,10 +84,16 @@ __host__ __device__ static inline size_t wmf_scan_stage_bytes(int tps, int ld) {
 //   s.score(acc, rs, is)                        the score
 struct WmfModelScore { static constexpr bool SCALED = false; };
 
-template <int NIT, int TPS, int NW, class P, class S = WmfModelScore>
+// GATHER: the scan walks a LIST of catalogue rows instead of [0, n_items): n_items is the length of the list, position p stands for
+// row cand_idx[p] (strictly ascending ids), and tiles and slices are cut from the positions.  The ids of a stage's 16 TPS positions
+// travel with the stage like the scaled score's scales -- requested with its global loads, stored with its rows to cand_lds (two
+// stages of TPS x 16 ids, which the kernel places) -- so the key and the policy get the real id from LDS.
+template <int NIT, int TPS, int NW, class P, class S = WmfModelScore, bool GATHER = false>
 __device__ __forceinline__ void wmf_catalogue_scan(const float* __restrict__ users, const float* __restrict__ items, int ld, int bias,
                                                    const int32_t* __restrict__ user_idx, int64_t n_rows, int64_t n_items, int n_slices,
-                                                   int64_t tiles_per_slice, int64_t n_work, P& p, S sp = S()) {
+                                                   int64_t tiles_per_slice, int64_t n_work, P& p, S sp = S(),
+                                                   const int32_t* __restrict__ cand_idx = nullptr, int32_t* cand_lds = nullptr) {
+    static_assert(!GATHER || TPS * 16 <= 64 * NW, "one thread per candidate id of a stage");
     extern __shared__ __align__(16) unsigned char wmf_scan_smem[];
     constexpr int PRE = (TPS * NIT + NW - 1) / NW;                // 16-byte pieces of a stage per thread
     const int tid = threadIdx.x;
@@ -137,19 +144,27 @@ __device__ __forceinline__ void wmf_catalogue_scan(const float* __restrict__ use
         // the next stage on its way: plain unrolled loops that write every element (as lambdas with a skipped element the
         // array was kept in scratch)
         float4 pre[PRE];
+        int32_t cand_pre = 0;                                      // (GATHER) this thread's id of the stage on its way (threads < 16 TPS)
 #define WMF_SCAN_LOAD_STAGE(TILE_FIRST)                                                                                       \
     {                                                                                                                         \
         _Pragma("unroll") for (int k = 0; k < PRE; ++k) {                                                                     \
-            const int64_t gi = min(16 * (TILE_FIRST) + (pk[k] >> 8), n_items - 1);   /* clamped: the scores are masked */      \
+            int64_t gi = min(16 * (TILE_FIRST) + (pk[k] >> 8), n_items - 1);         /* clamped: the scores are masked */      \
+            if constexpr (GATHER) gi = pk[k] >= 0 ? cand_idx[gi] : 0;                                                         \
             pre[k] = pk[k] >= 0 ? items4[gi * nch + (pk[k] & 255)] : make_float4(0.f, 0.f, 0.f, 0.f);                          \
         }                                                                                                                     \
         if constexpr (S::SCALED) sp.load(TILE_FIRST, n_items);                                                                \
+        if constexpr (GATHER) {                                                                                               \
+            if (tid < TPS * 16) cand_pre = cand_idx[min(16 * (TILE_FIRST) + (int64_t)tid, n_items - 1)];                      \
+        }                                                                                                                     \
     }
 #define WMF_SCAN_STORE_STAGE(BUF)                                                                                             \
     {                                                                                                                         \
         _Pragma("unroll") for (int k = 0; k < PRE; ++k)                                                                       \
             if (pk[k] >= 0) stage[(BUF) * stage_f4 + (pk[k] >> 8) * stride + (pk[k] & 255)] = pre[k];                         \
         if constexpr (S::SCALED) sp.store(BUF);                                                                               \
+        if constexpr (GATHER) {                                                                                               \
+            if (tid < TPS * 16) cand_lds[(BUF) * TPS * 16 + tid] = cand_pre;                                                  \
+        }                                                                                                                     \
     }
 
         if (n_st > 0) { WMF_SCAN_LOAD_STAGE(t0) WMF_SCAN_STORE_STAGE(0) }
@@ -186,14 +201,16 @@ __device__ __forceinline__ void wmf_catalogue_scan(const float* __restrict__ use
 #pragma unroll
                 for (int j = 0; j < TPS; ++j) {
                     if (tile_first + j < t1) {
-                        const int64_t item = 16 * (tile_first + j) + r;
+                        const int64_t pos = 16 * (tile_first + j) + r;
+                        int64_t item = pos;
+                        if constexpr (GATHER) item = cand_lds[(int)(s & 1) * TPS * 16 + 16 * j + r];
                         float ibr;
                         if constexpr (S::SCALED) ibr = sp.item(r, (int)(s & 1), j); else ibr = __shfl(ibv[j], r);
 #pragma unroll
                         for (int reg = 0; reg < 4; ++reg) {
                             float sc;
                             if constexpr (S::SCALED) sc = sp.score(acc[j][reg], ubr[reg], ibr); else sc = acc[j][reg] + (bias ? ubr[reg] + ibr : 0.f);
-                            p.score(reg, j, item, wmf_item_key(sc, item), item < n_items);
+                            p.score(reg, j, item, wmf_item_key(sc, item), pos < n_items);
                         }
                         p.tile(j);
                     }

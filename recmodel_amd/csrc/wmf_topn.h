@@ -42,7 +42,10 @@ __device__ __forceinline__ void rec_compact(unsigned mask, unsigned long long* _
 // The scan's epilogue: a running top-n per user.  LDS past the stages: [keys: 16 users x cap per wave][thresholds][counts].
 // partial[(b * n_slices + slice) * topn + k]: the k-th best key of batch position b in that slice, 0 = none.
 // SELF: the row's own id (self_idx[b], the catalogue row that batch position b is) is never inserted; self_idx == NULL: no such row.
-template <int NW, bool SELF = false>
+// MASK: an allow mask per row, allow_bits[allow_idx[b]][allow_words] (allow_idx == NULL: mask 0 for every row; allow_idx[b] == -1:
+// row b has none): item j may be inserted only when bit j & 31 of word j >> 5 is set.  Tested at insertion, after the threshold and
+// before the seen list (one load against the search's twenty): a masked-out item never enters a buffer or raises a threshold.
+template <int NW, bool SELF = false, bool MASK = false>
 struct RecTopN {
     const int64_t* __restrict__ seen_indptr; const int32_t* __restrict__ seen_indices;
     int64_t n_users; int topn, cap, n_slices;
@@ -54,6 +57,9 @@ struct RecTopN {
     unsigned long long thr[4];
     int64_t seen_lo[4], seen_hi[4];
     int32_t self[4];
+    // (MASK; set by the kernel after the aggregate's members above, and dead without MASK like self[])
+    const uint32_t* __restrict__ allow_bits = nullptr; int64_t allow_words = 0; const int32_t* __restrict__ allow_idx = nullptr;
+    const uint32_t* words[4];
 
     __device__ __forceinline__ void begin(unsigned char* lds, int64_t u0_, int sl_) {
         u0 = u0_; sl = sl_;
@@ -67,6 +73,10 @@ struct RecTopN {
             const int64_t b = u0 + 4 * q + reg;
             if (seen_indptr && b < n_users) { seen_lo[reg] = seen_indptr[b]; seen_hi[reg] = seen_indptr[b + 1]; }
             if constexpr (SELF) self[reg] = (self_idx && b < n_users) ? self_idx[b] : -1;
+            if constexpr (MASK) {
+                const int32_t g = b < n_users ? (allow_idx ? allow_idx[b] : 0) : -1;
+                words[reg] = g >= 0 ? allow_bits + (int64_t)g * allow_words : nullptr;
+            }
         }
         wmf_wave_sync();
     }
@@ -74,6 +84,9 @@ struct RecTopN {
     __device__ __forceinline__ void score(int reg, int, int64_t item, unsigned long long key, bool in_range) {
         bool take = in_range && u0 + 4 * q + reg < n_users && key > thr[reg];
         if constexpr (SELF) take = take && (int32_t)item != self[reg];
+        if constexpr (MASK) {
+            if (take && words[reg]) take = (words[reg][item >> 5] >> (item & 31)) & 1u;
+        }
         if (take && seen_lo[reg] < seen_hi[reg]) {
             int64_t lo = seen_lo[reg], hi = seen_hi[reg];
             while (lo < hi) {                                      // first entry >= item

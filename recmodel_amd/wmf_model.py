@@ -46,6 +46,80 @@ def _wrapped_ids(ids, n, what, dtype=np.int32):
     return np.where(ids < 0, ids + n, ids).astype(dtype)
 
 
+def pack_allow_masks(masks):
+    """bool [G, n] as the allow masks of include/wmf_hip.h: uint32 [G, ceil(n / 32)], item j is bit j & 31 of word j >> 5."""
+    masks = np.atleast_2d(np.asarray(masks, dtype=bool))
+    padded = np.zeros((masks.shape[0], 32 * max(1, (masks.shape[1] + 31) // 32)), dtype=bool)
+    padded[:, :masks.shape[1]] = masks
+    return np.ascontiguousarray(np.packbits(padded, axis=1, bitorder='little')).view('<u4').astype(np.uint32, copy=False)
+
+
+class _Allow:
+    """The ``allow`` / ``allow_idx`` arguments of the fused catalogue calls, checked on the host (every error a ValueError, before
+    the GPU is asked for).  ``ids``: the list form (int32, sorted, unique; may be empty), or None; ``masks`` (bool [G, n]) and ``idx``
+    (int32 per batch position, or None: mask 0 everywhere): the mask form.  ``as_mask``: an id list becomes its indicator mask."""
+
+    def __init__(self, allow, allow_idx, n, n_batch, what, as_mask=False):
+        self.n, self.ids, self.masks, self.idx = n, None, None, None
+        if allow is None:
+            raise ValueError("allow_idx needs a 2-D allow (one mask per row of it)")
+        a = np.asarray(allow)
+        if a.dtype == bool and a.ndim == 1:
+            if allow_idx is not None:
+                raise ValueError("allow_idx needs a 2-D allow (one mask per row of it); a 1-D mask is every row's")
+            if len(a) != n:
+                raise ValueError(f"a bool allow has one entry per {what} ({n}), not {len(a)}")
+            self.masks = a[None, :]
+        elif a.dtype == bool and a.ndim == 2:
+            if a.shape[1] != n or a.shape[0] < 1:
+                raise ValueError(f"a 2-D allow is [G >= 1, {n}] (one entry per {what}), not {a.shape}")
+            if allow_idx is None:
+                raise ValueError("a 2-D allow needs allow_idx: the mask of every batch position (-1: none)")
+            idx = np.asarray(allow_idx)
+            if idx.dtype == bool or not np.issubdtype(idx.dtype, np.integer) or idx.ndim != 1:
+                raise ValueError("allow_idx must be a 1-D integer array")
+            if len(idx) != n_batch:
+                raise ValueError(f"allow_idx has one entry per batch position ({n_batch}), not {len(idx)}")
+            if len(idx) and (idx.min() < -1 or idx.max() >= a.shape[0]):
+                raise ValueError(f"allow_idx must lie in [-1, {a.shape[0]})")
+            self.masks, self.idx = a, idx.astype(np.int32)
+        elif a.ndim == 1 and (np.issubdtype(a.dtype, np.integer) or a.size == 0):
+            if allow_idx is not None:
+                raise ValueError("allow_idx needs a 2-D allow (one mask per row of it), not a list of ids")
+            a = a.astype(np.int64)
+            if len(a) and (a.min() < -n or a.max() >= n):
+                raise ValueError(f"allow holds an id outside [-{n}, {n})")
+            self.ids = np.unique(np.where(a < 0, a + n, a)).astype(np.int32)
+            if as_mask and len(self.ids):
+                self.masks = np.zeros((1, n), dtype=bool)
+                self.masks[0, self.ids] = True
+                self.ids = None
+        else:
+            raise ValueError("allow must be a 1-D bool mask, a 1-D integer array of ids, or a 2-D bool array with allow_idx")
+
+    @property
+    def empty(self):
+        return self.ids is not None and len(self.ids) == 0
+
+    def allowed(self, b):
+        """The eligible ids of batch position b, ascending."""
+        if self.ids is not None:
+            return self.ids
+        g = 0 if self.idx is None else self.idx[b]
+        return np.arange(self.n, dtype=np.int32) if g < 0 else np.flatnonzero(self.masks[g]).astype(np.int32)
+
+    def upload(self):
+        """The device arrays, made once per call.  Returns at(b0): the filter arguments of a C call whose batch starts at b0 --
+        (allow_bits, allow_words, n_masks, allow_idx, cand_idx, n_cand)."""
+        if self.ids is not None:
+            cand = torch.from_numpy(self.ids).cuda()
+            return lambda b0: (None, 0, 0, None, _ptr(cand), len(self.ids))
+        bits = pack_allow_masks(self.masks)
+        bits_d = torch.from_numpy(bits.view(np.int32)).cuda()
+        idx_d = None if self.idx is None else torch.from_numpy(self.idx).cuda()
+        return lambda b0: (_ptr(bits_d), bits.shape[1], bits.shape[0], None if idx_d is None else _ptr(idx_d[b0:]), None, 0)
+
+
 def _transformed_dtype(count_dtype, alpha, beta, pre_process_count):
     """dtype of the confidence weights the reference ends up with (wmf_model.py:119-123), by NumPy's own rules."""
     probe = np.ones(1, dtype=count_dtype)
@@ -265,14 +339,26 @@ class WMF(RecModel):
         return out
 
     # ------------------------------------------------------------------ a11: recommend
-    def recommend(self, users, topn=10, exclude=None, return_scores=False):
+    def recommend(self, users, topn=10, exclude=None, return_scores=False, allow=None, allow_idx=None):
         """The ``topn`` best items of the whole catalogue for each of ``users`` (an int or a sequence of ints; negative
         indices count from the end, as in ``predict``), best first, equal scores in item order.  ``exclude``: a SciPy sparse
         matrix of shape [users of the model, items], e.g. the training matrix -- the stored entries of a user's row (stored
         zeros too) are never recommended to that user.  This is ``rank(np.delete(arange(n_items), seen_u), u, topn)`` for every
         user (RecModel/utils.py:3-17 on wmf_model.py:25-47) in one fused device pass per batch (wmf_recommend_topn).
         Returns int64 [len(users), topn], padded with -1 where a user has fewer eligible items; with ``return_scores`` also
-        the float32 scores, padded with -inf.  An int user gives one row."""
+        the float32 scores, padded with -inf.  An int user gives one row.
+        ``allow`` restricts the catalogue (in stock, licensed, on a shelf); the form follows the argument, nothing is routed:
+        a 1-D bool array of length items is one MASK for every row -- the whole catalogue is scored and the bit is tested where an
+        item would enter a row's top-n (wmf_recommend_topn_filtered, mask form); a 1-D integer array of ids (any order,
+        duplicates allowed, negative ids count from the end) is the LIST form, which reads and scores those rows only, at a cost
+        proportional to ``len(ids)``; a 2-D bool array [G, items] with ``allow_idx`` -- one entry per entry of ``users``, values
+        in [-1, G), -1: unrestricted -- gives every batch position its own mask, and a user may occur several times (the top 10
+        of each of a user's five shelves is one call).  All three return, bit for bit, what ``exclude`` with the ineligible
+        items added to every row returns.  An empty id list gives padding.  Which form: the mask form costs what the unfiltered
+        call costs whatever the filter passes (2048 users, a million items, k = 128 + biases, topn 10 on an MI355X: 10.4 .. 11.4 ms
+        against 11.0 ms, -4 .. +4.5 % on the scan kernel); the list form 0.55 ms for 99 ids, 1.03 ms for 10 000, 9.8 ms for
+        500 000 and 18.2 ms for all million -- the two cross at about 575 000 ids, so a filter that passes more than half of the
+        catalogue is faster as a mask (profiles/r19_recommend_filtered.json)."""
         n_users_model, n_items = self.users.shape[0], self.items.shape[0]
         seen = None
         if exclude is not None:
@@ -283,25 +369,28 @@ class WMF(RecModel):
         topn = int(topn)
         if topn < 1:
             raise ValueError(f"topn must be at least 1, not {topn}")
+        filt = None if allow is None and allow_idx is None else _Allow(allow, allow_idx, n_items, len(u), "item")
         _lib.require_gpu()
         out_items = np.full((len(u), topn), -1, dtype=np.int64)
         out_scores = np.full((len(u), topn), -np.inf, dtype=np.float32)
         if exclude is not None and len(u):
             seen = scipy.sparse.csr_matrix(exclude)[u]            # the requested rows, a copy
             seen.sort_indices()
-        if len(u) == 0:
+        if len(u) == 0 or (filt is not None and filt.empty):
             pass
         elif topn > RECOMMEND_MAX_TOPN:
             # beyond the fused kernel's buffers: the reference's formulation, user by user
             everything = np.arange(n_items, dtype=np.int32)
             for j, user in enumerate(u):
-                cand = everything if seen is None else np.delete(everything, seen.indices[seen.indptr[j]:seen.indptr[j + 1]])
+                cand = everything if filt is None else filt.allowed(j)
+                if seen is not None:
+                    cand = np.setdiff1d(cand, seen.indices[seen.indptr[j]:seen.indptr[j + 1]], assume_unique=False).astype(np.int32)
                 best = self.rank(cand, int(user), topn) if len(cand) else cand
                 out_items[j, :len(best)] = best
                 if return_scores and len(best):
                     out_scores[j, :len(best)] = self.predict([int(user)], best)
         else:
-            self._recommend_fused(u, topn, seen, out_items, out_scores if return_scores else None)
+            self._recommend_fused(u, topn, seen, out_items, out_scores if return_scores else None, filt)
         if one:
             out_items, out_scores = out_items[0], out_scores[0]
         return (out_items, out_scores) if return_scores else out_items
@@ -327,23 +416,37 @@ class WMF(RecModel):
             _lib.check(call(b0, nb, _ptr(ids_d[b0:]), windows, _ptr(ws), nbytes, _stream()))
         return [o if o is None else o.cpu().numpy() for o in outs]
 
-    def _recommend_fused(self, u, topn, seen, out_items, out_scores):
-        """wmf_recommend_topn in batches (_scan_batches); the rows of ``seen`` are those of ``u``."""
+    def _recommend_fused(self, u, topn, seen, out_items, out_scores, filt=None):
+        """wmf_recommend_topn in batches (_scan_batches); the rows of ``seen`` are those of ``u``.  ``filt``: an _Allow, then
+        wmf_recommend_topn_filtered."""
         users_t, items_t, f, ld = self._device_factors()
-        lib = _lib.load()
-        items_d = torch.empty(len(u), topn, dtype=torch.int32, device="cuda")
-        scores_d = torch.empty(len(u), topn, dtype=torch.float32, device="cuda") if out_scores is not None else None
-        out_items[:], scores = self._scan_batches(
-            u, [None if seen is None else (seen.indptr, seen.indices)],
-            lambda rows: lib.wmf_recommend_workspace_bytes(rows, topn, 0), [items_d, scores_d],
-            lambda b0, nb, ids, csrs, *ws: lib.wmf_recommend_topn(
-                _ptr(users_t), _ptr(items_t), f, ld, int(self.bias is True), ids, nb, self.items.shape[0], *csrs[0], topn, 0,
-                _ptr(items_d[b0:]), _ptr(scores_d[b0:]) if scores_d is not None else None, None, *ws))
+        out_items[:], scores = self._recommend_scan(users_t, items_t, f, ld, u, topn, seen, out_scores is not None, filt)
         if out_scores is not None:
             out_scores[:] = scores
 
+    def _recommend_scan(self, users_t, items_t, f, ld, u, topn, seen, want_scores, filt):
+        """The fused top-n of the rows ``u`` of the device matrix ``users_t`` in batches (_scan_batches): wmf_recommend_topn, or with
+        a filter wmf_recommend_topn_filtered -- its masks or ids uploaded once, the allow_idx window moving with the ids'.  Returns
+        the host (items, scores or None)."""
+        lib = _lib.load()
+        items_d = torch.empty(len(u), topn, dtype=torch.int32, device="cuda")
+        scores_d = torch.empty(len(u), topn, dtype=torch.float32, device="cuda") if want_scores else None
+        head = (_ptr(users_t), _ptr(items_t), f, ld, int(self.bias is True))
+        if filt is None:
+            def call(b0, nb, ids, csrs, *ws):
+                return lib.wmf_recommend_topn(*head, ids, nb, self.items.shape[0], *csrs[0], topn, 0, _ptr(items_d[b0:]),
+                                              _ptr(scores_d[b0:]) if scores_d is not None else None, None, *ws)
+        else:
+            at = filt.upload()
+
+            def call(b0, nb, ids, csrs, *ws):
+                return lib.wmf_recommend_topn_filtered(*head, ids, nb, self.items.shape[0], *csrs[0], *at(b0), topn, 0, _ptr(items_d[b0:]),
+                                                       _ptr(scores_d[b0:]) if scores_d is not None else None, None, *ws)
+        return self._scan_batches(u, [None if seen is None else (seen.indptr, seen.indices)],
+                                  lambda rows: lib.wmf_recommend_workspace_bytes(rows, topn, 0), [items_d, scores_d], call)
+
     # ------------------------------------------------------------------ a14: similar_items, similar_users
-    def similar_items(self, items, topn=10, metric='cosine', exclude_self=True, return_scores=False):
+    def similar_items(self, items, topn=10, metric='cosine', exclude_self=True, return_scores=False, allow=None, allow_idx=None):
         """The ``topn`` items closest to each of ``items`` in factor space (an int or a sequence of ints; negative indices count
         from the end), best first, equal scores in item order.  ``metric``: 'cosine' or 'dot', over the features -- the bias
         column of a bias model is not a feature in either.  ``exclude_self``: the item itself is not among its neighbours.
@@ -353,14 +456,18 @@ class WMF(RecModel):
         and inverse norms are made once; with a writable array every call uploads both matrices and computes the norms again
         -- freeze the arrays (``a.flags.writeable = False``) when they no longer change.  Returns int64 [len(items), topn], padded with -1 where there are fewer rows; with
         ``return_scores`` also the float32 scores, padded with -inf.  An int gives one row.  ``topn`` is at most
-        RECOMMEND_MAX_TOPN: there is no slower path beyond it, a larger ``topn`` is a ValueError."""
-        return self._similar("items", items, topn, metric, exclude_self, return_scores)
+        RECOMMEND_MAX_TOPN: there is no slower path beyond it, a larger ``topn`` is a ValueError.
+        ``allow`` / ``allow_idx``: the neighbours are taken among the allowed rows only, given as for ``recommend`` (a bool mask
+        of length items, a list of ids, or [G, items] masks with one ``allow_idx`` entry per query).  All three are served by the
+        mask form (wmf_similar_topn_filtered): the scaled score has no list form, a list of ids becomes its mask.  The row
+        itself is still left out under ``exclude_self`` when the mask allows it."""
+        return self._similar("items", items, topn, metric, exclude_self, return_scores, allow, allow_idx)
 
-    def similar_users(self, users, topn=10, metric='cosine', exclude_self=True, return_scores=False):
-        """``similar_items`` among the users: the ``topn`` users closest to each of ``users``."""
-        return self._similar("users", users, topn, metric, exclude_self, return_scores)
+    def similar_users(self, users, topn=10, metric='cosine', exclude_self=True, return_scores=False, allow=None, allow_idx=None):
+        """``similar_items`` among the users: the ``topn`` users closest to each of ``users`` (masks of length users)."""
+        return self._similar("users", users, topn, metric, exclude_self, return_scores, allow, allow_idx)
 
-    def _similar(self, side, ids, topn, metric, exclude_self, return_scores):
+    def _similar(self, side, ids, topn, metric, exclude_self, return_scores, allow=None, allow_idx=None):
         if metric not in ('cosine', 'dot'):
             raise ValueError(f"metric must be 'cosine' or 'dot', not {metric!r}")
         topn = int(topn)
@@ -371,17 +478,19 @@ class WMF(RecModel):
         n_rows = getattr(self, side).shape[0]
         one = np.ndim(ids) == 0
         q = _wrapped_ids(np.atleast_1d(np.asarray(ids)).reshape(-1).astype(np.int64), n_rows, side[:-1], np.int64)
+        filt = None if allow is None and allow_idx is None else _Allow(allow, allow_idx, n_rows, len(q), side[:-1], as_mask=True)
         _lib.require_gpu()
         out_rows = np.full((len(q), topn), -1, dtype=np.int64)
         out_scores = np.full((len(q), topn), -np.inf, dtype=np.float32)
-        if len(q):
-            self._similar_fused(side, q, topn, metric == 'cosine', bool(exclude_self), out_rows, out_scores if return_scores else None)
+        if len(q) and not (filt is not None and filt.empty):
+            self._similar_fused(side, q, topn, metric == 'cosine', bool(exclude_self), out_rows, out_scores if return_scores else None, filt)
         if one:
             out_rows, out_scores = out_rows[0], out_scores[0]
         return (out_rows, out_scores) if return_scores else out_rows
 
-    def _similar_fused(self, side, q, topn, cosine, exclude_self, out_rows, out_scores):
-        """wmf_similar_topn in batches (_scan_batches): the rows ``q`` of ``side`` against all of its rows."""
+    def _similar_fused(self, side, q, topn, cosine, exclude_self, out_rows, out_scores, filt=None):
+        """wmf_similar_topn in batches (_scan_batches): the rows ``q`` of ``side`` against all of its rows.  ``filt``: an _Allow in
+        the mask form, then wmf_similar_topn_filtered."""
         if cosine:
             users_t, items_t, f, ld, norms = self._device_inv_norms(side)
         else:
@@ -391,12 +500,18 @@ class WMF(RecModel):
         lib = _lib.load()
         rows_d = torch.empty(len(q), topn, dtype=torch.int32, device="cuda")
         scores_d = torch.empty(len(q), topn, dtype=torch.float32, device="cuda") if out_scores is not None else None
-        out_rows[:], scores = self._scan_batches(
-            q, [], lambda rows: lib.wmf_similar_workspace_bytes(rows, topn, 0), [rows_d, scores_d],
-            lambda b0, nb, ids, csrs, *ws: lib.wmf_similar_topn(
-                _ptr(mat), _ptr(mat), f, ld, int(self.bias is True), _ptr(norms) if cosine else None, _ptr(norms) if cosine else None,
-                ids, nb, mat.shape[0], int(exclude_self), None, None, topn, 0,
-                _ptr(rows_d[b0:]), _ptr(scores_d[b0:]) if scores_d is not None else None, None, *ws))
+        head = (_ptr(mat), _ptr(mat), f, ld, int(self.bias is True), _ptr(norms) if cosine else None, _ptr(norms) if cosine else None)
+        if filt is None:
+            def call(b0, nb, ids, csrs, *ws):
+                return lib.wmf_similar_topn(*head, ids, nb, mat.shape[0], int(exclude_self), None, None, topn, 0, _ptr(rows_d[b0:]),
+                                            _ptr(scores_d[b0:]) if scores_d is not None else None, None, *ws)
+        else:
+            at = filt.upload()
+
+            def call(b0, nb, ids, csrs, *ws):
+                return lib.wmf_similar_topn_filtered(*head, ids, nb, mat.shape[0], int(exclude_self), None, None, *at(b0)[:4], topn, 0,
+                                                     _ptr(rows_d[b0:]), _ptr(scores_d[b0:]) if scores_d is not None else None, None, *ws)
+        out_rows[:], scores = self._scan_batches(q, [], lambda rows: lib.wmf_similar_workspace_bytes(rows, topn, 0), [rows_d, scores_d], call)
         if out_scores is not None:
             out_scores[:] = scores
 
@@ -686,37 +801,31 @@ class WMF(RecModel):
         return np.ascontiguousarray(X_d[:, :f].cpu().numpy())
 
     def recommend_for(self, count_rows, topn=10, exclude_history=True, return_scores=False, alpha=10, beta=1,
-                      pre_process_count='log'):
+                      pre_process_count='log', allow=None, allow_idx=None):
         """``recommend`` for histories instead of user ids: the rows of ``count_rows`` ([B, items], as for ``fold_in``) are
         folded in and the ``topn`` best items of the whole catalogue are found for each, best first, equal scores in item order;
         the factors never leave the device.  ``exclude_history``: the stored entries of a row (stored zeros too) are not
         recommended to it.  Returns int64 [B, topn], padded with -1 where a row has fewer eligible items; with ``return_scores``
         also the float32 scores, padded with -inf -- the items and scores of ``recommend`` on a model whose ``users`` are
         ``fold_in(count_rows)``, bit for bit.  A row whose fold-in failed (NaN factors) is all -1 / -inf.  ``topn`` is at most
-        RECOMMEND_MAX_TOPN: a larger one is a ValueError."""
+        RECOMMEND_MAX_TOPN: a larger one is a ValueError.  ``allow`` / ``allow_idx``: the catalogue filter of ``recommend``
+        (``allow_idx`` has one entry per row of ``count_rows``), with the same identity."""
         mat, mode = self._foldin_arguments(count_rows, pre_process_count)
         topn = int(topn)
         if topn < 1 or topn > RECOMMEND_MAX_TOPN:
             raise ValueError(f"topn must be between 1 and {RECOMMEND_MAX_TOPN}, not {topn}")
-        _lib.require_gpu()
         B = mat.shape[0]
+        filt = None if allow is None and allow_idx is None else _Allow(allow, allow_idx, self.items.shape[0], B, "item")
+        _lib.require_gpu()
         out_items = np.full((B, topn), -1, dtype=np.int64)
         out_scores = np.full((B, topn), -np.inf, dtype=np.float32)
-        if B:
+        if B and not (filt is not None and filt.empty):
             X_d, items_t, f, ld = self._fold_in_device(mat, alpha, beta, mode)
             seen = None
             if exclude_history:
                 seen = mat.copy()                                  # the seen list as ``recommend`` prepares ``exclude``
                 seen.sort_indices()
-            lib = _lib.load()
-            items_d = torch.empty(B, topn, dtype=torch.int32, device="cuda")
-            scores_d = torch.empty(B, topn, dtype=torch.float32, device="cuda") if return_scores else None
-            got_items, got_scores = self._scan_batches(
-                np.arange(B, dtype=np.int64), [None if seen is None else (seen.indptr, seen.indices)],
-                lambda rows: lib.wmf_recommend_workspace_bytes(rows, topn, 0), [items_d, scores_d],
-                lambda b0, nb, ids, csrs, *ws: lib.wmf_recommend_topn(
-                    _ptr(X_d), _ptr(items_t), f, ld, int(self.bias is True), ids, nb, self.items.shape[0], *csrs[0], topn, 0,
-                    _ptr(items_d[b0:]), _ptr(scores_d[b0:]) if scores_d is not None else None, None, *ws))
+            got_items, got_scores = self._recommend_scan(X_d, items_t, f, ld, np.arange(B, dtype=np.int64), topn, seen, return_scores, filt)
             good = ~torch.isnan(X_d[:, :f]).any(dim=1).cpu().numpy()
             out_items[good] = got_items[good]
             if return_scores:

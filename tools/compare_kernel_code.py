@@ -4,7 +4,7 @@ side, to the build, or to which kernels are instantiated left every remaining ke
 usage: python tools/compare_kernel_code.py OBJDIR_A OBJDIR_B [file.o ...]      (default: every .o the two directories share)
 
 Per object: the kernels (symbols with a .kd descriptor) only A has, only B has, and those in both whose disassembly differs
-(branch-target comments stripped, so a kernel that merely moved compares equal).  Exit status 1 if any kernel differs or B
+(branch-target comments and trailing alignment padding stripped, so a kernel that merely moved compares equal).  Exit status 1 if any kernel differs or B
 has a kernel that A has not; kernels that only A has are listed (a build that drops kernels is what this tool is for)."""
 import hashlib
 import os
@@ -42,7 +42,9 @@ def kernels(obj):
             bodies[name] = []
         elif name:
             bodies[name].append(re.sub(r"\s*//.*$", "", line).strip())
-    return {k: hashlib.sha1("\n".join(v).encode()).hexdigest() for k, v in bodies.items() if k in descriptors}
+    # (the zero padding up to the next symbol's alignment, printed as "...", depends on what follows the kernel: not its code)
+    return {k: hashlib.sha1("\n".join(line for line in v if line and line != "...").encode()).hexdigest()
+            for k, v in bodies.items() if k in descriptors}
 
 
 def demangled(names):

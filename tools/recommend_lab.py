@@ -3,6 +3,7 @@ wmf_recommend_topn -- against the path it stands beside, WMF.rank(np.arange(n_it
 segmented sort, wmf_rank_topn_batch, in batches of 2^26 scores.
 
 Usage: python tools/recommend_lab.py [--out FILE] [--reps 5] [--topn 10] [users,items,k,bias ...]
+       python tools/recommend_lab.py --filters [--out FILE] [--reps 5] [--topn 10] [users,items,k,bias]
 
 Both paths run in one process on the same seeded Gaussian factors, without exclusions; after a warm-up of each they are timed
 in alternating repetitions with a host clock that ends in a device synchronise; median and spread (max - min) per path.  The two
@@ -10,7 +11,15 @@ answers are compared on the spot under the rounded-class rule of the tests: the 
 within B of the k-th of the other.  The fused call is also timed with a seen list of 10 entries per user.  The scan kernel's
 own time comes from the library's wmf_profile_* table and is set against max(2 U I ld / f32-MFMA peak, item bytes x passes /
 HBM peak) with the peaks of the MI355X data sheet (157.3 TFLOP/s, 8.0 TB/s); passes = blocks of 64 users, each of which
-streams the catalogue once."""
+streams the catalogue once.
+
+--filters: the catalogue filters of WMF.recommend (wmf_recommend_topn_filtered) at one shape, with a seen list of 10 entries per
+user, at pass rates of 50 %, 1 % and 0.01 % of the catalogue: the mask form and the list form next to the unfiltered call (the
+parent's scan kernel, unchanged) in alternating repetitions of one process, and the two routes a caller had before -- the
+complement of the filter appended to ``exclude`` through the unfiltered call, for the first COMPLEMENT_USERS users (for all of them
+the seen list would be about 8 GB), and rank(allowed, users, topn), which knows no seen items.  The answers are compared on the
+spot: filtered against complement-in-exclude bit for bit, rank under the rounded-class rule against the list form without a seen
+list.  Then the list form at a ladder of list lengths against the mask form of the same list: where the two cross."""
 import argparse
 import json
 import statistics
@@ -104,13 +113,130 @@ def run_shape(n_users, n_items, k, bias, topn, reps):
     return rec
 
 
+COMPLEMENT_USERS = 128
+PASS_RATES = (0.5, 0.01, 0.0001)
+LADDER = (1000, 10000, 100000, 250000, 500000, 750000, 1000000)
+
+
+def scan_kernel_s(lib, fn):
+    """{kernel: seconds} of one call of fn, from the library's own event table."""
+    lib.wmf_profile_reset()
+    lib.wmf_profile_enable(1)
+    timed(fn)
+    lib.wmf_profile_enable(0)
+    out = {name: ms * 1e-3 for name, _, ms, _, _, _ in _lib.profile_table(lib)}
+    lib.wmf_profile_reset()
+    return out
+
+
+def same_bits(a, b):
+    return bool(np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.int32), b[1].view(np.int32)))
+
+
+def run_filters(n_users, n_items, k, bias, topn, reps):
+    rng = np.random.default_rng(1000 * k + bias)
+    m = WMF(num_items=8, num_users=n_users, dim=k, gamma=0.1, weighted=True, bias=bool(bias))
+    f = k + bias
+    m.users, m.items = rng.standard_normal((n_users, f), dtype=np.float32), rng.standard_normal((n_items, f), dtype=np.float32)
+    m.num_items = n_items
+    m.users.flags.writeable = m.items.flags.writeable = False
+    users = np.arange(n_users)
+    seen = sp.csr_matrix((np.ones(10 * n_users, dtype=np.float32), rng.integers(0, n_items, 10 * n_users), 10 * np.arange(n_users + 1)),
+                         shape=(n_users, n_items))
+    seen.sum_duplicates()
+    lib = _lib.load()
+    few = users[:min(COMPLEMENT_USERS, n_users)]
+    unfiltered = lambda: m.recommend(users, topn, exclude=seen, return_scores=True)  # noqa: E731
+    timed(unfiltered)
+    rec = {"users": n_users, "items": n_items, "k": k, "bias": bias, "topn": topn, "seen_per_user": 10,
+           "complement_users": len(few), "rates": [], "ladder": []}
+    for rate in PASS_RATES:
+        mask = rng.random(n_items) < rate
+        ids = np.flatnonzero(mask)
+        comp = np.flatnonzero(~mask)
+        rows = [np.union1d(comp, seen.indices[seen.indptr[u]:seen.indptr[u + 1]]) for u in few]
+        big = sp.csr_matrix((np.ones(sum(len(r) for r in rows), dtype=np.float32), np.concatenate(rows),
+                             np.concatenate([[0], np.cumsum([len(r) for r in rows])])), shape=(len(few), n_items))
+        big.resize((n_users, n_items))                              # (rows past the first complement_users stay empty and are not asked for)
+        routes = {"unfiltered": unfiltered,
+                  "mask": lambda: m.recommend(users, topn, exclude=seen, return_scores=True, allow=mask),
+                  "list": lambda: m.recommend(users, topn, exclude=seen, return_scores=True, allow=ids),
+                  "mask_few_users": lambda: m.recommend(few, topn, exclude=seen, return_scores=True, allow=mask),
+                  "complement_in_exclude_few_users": lambda: m.recommend(few, topn, exclude=big, return_scores=True),
+                  "rank_allowed_no_seen": lambda: np.stack(m.rank(ids, list(users), topn=min(topn, len(ids))))}
+        first = {}
+        for name, fn in routes.items():                            # (the warm-up of each route; its time is not used)
+            dt, first[name] = timed(fn)
+            print(f"# pass rate {rate}: {name} warmed up in {dt:.3f} s", file=sys.stderr, flush=True)
+        agree = {"mask_equals_list_bits": same_bits(first["mask"], first["list"]),
+                 "mask_equals_complement_in_exclude_bits": same_bits(first["mask_few_users"], first["complement_in_exclude_few_users"]),
+                 "list_equals_complement_in_exclude_bits": same_bits([a[:len(few)] for a in first["list"]], first["complement_in_exclude_few_users"])}
+        no_seen = m.recommend(users, min(topn, len(ids)), allow=ids)
+        sa, ba = scores64(m, users, no_seen)
+        sb, bb = scores64(m, users, first["rank_allowed_no_seen"])
+        agree["rank_order_gap_over_bound"] = float((np.abs(sa - sb) / np.maximum(ba, bb)).max())
+        agree["rank_same_items_fraction"] = float((no_seen == first["rank_allowed_no_seen"]).mean())
+        assert all(v for key, v in agree.items() if key.endswith("_bits")) and agree["rank_order_gap_over_bound"] <= 1.0, agree
+        t = {name: [] for name in routes}
+        for _ in range(reps):
+            for name, fn in routes.items():
+                t[name].append(timed(fn)[0])
+        entry = {"pass_rate": rate, "allowed": int(len(ids)), "agreement": agree, **{name: stats(ts) for name, ts in t.items()},
+                 "kernel_s": {name: scan_kernel_s(lib, routes[name]) for name in ("unfiltered", "mask", "list")}}
+        scan = {name: sum(v for nm, v in entry["kernel_s"][name].items() if nm.startswith("recommend_scan")) for name in entry["kernel_s"]}
+        entry["scan_kernel_s"] = scan
+        entry["mask_over_unfiltered"] = {"call": entry["mask"]["median_s"] / entry["unfiltered"]["median_s"], "scan_kernel": scan["mask"] / scan["unfiltered"]}
+        entry["list_over_unfiltered"] = {"call": entry["list"]["median_s"] / entry["unfiltered"]["median_s"], "scan_kernel": scan["list"] / scan["unfiltered"]}
+        rec["rates"].append(entry)
+        print(json.dumps({key: entry[key] for key in ("pass_rate", "allowed", "agreement", "scan_kernel_s", "mask_over_unfiltered", "list_over_unfiltered")}
+                         | {name: entry[name]["median_s"] for name in routes}), flush=True)
+        del big, rows, comp
+    # where the two forms cross: the same list through both, at a ladder of lengths
+    order = rng.permutation(n_items)
+    for n_cand in [n for n in LADDER if n <= n_items]:
+        ids = np.sort(order[:n_cand])
+        mask = np.zeros(n_items, dtype=bool)
+        mask[ids] = True
+        forms = {"mask": lambda: m.recommend(users, topn, exclude=seen, return_scores=True, allow=mask),
+                 "list": lambda: m.recommend(users, topn, exclude=seen, return_scores=True, allow=ids)}
+        assert same_bits(timed(forms["mask"])[1], timed(forms["list"])[1])
+        t = {name: [] for name in forms}
+        for _ in range(reps):
+            for name, fn in forms.items():
+                t[name].append(timed(fn)[0])
+        kern = {name: sum(v for nm, v in scan_kernel_s(lib, fn).items() if nm.startswith("recommend_scan")) for name, fn in forms.items()}
+        rec["ladder"].append({"n_cand": n_cand, "mask": stats(t["mask"]), "list": stats(t["list"]), "scan_kernel_s": kern})
+        print(json.dumps({"n_cand": n_cand, "mask_s": rec["ladder"][-1]["mask"]["median_s"], "list_s": rec["ladder"][-1]["list"]["median_s"],
+                          "scan_kernel_s": kern}), flush=True)
+    for key, pick in (("call", lambda e, nm: e[nm]["median_s"]), ("scan_kernel", lambda e, nm: e["scan_kernel_s"][nm])):
+        cross = None
+        for lo, hi in zip(rec["ladder"], rec["ladder"][1:]):
+            d0, d1 = pick(lo, "list") - pick(lo, "mask"), pick(hi, "list") - pick(hi, "mask")
+            if d0 < 0 <= d1:
+                cross = lo["n_cand"] + (hi["n_cand"] - lo["n_cand"]) * (-d0) / (d1 - d0)
+        rec[f"crossover_n_cand_by_{key}"] = cross
+        rec[f"list_faster_at_every_length_by_{key}"] = bool(all(pick(e, "list") < pick(e, "mask") for e in rec["ladder"]))
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the full record to this file")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--topn", type=int, default=10)
-    ap.add_argument("shapes", nargs="*", default=list(DEFAULT_SHAPES))
+    ap.add_argument("--filters", action="store_true", help="the catalogue filters at one shape (default 2048,1000000,128,1)")
+    ap.add_argument("shapes", nargs="*", default=None)
     args = ap.parse_args()
+    if args.filters:
+        n_users, n_items, k, bias = (int(x) for x in (args.shapes or [DEFAULT_SHAPES[1]])[0].split(","))
+        out = {"device": torch.cuda.get_device_name(0), "method": __doc__.split("\n\n")[3],
+               "filters": run_filters(n_users, n_items, k, bias, args.topn, args.reps)}
+        print(json.dumps({key: out["filters"][key] for key in out["filters"] if key.startswith(("crossover", "list_faster"))}), flush=True)
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(out, fh, indent=1)
+        return
+    args.shapes = args.shapes or list(DEFAULT_SHAPES)
     out = {"device": torch.cuda.get_device_name(0), "method": __doc__.split("\n\n")[2], "shapes": []}
     for shape in args.shapes:
         n_users, n_items, k, bias = (int(x) for x in shape.split(","))
