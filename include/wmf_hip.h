@@ -387,6 +387,51 @@ int wmf_recommend_topn_filtered(const float* users, const float* items, int f, i
                                 int32_t* out_items, float* out_scores, int32_t* out_count,
                                 void* workspace, int64_t workspace_bytes, void* stream);
 
+/* wmf_recommend_topn_filtered for 1 <= topn <= WMF_RECOMMEND_WIDE_MAX_TOPN: the candidate pool of a two-stage recommender, the
+ * lists behind Recall@500.  The contract of wmf_recommend_topn_filtered in every respect but the limit: the same arguments, seen
+ * list per batch position, order (a higher score wins, equal scores go to the lower id, -0.0 equals +0.0), out_count, -1 / -inf
+ * padding; the call only enqueues, and every refusal (WMF_EINVAL) comes before any HIP call and leaves the outputs untouched.
+ * Filter forms: neither allow_bits nor cand_idx is an unfiltered call; exactly one of them is a filtered call (the mask form, the
+ *   list form); both is WMF_EINVAL, as are n_masks < 1, allow_words too small, allow_idx without allow_bits and n_cand outside
+ *   [1, n_items].
+ * Kernels: every topn from 1 to the limit runs the wide kernels -- nothing routes a small topn to wmf_recommend_topn's.  The scan
+ *   and its arithmetic are those of wmf_recommend_topn (the scores are the same bits); a row's running keys live in the workspace
+ *   instead of LDS, one buffer of WMF_RECOMMEND_WIDE_CAP(topn) keys per (batch position, slice), cut back to its topn best by an
+ *   exact radix select whenever the next tile could overflow it; a selection kernel then takes the topn best of a row's slices and
+ *   sorts them.  For topn <= WMF_RECOMMEND_MAX_TOPN the result equals wmf_recommend_topn[_filtered]'s bit for bit.
+ * Slices: 0: the library chooses; 1 .. WMF_RECOMMEND_MAX_SLICES forces it; the result does not depend on it.  The automatic count
+ *   is S0 = L0 / n_users (rounded down), L0 = min(WMF_RECOMMEND_WIDE_AUTO_SLICES * n_users, max(WMF_RECOMMEND_WIDE_AUTO_LISTS,
+ *   n_users)) lists -- 512 workgroups of 64 rows, enough to fill the device, at most WMF_RECOMMEND_WIDE_AUTO_SLICES slices --
+ *   lowered until a slice holds at least max(1024, WMF_RECOMMEND_WIDE_SLICE_TOPNS * topn) of the scanned positions (n_items, or
+ *   n_cand in the list form): a row inserts about topn (1 + ln(slice / topn)) keys per slice, each a seen-list search and a global
+ *   store, and they stay rare only while a slice is several times longer than topn.
+ * Workspace: wmf_recommend_wide_workspace_bytes(n_users, topn, n_slices) = WMF_RECOMMEND_WIDE_WS_BASE + L *
+ *   (WMF_RECOMMEND_WIDE_WS_PER_KEY * WMF_RECOMMEND_WIDE_CAP(topn) + WMF_RECOMMEND_WIDE_WS_PER_LIST), L = n_users * n_slices lists,
+ *   or L0 above for n_slices = 0.  Pure host code; it does not depend on n_items and grows with each of its arguments.
+ * Measured (MI355X, 1 000 000 items, k = 128 + biases, 10 seen items per row; profiles/r20_recommend_wide.json): 16 users at topn
+ *   200 in 5.2 ms where the host loop of WMF.recommend took 111 ms; 2048 users in 17.9 / 21.8 / 27.6 / 36.7 ms at topn 129 / 256 /
+ *   512 / 1000 (scan 17.0 .. 33.3 ms, selection 0.16 .. 0.90 ms), 16 users in 4.4 .. 16.7 ms at topn 129 .. 4096; at topn 128 the
+ *   scan takes 17.1 ms where wmf_recommend_topn's two-wave scan takes 46.9; the mask form at a 1 % pass rate 14.9 ms and the list
+ *   form of 10 000 ids 6.0 ms at topn 1000.  At topn 2048 / 4096 a row needs 4 / 2 MB of workspace at 62 / 31 slices: force fewer
+ *   slices, or call with fewer rows, when that is too much. */
+#define WMF_RECOMMEND_WIDE_MAX_TOPN 4096
+#define WMF_RECOMMEND_WIDE_AUTO_SLICES 64
+#define WMF_RECOMMEND_WIDE_AUTO_LISTS 32768
+#define WMF_RECOMMEND_WIDE_SLICE_TOPNS 8
+#define WMF_RECOMMEND_WIDE_CAP(topn) (2 * (topn) > 32 ? 2 * (topn) : 32)
+#define WMF_RECOMMEND_WIDE_WS_BASE 256
+#define WMF_RECOMMEND_WIDE_WS_PER_KEY 8
+#define WMF_RECOMMEND_WIDE_WS_PER_LIST 8
+int64_t wmf_recommend_wide_workspace_bytes(int64_t n_users, int64_t topn, int32_t n_slices);
+int wmf_recommend_topn_wide(const float* users, const float* items, int f, int ld, int bias,
+                            const int32_t* user_idx, int64_t n_users, int64_t n_items,
+                            const int64_t* seen_indptr, const int32_t* seen_indices,
+                            const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks, const int32_t* allow_idx,
+                            const int32_t* cand_idx, int64_t n_cand,
+                            int64_t topn, int32_t n_slices,
+                            int32_t* out_items, float* out_scores, int32_t* out_count,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Inverse row norms over the FEATURE columns, the scales of a cosine (wmf_similar_topn):
  * out[i] = 1 / sqrt(S_i) rounded to float32, S_i = sum over the columns c in [bias, f) of M[i, c]^2 accumulated in float64 in a
  * fixed order (two calls give the same bits); 0 where S_i == 0 or the quotient is not a finite float32.  With bias != 0 column 0

@@ -63,17 +63,18 @@ static int check_shape(int f, int ld) {
 
 // The checks the three catalogue-scan entry points share (before any HIP call).  null_text: what a missing pointer is called there;
 // own: the refusal of the call's own pointer rules, found by the caller, or NULL; rows / cat: the names the message prints for
-// n_rows / n_items; topn: NULL when the call has none; need(): the workspace of the call, asked once the sizes are in range
+// n_rows / n_items; topn: NULL when the call has none; need(): the workspace of the call, asked once the sizes are in range; max_topn:
+// the call's limit
 template <class Need>
 static int check_scan_call(const char* what, const void* users, const void* items, const void* user_idx, const void* out, const void* workspace,
                            const char* null_text, const char* own, const char* rows, int64_t n_rows, const char* cat, int64_t n_items,
-                           const int64_t* topn, int32_t n_slices, int64_t workspace_bytes, Need&& need) {
+                           const int64_t* topn, int32_t n_slices, int64_t workspace_bytes, Need&& need, int max_topn = WMF_RECOMMEND_MAX_TOPN) {
     if (!users || !items || !user_idx || !out || !workspace) { wmf_set_error("%s: %s", what, null_text); return WMF_EINVAL; }
     if (own) { wmf_set_error("%s: %s", what, own); return WMF_EINVAL; }
-    if (n_rows < 1 || n_items < 1 || n_items > 0x7fffffffLL || (topn && (*topn < 1 || *topn > WMF_RECOMMEND_MAX_TOPN)) || n_slices < 0 ||
+    if (n_rows < 1 || n_items < 1 || n_items > 0x7fffffffLL || (topn && (*topn < 1 || *topn > max_topn)) || n_slices < 0 ||
         n_slices > WMF_RECOMMEND_MAX_SLICES) {
         if (topn) wmf_set_error("%s: need %s >= 1, 1 <= %s < 2^31, 1 <= topn <= %d, 0 <= n_slices <= %d (%s=%lld, %s=%lld, topn=%lld, n_slices=%d)", what, rows,
-                                cat, WMF_RECOMMEND_MAX_TOPN, WMF_RECOMMEND_MAX_SLICES, rows, (long long)n_rows, cat, (long long)n_items, (long long)*topn, (int)n_slices);
+                                cat, max_topn, WMF_RECOMMEND_MAX_SLICES, rows, (long long)n_rows, cat, (long long)n_items, (long long)*topn, (int)n_slices);
         else wmf_set_error("%s: need %s >= 1, 1 <= %s < 2^31, 0 <= n_slices <= %d (%s=%lld, %s=%lld, n_slices=%d)", what, rows, cat,
                            WMF_RECOMMEND_MAX_SLICES, rows, (long long)n_rows, cat, (long long)n_items, (int)n_slices);
         return WMF_EINVAL;
@@ -744,6 +745,26 @@ int wmf_recommend_topn_filtered(const float* users, const float* items, int f, i
                                                       allow_words, allow_idx, cand_idx, n_cand, topn, n_slices, out_items, out_scores, out_count,
                                                       workspace, (hipStream_t)stream),
                         "wmf_recommend_topn_filtered", f, ld, "");
+}
+
+int64_t wmf_recommend_wide_workspace_bytes(int64_t n_users, int64_t topn, int32_t n_slices) { return wmf_recommend_wide_ws_bytes(n_users, topn, n_slices); }
+
+// every topn runs the wide kernels: for topn <= WMF_RECOMMEND_MAX_TOPN the entry points above are the cross-check, bit for bit
+int wmf_recommend_topn_wide(const float* users, const float* items, int f, int ld, int bias, const int32_t* user_idx, int64_t n_users,
+                            int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* allow_bits,
+                            int64_t allow_words, int32_t n_masks, const int32_t* allow_idx, const int32_t* cand_idx, int64_t n_cand,
+                            int64_t topn, int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* workspace,
+                            int64_t workspace_bytes, void* stream) {
+    int rc = check_shape(f, ld);
+    if (rc) return rc;
+    const char* own = filter_refusal(allow_bits, allow_words, n_masks, allow_idx, n_items, cand_idx, n_cand);
+    if ((rc = check_scan_call("wmf_recommend_topn_wide", users, items, user_idx, out_items, workspace, "null pointer", own, "n_users", n_users,
+                              "n_items", n_items, &topn, n_slices, workspace_bytes,
+                              [&] { return wmf_recommend_wide_ws_bytes(n_users, topn, n_slices); }, WMF_RECOMMEND_WIDE_MAX_TOPN))) return rc;
+    return launch_error(wmf_launch_recommend_wide(users, items, ld, bias, user_idx, n_users, n_items, seen_indptr, seen_indices, allow_bits,
+                                                  allow_words, allow_idx, cand_idx, n_cand, topn, n_slices, out_items, out_scores, out_count,
+                                                  workspace, (hipStream_t)stream),
+                        "wmf_recommend_topn_wide", f, ld, "");
 }
 
 int wmf_row_inv_norms(const float* M, int64_t n, int f, int ld, int bias, float* out, void* stream) {

@@ -13,6 +13,9 @@
 //                               costs anything in the scoring loop.
 //   * recommend_merge_kernel -- the sorted partial lists of a user's slices merged by rank: a key's place is the number of
 //                               keys above it, found by one binary search per slice.
+//   * recommend_scan_wide_kernel, recommend_select_wide_kernel -- the same scan for 1 <= topn <= 4096 (wmf_recommend_topn_wide): the
+//                               keys of a (user, slice) pair in the workspace, cut back by an exact select (wmf_topn_wide.h), and the
+//                               selection and sort of the topn best of a user's slices.
 // The keys of a user are pairwise distinct, so the result is a function of the scores alone: it cannot depend on the number of
 // slices, the grid or the order in which workgroups, waves or LDS atomics finish.  No float atomics.
 
@@ -20,6 +23,7 @@
 #include "wmf_internal.h"
 #include "wmf_scan.h"
 #include "wmf_topn.h"
+#include "wmf_topn_wide.h"
 
 #define WMF_REC_MERGE_GRID 1024      /* workgroups of the merge, four users each */
 #define WMF_REC_SLICE_TILES 64       /* an automatic slice holds at least this many 16-item tiles */
@@ -96,6 +100,88 @@ __global__ __launch_bounds__(256) void recommend_merge_kernel(const unsigned lon
             if (out_scores) out_scores[b * topn + k] = -__builtin_inff();
         }
         if (lane == 0 && out_count) out_count[b] = count;
+    }
+}
+
+// ---- beyond the LDS buffers: wmf_recommend_topn_wide -----------------------------------------------------------------------------
+// The same scans -- the same width classes, WmfModelScore, GATHER for the list form, so the same score bits -- with the epilogue of
+// wmf_topn_wide.h: the keys of a (batch position, slice) pair in the workspace, cut back by an exact select.  FORM 0: unfiltered,
+// 1: the mask form, 2: the list form.
+template <int NIT, int TPS, int NW, int FORM>
+__global__ __launch_bounds__(64 * NW) void recommend_scan_wide_kernel(const float* __restrict__ users, const float* __restrict__ items, int ld,
+                                                                      int bias, const int32_t* __restrict__ user_idx, int64_t n_users,
+                                                                      int64_t n_items, const int64_t* __restrict__ seen_indptr,
+                                                                      const int32_t* __restrict__ seen_indices,
+                                                                      const uint32_t* __restrict__ allow_bits, int64_t allow_words,
+                                                                      const int32_t* __restrict__ allow_idx,
+                                                                      const int32_t* __restrict__ cand_idx, int topn, int cap, int n_slices,
+                                                                      int64_t tiles_per_slice, int64_t n_work, unsigned long long* keys_ws,
+                                                                      int32_t* counts_ws) {
+    extern __shared__ __align__(16) unsigned char wmf_scan_smem[];
+    RecTopNWide<NW, FORM == 1> p{seen_indptr, seen_indices, n_users, topn, cap, n_slices, keys_ws, counts_ws};
+    p.allow_bits = allow_bits; p.allow_words = allow_words; p.allow_idx = allow_idx;
+    wmf_catalogue_scan<NIT, TPS, NW, decltype(p), WmfModelScore, FORM == 2>(
+        users, items, ld, bias, user_idx, n_users, n_items, n_slices, tiles_per_slice, n_work, p, WmfModelScore(), cand_idx,
+        reinterpret_cast<int32_t*>(wmf_scan_smem + wmf_scan_stage_bytes(TPS, ld) + rec_wide_lds_bytes(NW)));
+}
+
+// One workgroup per batch position: the topn best keys of all the row's slices (the exact select of wmf_topn_wide.h over the
+// buffers as the scan left them), sorted best first in LDS (bitonic, the keys are distinct: one result), then items, scores, count
+// and padding.
+__global__ __launch_bounds__(256) void recommend_select_wide_kernel(const unsigned long long* __restrict__ keys, const int32_t* __restrict__ counts,
+                                                                    int64_t n_users, int n_slices, int topn, int cap,
+                                                                    int32_t* __restrict__ out_items, float* __restrict__ out_scores,
+                                                                    int32_t* __restrict__ out_count) {
+    __shared__ unsigned long long sel[WMF_RECOMMEND_WIDE_MAX_TOPN];
+    __shared__ unsigned hist[256];
+    __shared__ int total_s, fill_s;
+    const int t = threadIdx.x;
+    for (int64_t b = blockIdx.x; b < n_users; b += gridDim.x) {
+        const unsigned long long* K = keys + (size_t)b * n_slices * cap;
+        const int32_t* C = counts + b * n_slices;
+        if (t == 0) { total_s = 0; fill_s = 0; }
+        __syncthreads();
+        int mine = 0;
+        for (int s = t; s < n_slices; s += 256) mine += min(C[s], cap);
+        if (mine) atomicAdd(&total_s, mine);
+        __syncthreads();
+        const int m = total_s, count = min(m, topn);               // (uniform: the select below holds barriers)
+        unsigned long long T = 1ull;                               // every key of an item is above 0
+        if (m > topn) T = rec_wide_kth<256>(K, C, n_slices, cap, 0, cap, topn, hist, t);
+        int P = 1;
+        while (P < count) P <<= 1;
+        for (int i = t; i < P; i += 256) sel[i] = 0ull;
+        __syncthreads();
+        for (int s = 0; s < n_slices; ++s) {
+            const int c = min(C[s], cap);
+            for (int e = t; e < c; e += 256) {
+                const unsigned long long key = K[(size_t)s * cap + e];
+                if (key >= T) {
+                    const int slot = atomicAdd(&fill_s, 1);        // exactly `count` keys are at or above T
+                    if (slot < topn) sel[slot] = key;
+                }
+            }
+        }
+        __syncthreads();
+        for (int k = 2; k <= P; k <<= 1) {
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                for (int i = t; i < P; i += 256) {
+                    const int o = i ^ j;
+                    if (o > i) {
+                        const unsigned long long x = sel[i], y = sel[o];
+                        if ((i & k) == 0 ? x < y : x > y) { sel[i] = y; sel[o] = x; }
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        for (int k = t; k < topn; k += 256) {
+            const unsigned long long key = k < count ? sel[k] : 0ull;
+            out_items[b * topn + k] = k < count ? (int32_t)(~(uint32_t)(key & 0xFFFFFFFFull)) : -1;
+            if (out_scores) out_scores[b * topn + k] = k < count ? wmf_key_float((uint32_t)(key >> 32)) : -__builtin_inff();
+        }
+        if (t == 0 && out_count) out_count[b] = count;
+        __syncthreads();                                           // sel and the counters are read before the next row resets them
     }
 }
 
@@ -178,5 +264,74 @@ int wmf_launch_recommend_filtered(const float* users, const float* items, int ld
     });
     if (rc) return rc;
     wmf_launch_topn_merge(partial, n_users, a.n_slices, n, out_items, out_scores, out_count, st);
+    return WMF_L_OK;
+}
+
+// ---- the wide launcher ------------------------------------------------------------------------------------------------------
+// the lists -- (batch position, slice) pairs -- the workspace of an automatic call is sized for: monotone in n_users
+static int64_t rec_wide_auto_lists(int64_t n_users) {
+    const int64_t most = WMF_RECOMMEND_WIDE_AUTO_SLICES * n_users;
+    const int64_t want = n_users > WMF_RECOMMEND_WIDE_AUTO_LISTS ? n_users : WMF_RECOMMEND_WIDE_AUTO_LISTS;
+    return most < want ? most : want;
+}
+// ... and the slice count that fits them
+static int64_t rec_wide_auto_bound(int64_t n_users) { return rec_wide_auto_lists(n_users) / n_users; }
+
+int64_t wmf_recommend_wide_ws_bytes(int64_t n_users, int64_t topn, int32_t n_slices) {
+    if (n_users < 1 || topn < 1 || n_slices < 0) return WMF_RECOMMEND_WIDE_WS_BASE;
+    const int64_t lists = n_slices == 0 ? rec_wide_auto_lists(n_users) : n_users * n_slices;
+    return WMF_RECOMMEND_WIDE_WS_BASE + lists * (WMF_RECOMMEND_WIDE_WS_PER_KEY * WMF_RECOMMEND_WIDE_CAP(topn) + WMF_RECOMMEND_WIDE_WS_PER_LIST);
+}
+
+// the slices of a wide call: the bound above, and a slice at least WMF_RECOMMEND_WIDE_SLICE_TOPNS x topn items (and
+// WMF_REC_SLICE_TILES tiles) long, so that insertions -- about topn (1 + ln(slice / topn)) per row and slice -- stay rare
+int wmf_recommend_wide_slices(int64_t n_users, int64_t n_scan, int64_t topn, int32_t n_slices) {
+    if (n_slices > 0) return n_slices;
+    const int64_t tiles = (n_scan + 15) / 16;
+    int64_t slice_tiles = (WMF_RECOMMEND_WIDE_SLICE_TOPNS * topn + 15) / 16;
+    if (slice_tiles < WMF_REC_SLICE_TILES) slice_tiles = WMF_REC_SLICE_TILES;
+    int64_t s = rec_wide_auto_bound(n_users);
+    const int64_t by_tiles = (tiles + slice_tiles - 1) / slice_tiles;
+    if (s > by_tiles) s = by_tiles;
+    return (int)(s < 1 ? 1 : s);
+}
+
+// allow_bits: the mask form; cand_idx: the list form; neither: the whole catalogue.  Never both (the entry point refuses it).
+int wmf_launch_recommend_wide(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
+                              int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* allow_bits,
+                              int64_t allow_words, const int32_t* allow_idx, const int32_t* cand_idx, int64_t n_cand, int64_t topn,
+                              int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* ws, hipStream_t st) {
+    const int64_t n_scan = cand_idx ? n_cand : n_items;
+    WmfScanArgs a = {users, items, ld, bias, user_idx, n_users, n_scan, wmf_recommend_wide_slices(n_users, n_scan, topn, n_slices), st};
+    const int n = (int)topn, cap = WMF_RECOMMEND_WIDE_CAP(n);
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws);
+    int32_t* counts = reinterpret_cast<int32_t*>(keys + (size_t)n_users * a.n_slices * cap);
+    constexpr int NW = WMF_REC_WIDE_WAVES;
+    const int rc = wmf_dispatch_scan(ld, [&](auto nit, auto tps) {
+        constexpr int NIT = decltype(nit)::value, TPS = decltype(tps)::value;
+        wmf_scan_geometry(a, NW);
+        const size_t lds = wmf_scan_stage_bytes(TPS, ld) + rec_wide_lds_bytes(NW);
+        if (cand_idx) {
+            static const char* name = wmf_kname("recommend_scan_wide_list_kernel<%d, %d, %d>", NIT, TPS, NW);
+            WMF_LAUNCH_LDS(name, (recommend_scan_wide_kernel<NIT, TPS, NW, 2>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW),
+                           lds + (size_t)2 * TPS * 16 * 4, st, a.users, a.items, a.ld, a.bias, a.user_idx, a.n_rows, a.n_items, seen_indptr,
+                           seen_indices, nullptr, (int64_t)0, nullptr, cand_idx, n, cap, a.n_slices, a.tiles_per_slice, a.n_work, keys, counts);
+        } else if (allow_bits) {
+            static const char* name = wmf_kname("recommend_scan_wide_mask_kernel<%d, %d, %d>", NIT, TPS, NW);
+            WMF_LAUNCH_LDS(name, (recommend_scan_wide_kernel<NIT, TPS, NW, 1>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW), lds, st,
+                           a.users, a.items, a.ld, a.bias, a.user_idx, a.n_rows, a.n_items, seen_indptr, seen_indices, allow_bits, allow_words,
+                           allow_idx, nullptr, n, cap, a.n_slices, a.tiles_per_slice, a.n_work, keys, counts);
+        } else {
+            static const char* name = wmf_kname("recommend_scan_wide_kernel<%d, %d, %d>", NIT, TPS, NW);
+            WMF_LAUNCH_LDS(name, (recommend_scan_wide_kernel<NIT, TPS, NW, 0>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW), lds, st,
+                           a.users, a.items, a.ld, a.bias, a.user_idx, a.n_rows, a.n_items, seen_indptr, seen_indices, nullptr, (int64_t)0,
+                           nullptr, nullptr, n, cap, a.n_slices, a.tiles_per_slice, a.n_work, keys, counts);
+        }
+        return (int)WMF_L_OK;
+    });
+    if (rc) return rc;
+    const int64_t grid = n_users < WMF_REC_MERGE_GRID ? n_users : WMF_REC_MERGE_GRID;    // rows beyond it take another trip
+    WMF_LAUNCH("recommend_select_wide_kernel", recommend_select_wide_kernel, dim3((unsigned)grid), dim3(256), 0, st, keys, counts, n_users,
+               a.n_slices, n, cap, out_items, out_scores, out_count);
     return WMF_L_OK;
 }

@@ -1,0 +1,178 @@
+// The running top-n of a catalogue scan beyond what LDS holds (gfx950): the epilogue policy of wmf_recommend_topn_wide, 1 <= topn <=
+// WMF_RECOMMEND_WIDE_MAX_TOPN.  A row's keys live in the WORKSPACE, one buffer of `cap` keys per (batch position, slice) pair; counts
+// and thresholds stay in LDS and registers as in RecTopN (wmf_topn.h).  A buffer that the next tile could overflow is cut back to its
+// topn best by an exact radix select of the topn-th largest key (the keys of a row are pairwise distinct, so that key is unique) and
+// one in-place compaction pass; nothing is sorted during the scan.  recommend_select_wide_kernel (wmf_recommend.hip) selects and
+// sorts the topn best of a row's slices with the same select.
+//
+// Who owns what: one wave owns the buffers of its 16 rows for the whole launch, and no other wave of the grid reads or writes them
+// before the kernel ends.  What orders the wave's own global accesses: see rec_wide_drain.
+#pragma once
+#include "wmf_scan.h"
+
+// A lane's global store followed by ANOTHER lane's load of the same address, both of one wave.  A wave issues its vector-memory
+// instructions in program order and all of them go through the one vector L1 of its CU, which writes through to L2; VM_CNT counts a
+// store until L2 has acknowledged it.  The load below the wait is therefore issued after the data is in L2 and after the L1 has seen
+// the store (the LLVM memory model for gfx942/gfx950 needs no cache action at wavefront or workgroup scope for that reason); the
+// fences keep the compiler from moving an access across.  wmf_wave_sync alone waits for nothing on the vector-memory side.
+__device__ __forceinline__ void rec_wide_drain() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The k-th largest (k = 1: the largest) of the keys of n_seg segments, segment s = base[s * seg_stride ...] of seg_cnt[s] keys
+// (seg_cnt == NULL: one segment of n_single keys); 1 <= k <= the number of keys, the keys pairwise distinct.  Eight passes over the
+// keys, most significant byte first: a 256-bin histogram (LDS atomics, integers: any order gives the same counts) of the keys that
+// share the prefix found so far, then the bin that holds the k-th.  Called by NT threads together, t = the thread's index among them;
+// NT = 64: one wave, hist is that wave's; NT > 64: the workgroup, one hist, __syncthreads.  Every thread returns the key.
+template <int NT>
+__device__ __forceinline__ void rec_wide_sync() {
+    if constexpr (NT == 64) wmf_wave_sync(); else __syncthreads();
+}
+template <int NT>
+__device__ __forceinline__ unsigned long long rec_wide_kth(const unsigned long long* base, const int32_t* seg_cnt, int n_seg,
+                                                           int64_t seg_stride, int n_single, int seg_max, int k, unsigned* hist, int t) {
+    const int lane = t & 63;
+    unsigned long long prefix = 0ull, mask = 0ull;
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        for (int i = t; i < 256; i += NT) hist[i] = 0u;
+        rec_wide_sync<NT>();
+        for (int s = 0; s < n_seg; ++s) {
+            const unsigned long long* seg = base + s * seg_stride;
+            const int c = seg_cnt ? min(seg_cnt[s], seg_max) : n_single;
+            for (int e = t; e < c; e += NT) {
+                const unsigned long long key = seg[e];
+                if ((key & mask) == prefix) atomicAdd(&hist[(unsigned)(key >> shift) & 255u], 1u);
+            }
+        }
+        rec_wide_sync<NT>();
+        // every wave for itself: lane l holds bins 4 l .. 4 l + 3; above = the keys in the bins of the higher lanes
+        const unsigned h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
+        const int own = (int)(h0 + h1 + h2 + h3);
+        int incl = own;                                            // own + the higher lanes'
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int v = __shfl_down(incl, o);
+            if (lane + o < 64) incl += v;
+        }
+        const int above = incl - own;
+        const bool here = above < k && k <= incl;                  // exactly one lane
+        int bin = 0, k_next = 0;
+        if (here) {
+            int a = above;
+            if (k <= a + (int)h3) { bin = 4 * lane + 3; }
+            else if (a += (int)h3, k <= a + (int)h2) { bin = 4 * lane + 2; }
+            else if (a += (int)h2, k <= a + (int)h1) { bin = 4 * lane + 1; }
+            else { a += (int)h1; bin = 4 * lane; }
+            k_next = k - a;
+        }
+        const int src = __builtin_ctzll(__ballot(here) | (1ull << 63));
+        bin = __shfl(bin, src);
+        k = __shfl(k_next, src);
+        prefix |= (unsigned long long)(unsigned)bin << shift;
+        mask |= 255ull << shift;
+        rec_wide_sync<NT>();                                       // the bins are read before the next pass clears them
+    }
+    return prefix;
+}
+
+// The scan's epilogue.  Workspace: keys[(b * n_slices + slice) * cap + e], e < counts[b * n_slices + slice], in no order, the topn
+// best eligible keys of that slice among them.  LDS past the stages: [thresholds: 16 per wave, 8 B][counts: 16 per wave][histogram:
+// 256 per wave].  MASK as in RecTopN.
+template <int NW, bool MASK = false>
+struct RecTopNWide {
+    const int64_t* __restrict__ seen_indptr; const int32_t* __restrict__ seen_indices;
+    int64_t n_users; int topn, cap, n_slices;
+    unsigned long long* keys_ws; int32_t* counts_ws;              // (not restrict: lanes read what other lanes of the wave wrote)
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
+    unsigned long long* thr_l; int* cnt; unsigned* hist;
+    int64_t u0; int sl;
+    unsigned long long thr[4];
+    unsigned long long* buf0; int64_t row_stride;                  // the buffer of row u0 + 4 q + reg: buf0 + reg * row_stride
+    int64_t seen_lo[4], seen_hi[4];
+    const uint32_t* __restrict__ allow_bits = nullptr; int64_t allow_words = 0; const int32_t* __restrict__ allow_idx = nullptr;
+    const uint32_t* words[4];
+
+    __device__ __forceinline__ unsigned long long* row_buf(int64_t b) const { return keys_ws + ((size_t)b * n_slices + sl) * (size_t)cap; }
+    __device__ __forceinline__ void begin(unsigned char* lds, int64_t u0_, int sl_) {
+        u0 = u0_; sl = sl_;
+        thr_l = reinterpret_cast<unsigned long long*>(lds) + wave * 16;
+        cnt = reinterpret_cast<int*>(lds + (size_t)NW * 16 * 8) + wave * 16;
+        hist = reinterpret_cast<unsigned*>(lds + (size_t)NW * 16 * 12) + wave * 256;
+        if (lane < 16) { cnt[lane] = 0; thr_l[lane] = 0ull; }
+        buf0 = row_buf(u0 + 4 * q);                                // (rows past the batch: never dereferenced)
+        row_stride = (int64_t)n_slices * cap;
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            thr[reg] = 0ull; seen_lo[reg] = 0; seen_hi[reg] = 0;
+            const int64_t b = u0 + 4 * q + reg;
+            if (seen_indptr && b < n_users) { seen_lo[reg] = seen_indptr[b]; seen_hi[reg] = seen_indptr[b + 1]; }
+            if constexpr (MASK) {
+                const int32_t g = b < n_users ? (allow_idx ? allow_idx[b] : 0) : -1;
+                words[reg] = g >= 0 ? allow_bits + (int64_t)g * allow_words : nullptr;
+            }
+        }
+        wmf_wave_sync();
+    }
+    __device__ __forceinline__ void score(int reg, int, int64_t item, unsigned long long key, bool in_range) {
+        bool take = in_range && u0 + 4 * q + reg < n_users && key > thr[reg];
+        if constexpr (MASK) {
+            if (take && words[reg]) take = (words[reg][item >> 5] >> (item & 31)) & 1u;
+        }
+        if (take && seen_lo[reg] < seen_hi[reg]) {
+            int64_t lo = seen_lo[reg], hi = seen_hi[reg];
+            while (lo < hi) {                                      // first entry >= item
+                const int64_t mid = (lo + hi) >> 1;
+                if (seen_indices[mid] < (int32_t)item) lo = mid + 1; else hi = mid;
+            }
+            take = !(lo < seen_hi[reg] && seen_indices[lo] == (int32_t)item);
+        }
+        if (take) {
+            const int slot = atomicAdd(&cnt[4 * q + reg], 1);      // at most 16 per row and tile: below cap
+            if (slot < cap) buf0[reg * row_stride + slot] = key;
+        }
+    }
+    // The buffers of the wave's rows in `full` (bit u = row u of 16) cut back to their topn best: the topn-th largest key T, then the
+    // keys >= T moved to the front, 64 at a time.  A chunk is loaded before any of its keys is stored (the store's data depends on
+    // the load), and it is stored at or below where it was read, so no key is overwritten before it is read.
+    __device__ __forceinline__ void cut(unsigned full) {
+        rec_wide_drain();                                          // the keys other lanes appended
+        while (full) {
+            const int u = __builtin_ctz(full);
+            full &= full - 1;
+            unsigned long long* ku = row_buf(u0 + u);
+            const int n = min(cnt[u], cap);
+            const unsigned long long T = rec_wide_kth<64>(ku, nullptr, 1, 0, n, cap, topn, hist, lane);
+            int out = 0;
+            for (int e0 = 0; e0 < n; e0 += 64) {
+                const unsigned long long key = e0 + lane < n ? ku[e0 + lane] : 0ull;
+                const bool keep = key >= T && e0 + lane < n;
+                const unsigned long long m = __ballot(keep);
+                if (keep) ku[out + __popcll(m & ((1ull << lane) - 1ull))] = key;
+                out += __popcll(m);
+            }
+            if (lane == 0) { cnt[u] = topn; thr_l[u] = T; }
+        }
+        rec_wide_drain();                                          // the compacted keys before the next appends and the next cut
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) thr[reg] = thr_l[4 * q + reg];
+    }
+    __device__ __forceinline__ void tile(int) {
+        wmf_wave_sync();
+        const unsigned full = (unsigned)(__ballot(cnt[r] > cap - 16) & 0xFFFFull);
+        if (full) cut(full);
+    }
+    __device__ __forceinline__ void end() {
+        wmf_wave_sync();
+        if (lane < 16 && u0 + lane < n_users) counts_ws[(u0 + lane) * n_slices + sl] = min(cnt[lane], cap);
+        wmf_wave_sync();                                           // the counts are read before the next pair resets them
+    }
+};
+
+// ---- sizes ------------------------------------------------------------------------------------------------------------------
+#define WMF_REC_WIDE_WAVES 4                                       /* waves of a wide scan's workgroup: one value, no switch */
+// (the keys of a buffer: WMF_RECOMMEND_WIDE_CAP(topn) of include/wmf_hip.h, >= topn + 16)
+// dynamic LDS of a scan with this epilogue, past the stages
+__host__ __device__ static inline size_t rec_wide_lds_bytes(int nw) { return (size_t)nw * 16 * 12 + (size_t)nw * 256 * 4; }

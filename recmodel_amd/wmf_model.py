@@ -33,7 +33,9 @@ def _csr_parts(mat):
 F64_ROW_WEIGHT = 1024.0
 
 RECOMMEND_BATCH_USERS = 4096      # users per wmf_recommend_topn call of WMF.recommend (its workspace is 8 x 64 x topn bytes a user)
-RECOMMEND_MAX_TOPN = 128          # WMF_RECOMMEND_MAX_TOPN of include/wmf_hip.h: beyond it recommend() ranks user by user
+RECOMMEND_MAX_TOPN = 128          # WMF_RECOMMEND_MAX_TOPN of include/wmf_hip.h: beyond it recommend() takes the kernels of candidates()
+CANDIDATES_MAX = 4096             # WMF_RECOMMEND_WIDE_MAX_TOPN of include/wmf_hip.h: the limit of candidates() and of recommend()'s device path
+CANDIDATES_WS_BYTES = 1 << 30     # the workspace of one wmf_recommend_topn_wide call at most: candidates() takes fewer rows per call
 RANKPOS_MAX_TARGETS = 16          # WMF_RANKPOS_MAX_TARGETS of include/wmf_hip.h: rank_positions() splits longer rows
 EXPLAIN_MAX_TARGETS = 16          # WMF_EXPLAIN_MAX_TARGETS of include/wmf_hip.h: explain() splits longer target lists
 
@@ -358,7 +360,15 @@ class WMF(RecModel):
         call costs whatever the filter passes (2048 users, a million items, k = 128 + biases, topn 10 on an MI355X: 10.4 .. 11.4 ms
         against 11.0 ms, -4 .. +4.5 % on the scan kernel); the list form 0.55 ms for 99 ids, 1.03 ms for 10 000, 9.8 ms for
         500 000 and 18.2 ms for all million -- the two cross at about 575 000 ids, so a filter that passes more than half of the
-        catalogue is faster as a mask (profiles/r19_recommend_filtered.json)."""
+        catalogue is faster as a mask (profiles/r19_recommend_filtered.json).
+        ``topn`` beyond RECOMMEND_MAX_TOPN (128) and up to CANDIDATES_MAX (4096) is served on the device as well, by the kernels of
+        ``candidates`` (wmf_recommend_topn_wide): the same scores and the same order.  Only beyond CANDIDATES_MAX are the users
+        ranked one by one through ``rank`` and ``predict``."""
+        return self._recommend(users, topn, exclude, return_scores, allow, allow_idx, False)
+
+    def _recommend(self, users, topn, exclude, return_scores, allow, allow_idx, wide):
+        """``recommend`` (wide False: the LDS kernels up to RECOMMEND_MAX_TOPN, the wide ones up to CANDIDATES_MAX, the host loop
+        beyond) and ``candidates`` (wide True: the wide kernels for every topn)."""
         n_users_model, n_items = self.users.shape[0], self.items.shape[0]
         seen = None
         if exclude is not None:
@@ -378,8 +388,8 @@ class WMF(RecModel):
             seen.sort_indices()
         if len(u) == 0 or (filt is not None and filt.empty):
             pass
-        elif topn > RECOMMEND_MAX_TOPN:
-            # beyond the fused kernel's buffers: the reference's formulation, user by user
+        elif topn > CANDIDATES_MAX:
+            # beyond the device's buffers: the reference's formulation, user by user
             everything = np.arange(n_items, dtype=np.int32)
             for j, user in enumerate(u):
                 cand = everything if filt is None else filt.allowed(j)
@@ -389,25 +399,36 @@ class WMF(RecModel):
                 out_items[j, :len(best)] = best
                 if return_scores and len(best):
                     out_scores[j, :len(best)] = self.predict([int(user)], best)
-        else:
-            self._recommend_fused(u, topn, seen, out_items, out_scores if return_scores else None, filt)
+        else:                                                      # (beyond RECOMMEND_MAX_TOPN: the wide kernels, as candidates())
+            self._recommend_fused(u, topn, seen, out_items, out_scores if return_scores else None, filt, wide=wide or topn > RECOMMEND_MAX_TOPN)
         if one:
             out_items, out_scores = out_items[0], out_scores[0]
         return (out_items, out_scores) if return_scores else out_items
 
-    def _scan_batches(self, ids, csrs, ws_bytes, outs, call):
+    def candidates(self, users, n=1000, exclude=None, return_scores=False, allow=None, allow_idx=None):
+        """The candidate pool of a two-stage recommender, the lists behind Recall@500: the ``n`` best items of the whole catalogue
+        for each of ``users``, 1 <= n <= CANDIDATES_MAX (4096; a ValueError otherwise, before the GPU is asked for).  The
+        arguments, order, padding (-1 / -inf) and dtypes of ``recommend``; always served by wmf_recommend_topn_wide, whose running
+        keys live in device memory instead of LDS, so for n <= RECOMMEND_MAX_TOPN it returns what ``recommend`` returns, bit for
+        bit, from other kernels.  Rows per call are bounded by RECOMMEND_BATCH_USERS and by a workspace of CANDIDATES_WS_BYTES."""
+        n = int(n)
+        if n < 1 or n > CANDIDATES_MAX:
+            raise ValueError(f"n must be between 1 and {CANDIDATES_MAX}, not {n}")
+        return self._recommend(users, n, exclude, return_scores, allow, allow_idx, True)
+
+    def _scan_batches(self, ids, csrs, ws_bytes, outs, call, max_rows=None):
         """The batch loop of the fused catalogue calls (recommend, the neighbours, rank_positions): windows of
         RECOMMEND_BATCH_USERS rows, all enqueued on one stream, one copy to the host at the end.  ``ids``: the row of the factors
         each batch position reads; ``csrs``: per-position lists as (indptr, indices), or None, uploaded once; ``ws_bytes(rows)``:
         the workspace of a batch; ``outs``: the device outputs (None: not asked for).  ``call(b0, nb, ids, csrs, ws, ws_bytes,
         stream)`` enqueues the nb positions from b0 on: pointers to the ids from b0 on and, for each CSR, to the window of its
-        pointers and to its one indices array (None, None without it) -- row b of the batch is row b0 + b.  Returns the host
-        copies of ``outs``."""
+        pointers and to its one indices array (None, None without it) -- row b of the batch is row b0 + b.  ``max_rows``: a
+        further bound on the rows of a window.  Returns the host copies of ``outs``."""
         n = len(ids)
         ids_d = torch.from_numpy(ids.astype(np.int32)).cuda()
         csrs_d = [None if c is None else (torch.from_numpy(c[0].astype(np.int64)).cuda(),         # (one spare index: never empty)
                                           torch.from_numpy(np.append(c[1], 0).astype(np.int32)).cuda()) for c in csrs]
-        per = max(1, int(RECOMMEND_BATCH_USERS))
+        per = max(1, min(int(RECOMMEND_BATCH_USERS), int(max_rows or RECOMMEND_BATCH_USERS)))
         nbytes = int(ws_bytes(min(per, n)))
         ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
         for b0 in range(0, n, per):
@@ -416,22 +437,34 @@ class WMF(RecModel):
             _lib.check(call(b0, nb, _ptr(ids_d[b0:]), windows, _ptr(ws), nbytes, _stream()))
         return [o if o is None else o.cpu().numpy() for o in outs]
 
-    def _recommend_fused(self, u, topn, seen, out_items, out_scores, filt=None):
+    def _recommend_fused(self, u, topn, seen, out_items, out_scores, filt=None, wide=False):
         """wmf_recommend_topn in batches (_scan_batches); the rows of ``seen`` are those of ``u``.  ``filt``: an _Allow, then
-        wmf_recommend_topn_filtered."""
+        wmf_recommend_topn_filtered.  ``wide``: wmf_recommend_topn_wide, with or without a filter."""
         users_t, items_t, f, ld = self._device_factors()
-        out_items[:], scores = self._recommend_scan(users_t, items_t, f, ld, u, topn, seen, out_scores is not None, filt)
+        out_items[:], scores = self._recommend_scan(users_t, items_t, f, ld, u, topn, seen, out_scores is not None, filt, wide)
         if out_scores is not None:
             out_scores[:] = scores
 
-    def _recommend_scan(self, users_t, items_t, f, ld, u, topn, seen, want_scores, filt):
+    def _recommend_scan(self, users_t, items_t, f, ld, u, topn, seen, want_scores, filt, wide=False):
         """The fused top-n of the rows ``u`` of the device matrix ``users_t`` in batches (_scan_batches): wmf_recommend_topn, or with
         a filter wmf_recommend_topn_filtered -- its masks or ids uploaded once, the allow_idx window moving with the ids'.  Returns
-        the host (items, scores or None)."""
+        the host (items, scores or None).  ``wide``: wmf_recommend_topn_wide for either, in windows whose workspace stays within
+        CANDIDATES_WS_BYTES (one row at least)."""
         lib = _lib.load()
         items_d = torch.empty(len(u), topn, dtype=torch.int32, device="cuda")
         scores_d = torch.empty(len(u), topn, dtype=torch.float32, device="cuda") if want_scores else None
         head = (_ptr(users_t), _ptr(items_t), f, ld, int(self.bias is True))
+        if wide:
+            at = filt.upload() if filt is not None else (lambda b0: (None, 0, 0, None, None, 0))
+
+            def call(b0, nb, ids, csrs, *ws):
+                return lib.wmf_recommend_topn_wide(*head, ids, nb, self.items.shape[0], *csrs[0], *at(b0), topn, 0, _ptr(items_d[b0:]),
+                                                   _ptr(scores_d[b0:]) if scores_d is not None else None, None, *ws)
+            need = lambda rows: int(lib.wmf_recommend_wide_workspace_bytes(rows, topn, 0))   # noqa: E731
+            rows = max(1, min(len(u), int(RECOMMEND_BATCH_USERS)))
+            while rows > 1 and need(rows) > CANDIDATES_WS_BYTES:   # (it grows with the rows: halve until a window fits)
+                rows //= 2
+            return self._scan_batches(u, [None if seen is None else (seen.indptr, seen.indices)], need, [items_d, scores_d], call, rows)
         if filt is None:
             def call(b0, nb, ids, csrs, *ws):
                 return lib.wmf_recommend_topn(*head, ids, nb, self.items.shape[0], *csrs[0], topn, 0, _ptr(items_d[b0:]),
@@ -810,10 +843,25 @@ class WMF(RecModel):
         ``fold_in(count_rows)``, bit for bit.  A row whose fold-in failed (NaN factors) is all -1 / -inf.  ``topn`` is at most
         RECOMMEND_MAX_TOPN: a larger one is a ValueError.  ``allow`` / ``allow_idx``: the catalogue filter of ``recommend``
         (``allow_idx`` has one entry per row of ``count_rows``), with the same identity."""
+        return self._recommend_for(count_rows, topn, RECOMMEND_MAX_TOPN, "topn", exclude_history, return_scores, alpha, beta,
+                                   pre_process_count, allow, allow_idx)
+
+    def candidates_for(self, count_rows, n=1000, exclude_history=True, return_scores=False, alpha=10, beta=1,
+                       pre_process_count='log', allow=None, allow_idx=None):
+        """``candidates`` for histories instead of user ids, as ``recommend_for`` is to ``recommend``: the rows of ``count_rows``
+        are folded in on the device -- the factors never leave it -- and the ``n`` best items of the catalogue are found for each,
+        1 <= n <= CANDIDATES_MAX (4096; a ValueError otherwise, before the GPU is asked for).  The arguments, padding and dtypes of
+        ``recommend_for``; a row whose fold-in failed is all -1 / -inf.  Bit for bit the output of ``candidates`` on a model whose
+        ``users`` are ``fold_in(count_rows)``."""
+        return self._recommend_for(count_rows, n, CANDIDATES_MAX, "n", exclude_history, return_scores, alpha, beta, pre_process_count,
+                                   allow, allow_idx)
+
+    def _recommend_for(self, count_rows, topn, limit, name, exclude_history, return_scores, alpha, beta, pre_process_count, allow, allow_idx):
+        """recommend_for (limit RECOMMEND_MAX_TOPN: the LDS kernels) and candidates_for (limit CANDIDATES_MAX: the wide ones)."""
         mat, mode = self._foldin_arguments(count_rows, pre_process_count)
         topn = int(topn)
-        if topn < 1 or topn > RECOMMEND_MAX_TOPN:
-            raise ValueError(f"topn must be between 1 and {RECOMMEND_MAX_TOPN}, not {topn}")
+        if topn < 1 or topn > limit:
+            raise ValueError(f"{name} must be between 1 and {limit}, not {topn}")
         B = mat.shape[0]
         filt = None if allow is None and allow_idx is None else _Allow(allow, allow_idx, self.items.shape[0], B, "item")
         _lib.require_gpu()
@@ -825,7 +873,8 @@ class WMF(RecModel):
             if exclude_history:
                 seen = mat.copy()                                  # the seen list as ``recommend`` prepares ``exclude``
                 seen.sort_indices()
-            got_items, got_scores = self._recommend_scan(X_d, items_t, f, ld, np.arange(B, dtype=np.int64), topn, seen, return_scores, filt)
+            got_items, got_scores = self._recommend_scan(X_d, items_t, f, ld, np.arange(B, dtype=np.int64), topn, seen, return_scores, filt,
+                                                         limit == CANDIDATES_MAX)
             good = ~torch.isnan(X_d[:, :f]).any(dim=1).cpu().numpy()
             out_items[good] = got_items[good]
             if return_scores:

@@ -4,6 +4,7 @@ segmented sort, wmf_rank_topn_batch, in batches of 2^26 scores.
 
 Usage: python tools/recommend_lab.py [--out FILE] [--reps 5] [--topn 10] [users,items,k,bias ...]
        python tools/recommend_lab.py --filters [--out FILE] [--reps 5] [--topn 10] [users,items,k,bias]
+       python tools/recommend_lab.py --wide [--out FILE] [--reps 5] [items,k,bias]
 
 Both paths run in one process on the same seeded Gaussian factors, without exclusions; after a warm-up of each they are timed
 in alternating repetitions with a host clock that ends in a device synchronise; median and spread (max - min) per path.  The two
@@ -19,7 +20,14 @@ parent's scan kernel, unchanged) in alternating repetitions of one process, and 
 complement of the filter appended to ``exclude`` through the unfiltered call, for the first COMPLEMENT_USERS users (for all of them
 the seen list would be about 8 GB), and rank(allowed, users, topn), which knows no seen items.  The answers are compared on the
 spot: filtered against complement-in-exclude bit for bit, rank under the rounded-class rule against the list form without a seen
-list.  Then the list form at a ladder of list lengths against the mask form of the same list: where the two cross."""
+list.  Then the list form at a ladder of list lengths against the mask form of the same list: where the two cross.
+
+--wide: WMF.candidates and the device path of WMF.recommend beyond 128 (wmf_recommend_topn_wide) at 1 000 000 items, k = 128 +
+biases, 10 seen items per row, 2048 and 16 users, every pair of routes in alternating repetitions of one process: (1) 16 users at
+topn 200, this commit's recommend against the parent's, the host loop over rank() and predict(), which is still the code beyond
+CANDIDATES_MAX and is reached by lowering that constant for the call; (2) topn 128 through wmf_recommend_topn and through the wide
+kernels, scan and selection kernel apart from the library's wmf_profile_* table; (3) the ladder topn 129 .. 4096 with the automatic
+slice count, the workspace and the rows of a call; (4) the mask form at a 1 % pass rate and the list form of 10 000 ids at topn 1000."""
 import argparse
 import json
 import statistics
@@ -219,14 +227,138 @@ def run_filters(n_users, n_items, k, bias, topn, reps):
     return rec
 
 
+WIDE_LADDER = (129, 256, 512, 1000, 2048, 4096)
+WIDE_USERS = (2048, 16)
+
+
+def wide_slices(n_users, n_scan, topn):
+    """The automatic slice count of wmf_recommend_topn_wide, from the constants and the rule of include/wmf_hip.h."""
+    import re
+    header = open("include/wmf_hip.h").read()
+    c = {n: int(re.search(rf"#define\s+WMF_RECOMMEND_WIDE_{n}\s+(\d+)", header).group(1)) for n in ("AUTO_SLICES", "AUTO_LISTS", "SLICE_TOPNS")}
+    s0 = min(c["AUTO_SLICES"] * n_users, max(c["AUTO_LISTS"], n_users)) // n_users
+    slice_items = max(1024, c["SLICE_TOPNS"] * topn)
+    return max(1, min(s0, -(-((n_scan + 15) // 16) // -(-slice_items // 16))))
+
+
+def kernel_split(lib, fn):
+    """(scan seconds, selection or merge seconds, names) of one call of fn."""
+    k = scan_kernel_s(lib, fn)
+    return (sum(v for nm, v in k.items() if nm.startswith("recommend_scan")),
+            sum(v for nm, v in k.items() if nm.startswith(("recommend_select", "recommend_merge"))), sorted(k))
+
+
+def alternate(routes, reps):
+    """{name: stats} of the routes timed in alternating repetitions, after one warm-up each."""
+    for fn in routes.values():
+        timed(fn)
+    t = {name: [] for name in routes}
+    for _ in range(reps):
+        for name, fn in routes.items():
+            t[name].append(timed(fn)[0])
+    return {name: stats(ts) for name, ts in t.items()}
+
+
+def run_wide(n_items, k, bias, reps):
+    from recmodel_amd import wmf_model
+    rng = np.random.default_rng(1000 * k + bias)
+    f = k + bias
+    n_all = max(WIDE_USERS)
+    m = WMF(num_items=8, num_users=n_all, dim=k, gamma=0.1, weighted=True, bias=bool(bias))
+    m.users, m.items = rng.standard_normal((n_all, f), dtype=np.float32), rng.standard_normal((n_items, f), dtype=np.float32)
+    m.num_items = n_items
+    m.users.flags.writeable = m.items.flags.writeable = False
+    seen = sp.csr_matrix((np.ones(10 * n_all, dtype=np.float32), rng.integers(0, n_items, 10 * n_all), 10 * np.arange(n_all + 1)),
+                         shape=(n_all, n_items))
+    seen.sum_duplicates()
+    lib = _lib.load()
+    rec = {"items": n_items, "k": k, "bias": bias, "seen_per_user": 10}
+
+    # 1. the gate: 16 users, topn 200, the parent's host loop against the device path
+    few = np.arange(16)
+
+    def parent_200():
+        limit = wmf_model.CANDIDATES_MAX
+        wmf_model.CANDIDATES_MAX = wmf_model.RECOMMEND_MAX_TOPN        # the parent's routing: beyond 128, user by user
+        try:
+            return m.recommend(few, 200, exclude=seen, return_scores=True)
+        finally:
+            wmf_model.CANDIDATES_MAX = limit
+    new_200 = lambda: m.recommend(few, 200, exclude=seen, return_scores=True)  # noqa: E731
+    a, b = parent_200(), new_200()
+    sa, ba = scores64(m, few, a[0])
+    sb, bb = scores64(m, few, b[0])
+    gate = alternate({"parent_host_loop": parent_200, "wide_device_path": new_200}, reps)
+    gate["same_items_fraction"] = float((a[0] == b[0]).mean())
+    gate["order_gap_over_bound"] = float((np.abs(sa - sb) / np.maximum(ba, bb)).max())
+    gate["parent_over_wide"] = gate["parent_host_loop"]["median_s"] / gate["wide_device_path"]["median_s"]
+    gate["wide_faster_beyond_spread"] = bool(gate["parent_host_loop"]["median_s"] - gate["wide_device_path"]["median_s"]
+                                             > max(gate["parent_host_loop"]["spread_s"], gate["wide_device_path"]["spread_s"]))
+    assert gate["order_gap_over_bound"] <= 1.0, gate
+    rec["topn200_16_users"] = gate
+    print(json.dumps({"topn200_16_users": {key: (v["median_s"] if isinstance(v, dict) else v) for key, v in gate.items()}}), flush=True)
+
+    # 2. the price of the workspace buffers at topn 128, and 3. the ladder
+    rec["topn128"], rec["ladder"] = [], []
+    for n_users in WIDE_USERS:
+        users = np.arange(n_users)
+        routes = {"fused": lambda: m.recommend(users, 128, exclude=seen, return_scores=True),
+                  "wide": lambda: m.candidates(users, 128, exclude=seen, return_scores=True)}
+        assert same_bits(routes["fused"](), routes["wide"]())
+        entry = {"users": n_users, **alternate(routes, reps)}
+        for name, fn in routes.items():
+            scan, tail, names = kernel_split(lib, fn)
+            entry[name + "_kernels"] = {"scan_s": scan, "select_or_merge_s": tail, "names": names}
+        entry["wide_scan_over_fused_scan"] = entry["wide_kernels"]["scan_s"] / entry["fused_kernels"]["scan_s"]
+        rec["topn128"].append(entry)
+        print(json.dumps({key: (v["median_s"] if isinstance(v, dict) and "median_s" in v else v) for key, v in entry.items()}), flush=True)
+        for topn in WIDE_LADDER:
+            fn = lambda: m.candidates(users, topn, exclude=seen, return_scores=True)  # noqa: E731
+            rows = n_users
+            while rows > 1 and lib.wmf_recommend_wide_workspace_bytes(rows, topn, 0) > wmf_model.CANDIDATES_WS_BYTES:
+                rows //= 2
+            step = {"users": n_users, "topn": topn, "rows_per_call": rows, "auto_slices": wide_slices(rows, n_items, topn),
+                    "workspace_bytes": int(lib.wmf_recommend_wide_workspace_bytes(rows, topn, 0)), **alternate({"call": fn}, reps)}
+            step["scan_s"], step["select_s"], _ = kernel_split(lib, fn)
+            rec["ladder"].append(step)
+            print(json.dumps({key: (v["median_s"] if isinstance(v, dict) else v) for key, v in step.items()}), flush=True)
+
+    # 4. the filtered forms at topn 1000
+    users = np.arange(n_all)
+    mask = rng.random(n_items) < 0.01
+    ids = np.sort(rng.choice(n_items, 10000, replace=False))
+    routes = {"unfiltered": lambda: m.candidates(users, 1000, exclude=seen, return_scores=True),
+              "mask_1_percent": lambda: m.candidates(users, 1000, exclude=seen, return_scores=True, allow=mask),
+              "list_10000_ids": lambda: m.candidates(users, 1000, exclude=seen, return_scores=True, allow=ids)}
+    filt = {"users": n_all, "topn": 1000, "mask_allowed": int(mask.sum()), **alternate(routes, reps)}
+    for name, fn in routes.items():
+        scan, tail, names = kernel_split(lib, fn)
+        filt[name + "_kernels"] = {"scan_s": scan, "select_s": tail, "names": names}
+    list_mask = np.zeros(n_items, dtype=bool)
+    list_mask[ids] = True
+    filt["list_equals_its_mask_bits"] = same_bits(routes["list_10000_ids"](), m.candidates(users, 1000, exclude=seen, return_scores=True, allow=list_mask))
+    assert filt["list_equals_its_mask_bits"]
+    rec["filters_topn1000"] = filt
+    print(json.dumps({key: (v["median_s"] if isinstance(v, dict) and "median_s" in v else v) for key, v in filt.items()}), flush=True)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the full record to this file")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--topn", type=int, default=10)
     ap.add_argument("--filters", action="store_true", help="the catalogue filters at one shape (default 2048,1000000,128,1)")
+    ap.add_argument("--wide", action="store_true", help="candidates() and recommend() beyond 128 (default 1000000,128,1)")
     ap.add_argument("shapes", nargs="*", default=None)
     args = ap.parse_args()
+    if args.wide:
+        n_items, k, bias = (int(x) for x in (args.shapes or ["1000000,128,1"])[0].split(","))
+        out = {"device": torch.cuda.get_device_name(0), "method": __doc__.split("\n\n")[4], "wide": run_wide(n_items, k, bias, args.reps)}
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(out, fh, indent=1)
+        return
     if args.filters:
         n_users, n_items, k, bias = (int(x) for x in (args.shapes or [DEFAULT_SHAPES[1]])[0].split(","))
         out = {"device": torch.cuda.get_device_name(0), "method": __doc__.split("\n\n")[3],
