@@ -489,6 +489,66 @@ int wmf_similar_topn_filtered(const float* queries, const float* catalogue, int 
                               int32_t* out_rows, float* out_scores, int32_t* out_count,
                               void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Diversified top-n: greedy Maximal Marginal Relevance (Carbonell & Goldstein 1998) over a candidate pool, the second stage behind
+ * wmf_recommend_topn_wide.  A pure top-n of a factor model returns near-duplicates; MMR picks items one by one and trades the
+ * relevance of a candidate against its highest similarity to what is already picked.  The reference has no counterpart.  Needs the
+ * item factors only: nothing of size rows x pool x f is ever stored.
+ * Inputs: all arrays on the device, `items` [n_items, ld] in the library's layout.  Row b owns pool_items[b * pool .. b * pool + pool)
+ *   and the pool_scores at the same places: the layout wmf_recommend_topn_wide(topn = pool) writes.
+ * Candidates: the candidates of row b are its leading c_b = pool_count[b] entries (values in [0, pool]); pool_count == NULL: all
+ *   `pool` entries.  Candidates are numbered by their position j.  Ids lie in [0, n_items); an id listed twice is two candidates.
+ *   r_j = pool_scores[b, j] is taken as given: nothing is scored again.
+ * Similarity: d(j, s) = the sum over the columns c in [bias, f) of items[id_j, c] * items[id_s, c], in ONE order: of 16 lanes, lane
+ *   g takes the 16-byte pieces g, g + 16, ... of the two rows in turn and the four columns of a piece in ascending order, each product
+ *   added by one fused multiply-add into the lane's float32 sum (which starts at +0; a column outside [bias, f) enters as a zero
+ *   factor); the 16 sums are then added by the butterfly of wmf_predict_pairs, s += s[lane ^ 1], s += s[lane ^ 2], s += s[7 - lane]
+ *   within each half of eight lanes, s += s[15 - lane].  With bias != 0 column 0 is the bias and no
+ *   feature.  inv_norm == NULL: sim = d (dot product).  inv_norm = wmf_row_inv_norms(items): sim(j, s) = (d * inv_norm[id_j]) *
+ *   inv_norm[id_s] (cosine) -- two float32 multiplications in exactly that order, as in wmf_similar_topn; j is the candidate, s the
+ *   pick.
+ * Greedy selection: mu = 1.0f - lambda in float32.  Step 0: v_j = lambda * r_j.  Step t >= 1: m_j = the largest sim(j, s_i) over the
+ *   picks s_0 .. s_{t-1} so far (the first one as it is; a later one replaces m_j only where it compares greater), and v_j = lambda * r_j
+ *   - mu * m_j: three separately rounded float32 operations, never a fused multiply-add.  Every step takes the remaining candidate
+ *   with the largest v; equal v go to the lower position and -0.0 equals +0.0 (the key of wmf_recommend_topn on v, with the
+ *   position in the place of the item id: the library's one total order).  A picked position is never picked again.
+ * Outputs: out_count[b] (may be NULL) = min(topn, c_b); out_items[b * topn + k] = the id of pick k; out_scores[b * topn + k] (may be
+ *   NULL) = the bits of r of pick k; out_marginal[b * topn + k] (may be NULL) = the v it was picked with; entries past the count hold
+ *   -1, -inf, -inf.  lambda = 1 returns the pool's prefix when the pool is sorted (as wmf_recommend_topn_wide leaves it).
+ * Limits: 1 <= pool <= WMF_MMR_MAX_POOL, 1 <= topn <= WMF_RECOMMEND_MAX_TOPN, 0 <= lambda <= 1, n_rows >= 1, 1 <= n_items < 2^31.
+ * Kernels: one workgroup per row; r_j, m_j, the id with its taken flag and the inverse norm live in LDS (16 bytes a candidate).  pool <=
+ *   wmf_rerank_mmr_resident_pool(f, ld) -- pure host code, the rows that fit the 160 KB of a CU beside that state; it does not grow
+ *   with ld -- takes the RESIDENT kernel: the candidates' rows are gathered into LDS once and every step reads them there (bytes read
+ *   from the table: rows x pool x row).  A larger pool takes the STREAMING kernel, which reads the rows from the table again each
+ *   step (rows x pool x (picks - 1) x row).  One body: the two give the same bits; the routing is a function of (f, ld, pool) alone.
+ * Determinism: a row's result is a function of that row's inputs alone, not of the batch, the row's position, the grid or timing.
+ * The call only enqueues: it does not allocate, synchronise or read back.  WMF_EINVAL, before any HIP call and with the outputs
+ * untouched, for a bad shape, a null pointer, lambda outside [0, 1] or NaN, topn or pool out of range.  Factors, scales and scores
+ * are finite; non-finite scores or similarities are unspecified, but every index written is in range. */
+#define WMF_MMR_MAX_POOL 4096
+int64_t wmf_rerank_mmr_resident_pool(int f, int ld);
+int wmf_rerank_mmr(const float* items, int64_t n_items, int f, int ld, int bias,
+                   const float* inv_norm,
+                   const int32_t* pool_items, const float* pool_scores, const int32_t* pool_count,
+                   int64_t n_rows, int64_t pool,
+                   float lambda, int64_t topn,
+                   int32_t* out_items, float* out_scores, float* out_marginal, int32_t* out_count,
+                   void* stream);
+
+/* Intra-list similarity, the measure a diversified list is judged by: for row b, over the unordered pairs i < j of the leading n =
+ * list_count[b] entries of lists[b * width .. b * width + width) (list_count == NULL: all `width`; values in [0, width]; ids in
+ * [0, n_items), an id listed twice is two entries), sim = sim(j, i) of wmf_rerank_mmr -- the same dot, and for the cosine (d *
+ * inv_norm[id_j]) * inv_norm[id_i].  out_mean[b] = the mean of sim: S_j = the float64 sum of sim(j, i) over i = 0 .. j - 1 in that
+ * order, the total = S_1 + S_2 + ... + S_{n-1} in that order, divided in float64 by n (n - 1) / 2 and rounded to float32 once; 0 for
+ * fewer than two entries.  out_max[b] = the largest of those sims (-inf for fewer than two entries).  1 <= width <=
+ * WMF_ILS_MAX_WIDTH, n_rows >= 1, 1 <= n_items < 2^31; WMF_EINVAL before any HIP call otherwise, and for a null pointer.  Enqueues
+ * only; one workgroup per row. */
+#define WMF_ILS_MAX_WIDTH 128
+int wmf_intra_list_similarity(const float* items, int64_t n_items, int f, int ld, int bias,
+                              const float* inv_norm,
+                              const int32_t* lists, const int32_t* list_count,
+                              int64_t n_rows, int64_t width,
+                              float* out_mean, float* out_max, void* stream);
+
 /* The exact place of held-out items in the full-catalogue order of wmf_recommend_topn: the dual query of that entry point, not
  * "which are the topn best" but "at which place does this item stand", for unsampled, train-excluded Recall / NDCG / ARHR
  * (RecModel.eval_ranking; the reference offers only the sampled Recall@N of base_model.py:100-148).  One counting pass over the

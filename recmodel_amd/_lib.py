@@ -74,6 +74,10 @@ SIGNATURES = {
     "wmf_similar_workspace_bytes": (c_i64, [c_i64, c_i64, c_int]),
     "wmf_similar_topn": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_i64, c_int,
                                  c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "wmf_rerank_mmr_resident_pool": (c_i64, [c_int, c_int]),
+    "wmf_rerank_mmr": (c_int, [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, ctypes.c_float, c_i64, c_vp, c_vp,
+                               c_vp, c_vp, c_vp]),
+    "wmf_intra_list_similarity": (c_int, [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "wmf_rank_positions_workspace_bytes": (c_i64, [c_i64, c_i64, c_int]),
     "wmf_rank_positions": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp,
                                    c_vp, c_i64, c_vp]),

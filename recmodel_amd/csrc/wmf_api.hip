@@ -818,6 +818,40 @@ int wmf_similar_topn_filtered(const float* queries, const float* catalogue, int 
                         "wmf_similar_topn_filtered", f, ld, "");
 }
 
+int64_t wmf_rerank_mmr_resident_pool(int f, int ld) { return wmf_mmr_resident_pool(f, ld); }
+
+int wmf_rerank_mmr(const float* items, int64_t n_items, int f, int ld, int bias, const float* inv_norm, const int32_t* pool_items,
+                   const float* pool_scores, const int32_t* pool_count, int64_t n_rows, int64_t pool, float lambda, int64_t topn,
+                   int32_t* out_items, float* out_scores, float* out_marginal, int32_t* out_count, void* stream) {
+    int rc = check_shape(f, ld);
+    if (rc) return rc;
+    if (!items || !pool_items || !pool_scores || !out_items) { wmf_set_error("wmf_rerank_mmr: null pointer"); return WMF_EINVAL; }
+    if (n_rows < 1 || n_items < 1 || n_items > 0x7fffffffLL || pool < 1 || pool > WMF_MMR_MAX_POOL || topn < 1 || topn > WMF_RECOMMEND_MAX_TOPN) {
+        wmf_set_error("wmf_rerank_mmr: need n_rows >= 1, 1 <= n_items < 2^31, 1 <= pool <= %d, 1 <= topn <= %d (n_rows=%lld, n_items=%lld, pool=%lld, topn=%lld)",
+                      WMF_MMR_MAX_POOL, WMF_RECOMMEND_MAX_TOPN, (long long)n_rows, (long long)n_items, (long long)pool, (long long)topn);
+        return WMF_EINVAL;
+    }
+    if (!(lambda >= 0.f && lambda <= 1.f)) { wmf_set_error("wmf_rerank_mmr: lambda=%g outside [0, 1]", (double)lambda); return WMF_EINVAL; }
+    return launch_error(wmf_launch_mmr(items, n_items, f, ld, bias, inv_norm, pool_items, pool_scores, pool_count, n_rows, pool, lambda, topn,
+                                       out_items, out_scores, out_marginal, out_count, (hipStream_t)stream),
+                        "wmf_rerank_mmr", f, ld, "");
+}
+
+int wmf_intra_list_similarity(const float* items, int64_t n_items, int f, int ld, int bias, const float* inv_norm, const int32_t* lists,
+                              const int32_t* list_count, int64_t n_rows, int64_t width, float* out_mean, float* out_max, void* stream) {
+    int rc = check_shape(f, ld);
+    if (rc) return rc;
+    if (!items || !lists || !out_mean || !out_max) { wmf_set_error("wmf_intra_list_similarity: null pointer"); return WMF_EINVAL; }
+    if (n_rows < 1 || n_items < 1 || n_items > 0x7fffffffLL || width < 1 || width > WMF_ILS_MAX_WIDTH) {
+        wmf_set_error("wmf_intra_list_similarity: need n_rows >= 1, 1 <= n_items < 2^31, 1 <= width <= %d (n_rows=%lld, n_items=%lld, width=%lld)",
+                      WMF_ILS_MAX_WIDTH, (long long)n_rows, (long long)n_items, (long long)width);
+        return WMF_EINVAL;
+    }
+    return launch_error(wmf_launch_ils(items, n_items, f, ld, bias, inv_norm, lists, list_count, n_rows, width, out_mean, out_max,
+                                       (hipStream_t)stream),
+                        "wmf_intra_list_similarity", f, ld, "");
+}
+
 int64_t wmf_rank_positions_workspace_bytes(int64_t n_rows, int64_t n_targets, int32_t n_slices) {
     (void)n_targets; (void)n_slices;                              // (at most WMF_RANKPOS_MAX_TARGETS a row are counted, by atomics)
     return wmf_rank_positions_ws_bytes(n_rows);

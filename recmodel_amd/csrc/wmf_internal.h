@@ -268,6 +268,14 @@ int wmf_launch_similar_filtered(const float* queries, const float* catalogue, in
                                 const int32_t* excl_indices, const uint32_t* allow_bits, int64_t allow_words, const int32_t* allow_idx,
                                 int64_t topn, int32_t n_slices, int32_t* out_rows, float* out_scores, int32_t* out_count, void* ws,
                                 hipStream_t st);
+// wmf_mmr.hip: greedy MMR re-ranking of a row's candidate pool (the resident kernel for pool <= wmf_mmr_resident_pool, the
+// streaming one beyond), and the intra-list similarity of finished lists
+int64_t wmf_mmr_resident_pool(int f, int ld);
+int wmf_launch_mmr(const float* items, int64_t n_items, int f, int ld, int bias, const float* inv_norm, const int32_t* pool_items,
+                   const float* pool_scores, const int32_t* pool_count, int64_t n_rows, int64_t pool, float lambda, int64_t topn,
+                   int32_t* out_items, float* out_scores, float* out_marginal, int32_t* out_count, hipStream_t st);
+int wmf_launch_ils(const float* items, int64_t n_items, int f, int ld, int bias, const float* inv_norm, const int32_t* lists,
+                   const int32_t* list_count, int64_t n_rows, int64_t width, float* out_mean, float* out_max, hipStream_t st);
 // wmf_rankpos.hip: exact full-catalogue ranks of target items, seen items left out
 int64_t wmf_rank_positions_ws_bytes(int64_t n_rows);
 int wmf_launch_rank_positions(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_rows,

@@ -218,6 +218,23 @@ class HipKernels:
         _lib.check(self.lib.wmf_confidence_transform(_ptr(values), values.numel(), float(alpha), float(beta), int(mode),
                                                      _stream()))
 
+    def rerank_mmr_resident_pool(self, f, ld):
+        return int(self.lib.wmf_rerank_mmr_resident_pool(f, ld))
+
+    def rerank_mmr(self, items, f, ld, bias, inv_norm, pool_items, pool_scores, pool_count, lam, topn, out_items, out_scores=None,
+                   out_marginal=None, out_count=None):
+        """Greedy MMR over the rows of pool_items / pool_scores [rows, pool] (include/wmf_hip.h, wmf_rerank_mmr); inv_norm None: the
+        dot product, else the cosine."""
+        _lib.check(self.lib.wmf_rerank_mmr(_ptr(items), items.shape[0], f, ld, int(bias), _ptr(inv_norm), _ptr(pool_items), _ptr(pool_scores),
+                                           _ptr(pool_count), pool_items.shape[0], pool_items.shape[1], float(lam), int(topn), _ptr(out_items),
+                                           _ptr(out_scores), _ptr(out_marginal), _ptr(out_count), _stream()))
+
+    def intra_list_similarity(self, items, f, ld, bias, inv_norm, lists, list_count, out_mean, out_max):
+        """Mean and largest pairwise similarity of every row of lists [rows, width] (wmf_intra_list_similarity)."""
+        _lib.check(self.lib.wmf_intra_list_similarity(_ptr(items), items.shape[0], f, ld, int(bias), _ptr(inv_norm), _ptr(lists),
+                                                      _ptr(list_count), lists.shape[0], lists.shape[1], _ptr(out_mean), _ptr(out_max),
+                                                      _stream()))
+
     def half_step_f64_workspace_bytes(self, f, m, n):
         return int(self.lib.wmf_half_step_f64_workspace_bytes(f, m, n))
 

@@ -36,6 +36,8 @@ RECOMMEND_BATCH_USERS = 4096      # users per wmf_recommend_topn call of WMF.rec
 RECOMMEND_MAX_TOPN = 128          # WMF_RECOMMEND_MAX_TOPN of include/wmf_hip.h: beyond it recommend() takes the kernels of candidates()
 CANDIDATES_MAX = 4096             # WMF_RECOMMEND_WIDE_MAX_TOPN of include/wmf_hip.h: the limit of candidates() and of recommend()'s device path
 CANDIDATES_WS_BYTES = 1 << 30     # the workspace of one wmf_recommend_topn_wide call at most: candidates() takes fewer rows per call
+MMR_MAX_POOL = 4096               # WMF_MMR_MAX_POOL of include/wmf_hip.h: the largest pool rerank_mmr() and recommend_diverse() take
+ILS_MAX_WIDTH = 128               # WMF_ILS_MAX_WIDTH of include/wmf_hip.h: the longest list of intra_list_similarity()
 RANKPOS_MAX_TARGETS = 16          # WMF_RANKPOS_MAX_TARGETS of include/wmf_hip.h: rank_positions() splits longer rows
 EXPLAIN_MAX_TARGETS = 16          # WMF_EXPLAIN_MAX_TARGETS of include/wmf_hip.h: explain() splits longer target lists
 
@@ -366,9 +368,11 @@ class WMF(RecModel):
         ranked one by one through ``rank`` and ``predict``."""
         return self._recommend(users, topn, exclude, return_scores, allow, allow_idx, False)
 
-    def _recommend(self, users, topn, exclude, return_scores, allow, allow_idx, wide):
+    def _recommend(self, users, topn, exclude, return_scores, allow, allow_idx, wide, mmr=None):
         """``recommend`` (wide False: the LDS kernels up to RECOMMEND_MAX_TOPN, the wide ones up to CANDIDATES_MAX, the host loop
-        beyond) and ``candidates`` (wide True: the wide kernels for every topn)."""
+        beyond) and ``candidates`` (wide True: the wide kernels for every topn).  ``mmr``: the checked (pool, lam, cosine) of
+        ``recommend_diverse`` -- the pool of ``candidates`` re-ranked on the device (_diverse_scan); topn is then at most
+        RECOMMEND_MAX_TOPN."""
         n_users_model, n_items = self.users.shape[0], self.items.shape[0]
         seen = None
         if exclude is not None:
@@ -400,7 +404,8 @@ class WMF(RecModel):
                 if return_scores and len(best):
                     out_scores[j, :len(best)] = self.predict([int(user)], best)
         else:                                                      # (beyond RECOMMEND_MAX_TOPN: the wide kernels, as candidates())
-            self._recommend_fused(u, topn, seen, out_items, out_scores if return_scores else None, filt, wide=wide or topn > RECOMMEND_MAX_TOPN)
+            self._recommend_fused(u, topn, seen, out_items, out_scores if return_scores else None, filt, wide=wide or topn > RECOMMEND_MAX_TOPN,
+                                  mmr=mmr)
         if one:
             out_items, out_scores = out_items[0], out_scores[0]
         return (out_items, out_scores) if return_scores else out_items
@@ -415,6 +420,154 @@ class WMF(RecModel):
         if n < 1 or n > CANDIDATES_MAX:
             raise ValueError(f"n must be between 1 and {CANDIDATES_MAX}, not {n}")
         return self._recommend(users, n, exclude, return_scores, allow, allow_idx, True)
+
+    # ------------------------------------------------------------------ a15: diversified lists
+    @staticmethod
+    def _mmr_arguments(topn, pool, lam, metric):
+        """The checks the diversified calls share, before the GPU is asked for; returns (topn, pool, lam, cosine)."""
+        if metric not in ('cosine', 'dot'):
+            raise ValueError(f"metric must be 'cosine' or 'dot', not {metric!r}")
+        topn = int(topn)
+        if topn < 1 or topn > RECOMMEND_MAX_TOPN:
+            raise ValueError(f"topn must be between 1 and {RECOMMEND_MAX_TOPN}, not {topn}")
+        pool = min(10 * topn, MMR_MAX_POOL) if pool is None else int(pool)
+        if pool < 1 or pool > MMR_MAX_POOL:
+            raise ValueError(f"pool must be between 1 and {MMR_MAX_POOL}, not {pool}")
+        lam = float(lam)
+        if not 0.0 <= lam <= 1.0:                                  # (a NaN fails both comparisons)
+            raise ValueError(f"lam must lie in [0, 1], not {lam}")
+        return topn, pool, lam, metric == 'cosine'
+
+    def recommend_diverse(self, users, topn=10, pool=None, lam=0.7, metric='cosine', exclude=None, allow=None, allow_idx=None,
+                          return_scores=False):
+        """``recommend`` with the near-duplicates thinned out: the ``pool`` best items of each user (``candidates``, with its
+        ``exclude`` / ``allow`` / ``allow_idx``) re-ranked by greedy Maximal Marginal Relevance -- items are picked one by one, each
+        the remaining candidate with the largest ``lam * score - (1 - lam) * (highest similarity to the items picked so far)``,
+        equal values in pool order.  ``metric``: the similarity, 'cosine' or 'dot' over the item features (the bias column is none).
+        ``pool=None`` is ``min(10 * topn, MMR_MAX_POOL)``; 1 <= topn <= RECOMMEND_MAX_TOPN, topn <= pool <= MMR_MAX_POOL (4096) and
+        0 <= lam <= 1, a ValueError otherwise, before the GPU is asked for.  ``lam == 1`` returns exactly what ``recommend`` returns;
+        ``lam == 0`` keeps the best item and then spreads out.  The pool never leaves the device (wmf_recommend_topn_wide into
+        wmf_rerank_mmr, per window of rows); one copy back.  Returns int64 [len(users), topn], padded with -1; with
+        ``return_scores`` also the items' float32 scores (those of ``recommend``, not the marginal values), padded with -inf."""
+        topn, pool, lam, cosine = self._mmr_arguments(topn, pool, lam, metric)
+        if pool < topn:
+            raise ValueError(f"pool ({pool}) must be at least topn ({topn})")
+        return self._recommend(users, topn, exclude, return_scores, allow, allow_idx, True, mmr=(pool, lam, cosine))
+
+    def rerank_mmr(self, pool_items, pool_scores, topn=10, lam=0.7, metric='cosine', pool_count=None, return_scores=False):
+        """Greedy Maximal Marginal Relevance over candidate pools of the caller's: ``pool_items`` [B, pool] item ids and
+        ``pool_scores`` [B, pool] their relevances, taken as given, e.g. the two outputs of ``candidates`` or the scores of another
+        model.  NumPy arrays, or torch tensors on the device (int32 ids, float32 scores), which are used as they are.  The candidates
+        of a row are its leading ``pool_count[b]`` entries; ``pool_count=None``: the entries before the row's first negative id (the
+        -1 padding of ``candidates``).  An id listed twice is two candidates.  ``topn``, ``lam``, ``metric`` and the order as in
+        ``recommend_diverse``; the pool may be shorter than ``topn`` (the rows are padded).  Returns int64 [B, topn], padded with
+        -1; with ``return_scores`` also the float32 relevances of the picks, padded with -inf.  One-dimensional inputs are one row."""
+        topn, _, lam, cosine = self._mmr_arguments(topn, 1, lam, metric)
+        if self.users is None:                                      # (the device copies are of both matrices; as in similar_items)
+            raise AttributeError("the model has no user factors yet: train it, or assign users, before re-ranking")
+        n_items = self.items.shape[0]
+        on_device = torch.is_tensor(pool_items)
+        if on_device != torch.is_tensor(pool_scores) or (pool_count is not None and torch.is_tensor(pool_count) != on_device):
+            raise ValueError("pool_items, pool_scores and pool_count must all be host arrays or all be device tensors")
+        if not on_device:
+            pool_items, pool_scores = np.asarray(pool_items), np.asarray(pool_scores)
+            if pool_items.dtype == bool or not np.issubdtype(pool_items.dtype, np.integer):
+                raise ValueError("pool_items must be an integer array")
+        elif pool_items.dtype != torch.int32 or pool_scores.dtype != torch.float32 or not pool_items.is_cuda or not pool_scores.is_cuda:
+            raise ValueError("device pools are int32 ids and float32 scores on the GPU")
+        one = pool_items.ndim == 1
+        if one:
+            pool_items, pool_scores = pool_items[None, :], pool_scores[None, :] if pool_scores.ndim == 1 else pool_scores
+        if pool_items.ndim != 2 or tuple(pool_items.shape) != tuple(pool_scores.shape):
+            raise ValueError(f"pool_items and pool_scores must have one shape [B, pool], not {tuple(pool_items.shape)} and {tuple(pool_scores.shape)}")
+        B, pool = int(pool_items.shape[0]), int(pool_items.shape[1])
+        if pool < 1 or pool > MMR_MAX_POOL:
+            raise ValueError(f"the pool must hold between 1 and {MMR_MAX_POOL} entries a row, not {pool}")
+        if not on_device:
+            if pool_items.size and (pool_items.min() < -1 or pool_items.max() >= n_items):
+                raise IndexError("item index out of bounds")
+            if np.isnan(np.asarray(pool_scores, dtype=np.float32)).any():
+                raise ValueError("pool_scores holds a NaN")
+        if pool_count is not None:
+            if tuple(pool_count.shape) != (B,):
+                raise ValueError(f"pool_count has one entry per row ({B}), not shape {tuple(pool_count.shape)}")
+            if not on_device:
+                pool_count = np.asarray(pool_count)
+                if pool_count.dtype == bool or not np.issubdtype(pool_count.dtype, np.integer):
+                    raise ValueError("pool_count must be an integer array")
+                if B and (pool_count.min() < 0 or pool_count.max() > pool):
+                    raise ValueError(f"pool_count must lie in [0, {pool}]")
+            elif pool_count.dtype != torch.int32 or not pool_count.is_cuda:
+                raise ValueError("a device pool_count is int32 on the GPU")
+        _lib.require_gpu()
+        out_items = np.full((B, topn), -1, dtype=np.int64)
+        out_scores = np.full((B, topn), -np.inf, dtype=np.float32)
+        if B:
+            if cosine:
+                _, items_t, f, ld, norms = self._device_inv_norms("items")
+            else:
+                (_, items_t, f, ld), norms = self._device_factors(), None
+            if not on_device:
+                pool_items = torch.from_numpy(np.ascontiguousarray(pool_items, dtype=np.int32)).cuda()
+                pool_scores = torch.from_numpy(np.ascontiguousarray(pool_scores, dtype=np.float32)).cuda()
+                pool_count = None if pool_count is None else torch.from_numpy(np.ascontiguousarray(pool_count, dtype=np.int32)).cuda()
+            pool_items, pool_scores = pool_items.contiguous(), pool_scores.contiguous()
+            if pool_count is None:                                 # the entries before the first negative id
+                pool_count = (pool_items >= 0).to(torch.int32).cumprod(dim=1).sum(dim=1).to(torch.int32)
+            items_d = torch.empty(B, topn, dtype=torch.int32, device="cuda")
+            scores_d = torch.empty(B, topn, dtype=torch.float32, device="cuda") if return_scores else None
+            _lib.check(_lib.load().wmf_rerank_mmr(_ptr(items_t), n_items, f, ld, int(self.bias is True), _ptr(norms), _ptr(pool_items),
+                                                  _ptr(pool_scores), _ptr(pool_count.contiguous()), B, pool, lam, topn, _ptr(items_d),
+                                                  _ptr(scores_d), None, None, _stream()))
+            out_items[:] = items_d.cpu().numpy()
+            if return_scores:
+                out_scores[:] = scores_d.cpu().numpy()
+        if one:
+            out_items, out_scores = out_items[0], out_scores[0]
+        return (out_items, out_scores) if return_scores else out_items
+
+    def intra_list_similarity(self, item_lists, metric='cosine'):
+        """How alike the items of each list are, the measure a diversified list is judged by: for every row of ``item_lists``
+        ([B, width <= ILS_MAX_WIDTH] item ids, e.g. what ``recommend`` or ``recommend_diverse`` returned; a NumPy array, or an int32
+        torch tensor on the device, used as it is) the mean and the largest similarity over the unordered pairs of its entries.
+        The first negative entry ends a list (the -1 padding); an id listed twice is two entries.  ``metric``: 'cosine' or 'dot'
+        over the item features.  Returns (mean, max), float32 [B]: 0 and -inf for a list of fewer than two items.  One workgroup
+        per list on the device (wmf_intra_list_similarity).  A one-dimensional input is one list and gives two scalars."""
+        if metric not in ('cosine', 'dot'):
+            raise ValueError(f"metric must be 'cosine' or 'dot', not {metric!r}")
+        if self.users is None:                                      # (the device copies are of both matrices; as in similar_items)
+            raise AttributeError("the model has no user factors yet: train it, or assign users, before asking for similarities")
+        n_items = self.items.shape[0]
+        on_device = torch.is_tensor(item_lists)
+        if not on_device:
+            item_lists = np.asarray(item_lists)
+            if item_lists.dtype == bool or not np.issubdtype(item_lists.dtype, np.integer):
+                raise ValueError("item_lists must be an integer array")
+        elif item_lists.dtype != torch.int32 or not item_lists.is_cuda:
+            raise ValueError("a device item_lists is int32 on the GPU")
+        one = item_lists.ndim == 1
+        if one:
+            item_lists = item_lists[None, :]
+        if item_lists.ndim != 2 or item_lists.shape[1] < 1 or item_lists.shape[1] > ILS_MAX_WIDTH:
+            raise ValueError(f"item_lists must be [B, width] with 1 <= width <= {ILS_MAX_WIDTH}, not {tuple(item_lists.shape)}")
+        if not on_device and item_lists.size and (item_lists.min() < -1 or item_lists.max() >= n_items):
+            raise IndexError("item index out of bounds")
+        _lib.require_gpu()
+        B, width = int(item_lists.shape[0]), int(item_lists.shape[1])
+        mean, top = np.zeros(B, dtype=np.float32), np.full(B, -np.inf, dtype=np.float32)
+        if B:
+            if metric == 'cosine':
+                _, items_t, f, ld, norms = self._device_inv_norms("items")
+            else:
+                (_, items_t, f, ld), norms = self._device_factors(), None
+            lists_d = item_lists.contiguous() if on_device else torch.from_numpy(np.ascontiguousarray(item_lists, dtype=np.int32)).cuda()
+            count_d = (lists_d >= 0).to(torch.int32).cumprod(dim=1).sum(dim=1).to(torch.int32)
+            mean_d = torch.empty(B, dtype=torch.float32, device="cuda")
+            top_d = torch.empty(B, dtype=torch.float32, device="cuda")
+            _lib.check(_lib.load().wmf_intra_list_similarity(_ptr(items_t), n_items, f, ld, int(self.bias is True), _ptr(norms), _ptr(lists_d),
+                                                             _ptr(count_d), B, width, _ptr(mean_d), _ptr(top_d), _stream()))
+            mean, top = mean_d.cpu().numpy(), top_d.cpu().numpy()
+        return (mean[0], top[0]) if one else (mean, top)
 
     def _scan_batches(self, ids, csrs, ws_bytes, outs, call, max_rows=None):
         """The batch loop of the fused catalogue calls (recommend, the neighbours, rank_positions): windows of
@@ -437,19 +590,57 @@ class WMF(RecModel):
             _lib.check(call(b0, nb, _ptr(ids_d[b0:]), windows, _ptr(ws), nbytes, _stream()))
         return [o if o is None else o.cpu().numpy() for o in outs]
 
-    def _recommend_fused(self, u, topn, seen, out_items, out_scores, filt=None, wide=False):
+    def _recommend_fused(self, u, topn, seen, out_items, out_scores, filt=None, wide=False, mmr=None):
         """wmf_recommend_topn in batches (_scan_batches); the rows of ``seen`` are those of ``u``.  ``filt``: an _Allow, then
-        wmf_recommend_topn_filtered.  ``wide``: wmf_recommend_topn_wide, with or without a filter."""
+        wmf_recommend_topn_filtered.  ``wide``: wmf_recommend_topn_wide, with or without a filter.  ``mmr``: _diverse_scan."""
         users_t, items_t, f, ld = self._device_factors()
-        out_items[:], scores = self._recommend_scan(users_t, items_t, f, ld, u, topn, seen, out_scores is not None, filt, wide)
+        out_items[:], scores = self._recommend_scan(users_t, items_t, f, ld, u, topn, seen, out_scores is not None, filt, wide, mmr)
         if out_scores is not None:
             out_scores[:] = scores
 
-    def _recommend_scan(self, users_t, items_t, f, ld, u, topn, seen, want_scores, filt, wide=False):
+    def _wide_rows(self, n, topn):
+        """(need, rows): the workspace of a wmf_recommend_topn_wide call as a function of its rows, and the rows of a window of
+        ``n`` positions whose workspace stays within CANDIDATES_WS_BYTES (one row at least)."""
+        lib = _lib.load()
+        need = lambda rows: int(lib.wmf_recommend_wide_workspace_bytes(rows, topn, 0))   # noqa: E731
+        rows = max(1, min(n, int(RECOMMEND_BATCH_USERS)))
+        while rows > 1 and need(rows) > CANDIDATES_WS_BYTES:       # (it grows with the rows: halve until a window fits)
+            rows //= 2
+        return need, rows
+
+    def _diverse_scan(self, users_t, items_t, f, ld, u, topn, seen, want_scores, filt, mmr):
+        """``candidates`` re-ranked without leaving the device: per window of _scan_batches, wmf_recommend_topn_wide(topn = pool)
+        into pool buffers of one window's rows -- reused by the next window, which the stream orders behind this one -- and
+        wmf_rerank_mmr from those buffers, the pool's out_count as its pool_count, into the outputs.  One copy back."""
+        pool, lam, cosine = mmr
+        lib = _lib.load()
+        norms = self._device_inv_norms("items")[4] if cosine else None
+        need, rows = self._wide_rows(len(u), pool)
+        pool_i = torch.empty(rows, pool, dtype=torch.int32, device="cuda")
+        pool_s = torch.empty(rows, pool, dtype=torch.float32, device="cuda")
+        pool_c = torch.empty(rows, dtype=torch.int32, device="cuda")
+        items_d = torch.empty(len(u), topn, dtype=torch.int32, device="cuda")
+        scores_d = torch.empty(len(u), topn, dtype=torch.float32, device="cuda") if want_scores else None
+        head = (_ptr(users_t), _ptr(items_t), f, ld, int(self.bias is True))
+        n_items = self.items.shape[0]
+        at = filt.upload() if filt is not None else (lambda b0: (None, 0, 0, None, None, 0))
+
+        def call(b0, nb, ids, csrs, *ws):
+            rc = lib.wmf_recommend_topn_wide(*head, ids, nb, n_items, *csrs[0], *at(b0), pool, 0, _ptr(pool_i), _ptr(pool_s), _ptr(pool_c), *ws)
+            if rc != _lib.WMF_OK:
+                return rc
+            return lib.wmf_rerank_mmr(_ptr(items_t), n_items, f, ld, int(self.bias is True), _ptr(norms), _ptr(pool_i), _ptr(pool_s), _ptr(pool_c),
+                                      nb, pool, lam, topn, _ptr(items_d[b0:]), _ptr(scores_d[b0:]) if scores_d is not None else None, None,
+                                      None, ws[-1])
+        return self._scan_batches(u, [None if seen is None else (seen.indptr, seen.indices)], need, [items_d, scores_d], call, rows)
+
+    def _recommend_scan(self, users_t, items_t, f, ld, u, topn, seen, want_scores, filt, wide=False, mmr=None):
         """The fused top-n of the rows ``u`` of the device matrix ``users_t`` in batches (_scan_batches): wmf_recommend_topn, or with
         a filter wmf_recommend_topn_filtered -- its masks or ids uploaded once, the allow_idx window moving with the ids'.  Returns
         the host (items, scores or None).  ``wide``: wmf_recommend_topn_wide for either, in windows whose workspace stays within
-        CANDIDATES_WS_BYTES (one row at least)."""
+        CANDIDATES_WS_BYTES (one row at least).  ``mmr``: _diverse_scan instead."""
+        if mmr is not None:
+            return self._diverse_scan(users_t, items_t, f, ld, u, topn, seen, want_scores, filt, mmr)
         lib = _lib.load()
         items_d = torch.empty(len(u), topn, dtype=torch.int32, device="cuda")
         scores_d = torch.empty(len(u), topn, dtype=torch.float32, device="cuda") if want_scores else None
@@ -460,10 +651,7 @@ class WMF(RecModel):
             def call(b0, nb, ids, csrs, *ws):
                 return lib.wmf_recommend_topn_wide(*head, ids, nb, self.items.shape[0], *csrs[0], *at(b0), topn, 0, _ptr(items_d[b0:]),
                                                    _ptr(scores_d[b0:]) if scores_d is not None else None, None, *ws)
-            need = lambda rows: int(lib.wmf_recommend_wide_workspace_bytes(rows, topn, 0))   # noqa: E731
-            rows = max(1, min(len(u), int(RECOMMEND_BATCH_USERS)))
-            while rows > 1 and need(rows) > CANDIDATES_WS_BYTES:   # (it grows with the rows: halve until a window fits)
-                rows //= 2
+            need, rows = self._wide_rows(len(u), topn)
             return self._scan_batches(u, [None if seen is None else (seen.indptr, seen.indices)], need, [items_d, scores_d], call, rows)
         if filt is None:
             def call(b0, nb, ids, csrs, *ws):
@@ -856,8 +1044,23 @@ class WMF(RecModel):
         return self._recommend_for(count_rows, n, CANDIDATES_MAX, "n", exclude_history, return_scores, alpha, beta, pre_process_count,
                                    allow, allow_idx)
 
-    def _recommend_for(self, count_rows, topn, limit, name, exclude_history, return_scores, alpha, beta, pre_process_count, allow, allow_idx):
-        """recommend_for (limit RECOMMEND_MAX_TOPN: the LDS kernels) and candidates_for (limit CANDIDATES_MAX: the wide ones)."""
+    def recommend_diverse_for(self, count_rows, topn=10, pool=None, lam=0.7, metric='cosine', exclude_history=True, return_scores=False,
+                              alpha=10, beta=1, pre_process_count='log', allow=None, allow_idx=None):
+        """``recommend_diverse`` for histories instead of user ids, as ``recommend_for`` is to ``recommend``: the rows of
+        ``count_rows`` are folded in on the device, their ``pool`` best items found (``candidates_for``) and re-ranked by greedy
+        Maximal Marginal Relevance; neither the factors nor the pool leave the device.  The arguments of ``recommend_for`` and of
+        ``recommend_diverse``; a row whose fold-in failed is all -1 / -inf.  Bit for bit the output of ``recommend_diverse`` on a
+        model whose ``users`` are ``fold_in(count_rows)``."""
+        topn, pool, lam, cosine = self._mmr_arguments(topn, pool, lam, metric)
+        if pool < topn:
+            raise ValueError(f"pool ({pool}) must be at least topn ({topn})")
+        return self._recommend_for(count_rows, topn, RECOMMEND_MAX_TOPN, "topn", exclude_history, return_scores, alpha, beta,
+                                   pre_process_count, allow, allow_idx, mmr=(pool, lam, cosine))
+
+    def _recommend_for(self, count_rows, topn, limit, name, exclude_history, return_scores, alpha, beta, pre_process_count, allow, allow_idx,
+                       mmr=None):
+        """recommend_for (limit RECOMMEND_MAX_TOPN: the LDS kernels) and candidates_for (limit CANDIDATES_MAX: the wide ones);
+        ``mmr``: the checked (pool, lam, cosine) of recommend_diverse_for (_diverse_scan)."""
         mat, mode = self._foldin_arguments(count_rows, pre_process_count)
         topn = int(topn)
         if topn < 1 or topn > limit:
@@ -874,7 +1077,7 @@ class WMF(RecModel):
                 seen = mat.copy()                                  # the seen list as ``recommend`` prepares ``exclude``
                 seen.sort_indices()
             got_items, got_scores = self._recommend_scan(X_d, items_t, f, ld, np.arange(B, dtype=np.int64), topn, seen, return_scores, filt,
-                                                         limit == CANDIDATES_MAX)
+                                                         limit == CANDIDATES_MAX, mmr)
             good = ~torch.isnan(X_d[:, :f]).any(dim=1).cpu().numpy()
             out_items[good] = got_items[good]
             if return_scores:
