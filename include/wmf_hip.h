@@ -432,6 +432,52 @@ int wmf_recommend_topn_wide(const float* users, const float* items, int f, int l
                             int32_t* out_items, float* out_scores, int32_t* out_count,
                             void* workspace, int64_t workspace_bytes, void* stream);
 
+/* One list per (row, GROUP) from ONE scan of the catalogue: the topn best items of each of n_groups shelves (genres, departments,
+ * carousels) for every row of a batch.  group_of is int32[n_items] on the device: item j is on shelf group_of[j]; any value outside
+ * [0, n_groups) -- -1, for instance -- means "on no shelf", and the item is never returned (the test is unsigned: every index
+ * derived from the value is in range whatever the caller passes).
+ * Contract: list (b, g) is, bit for bit (items, score bits, count, padding), what wmf_recommend_topn_filtered returns for row b under
+ *   the mask {j : group_of[j] == g}, intersected with the row's allow mask if any; equivalently, wmf_recommend_topn with the
+ *   complement appended to the row's seen list.  The seen list, order (a higher score wins, equal scores go to the lower id, -0.0
+ *   equals +0.0) and -1 / -inf padding are those of wmf_recommend_topn.
+ * Outputs: out_items[(b * n_groups + g) * topn + k], out_scores (may be NULL) likewise, out_count[b * n_groups + g] (may be NULL) =
+ *   min(topn, eligible unseen items of the group).
+ * Filter: the mask form of wmf_recommend_topn_filtered (allow_bits, allow_words, n_masks, allow_idx), or allow_bits == NULL for
+ *   none.  There is no list form.
+ * Limits: 1 <= n_groups <= WMF_RECOMMEND_GROUPS_MAX, 1 <= topn <= WMF_RECOMMEND_MAX_TOPN (shelves are short), otherwise those of
+ *   wmf_recommend_topn_wide.
+ * Kernels: the scan, arithmetic and keys of wmf_recommend_topn_wide (the scores are the same bits), every score computed once; a
+ *   row's running keys live in the workspace, one buffer of WMF_RECOMMEND_WIDE_CAP(topn) keys per (row, group, slice), thresholds
+ *   and counts of a wave's 16 x n_groups buffers in LDS (768 bytes per group and workgroup); wmf_recommend_topn_wide's selection
+ *   kernel then finishes the n_users * n_groups lists.
+ * Slices: 0: the automatic count of wmf_recommend_topn_wide with topn * n_groups in place of topn for the minimum slice length (with
+ *   even groups a slice then holds at least WMF_RECOMMEND_WIDE_SLICE_TOPNS x topn items of every group; uneven groups cost
+ *   insertions, never correctness); 1 .. WMF_RECOMMEND_MAX_SLICES forces it.  The result does not depend on it.
+ * Workspace: wmf_recommend_grouped_workspace_bytes(n_users, n_groups, topn, n_slices) = WMF_RECOMMEND_WIDE_WS_BASE + n_groups * L *
+ *   (WMF_RECOMMEND_WIDE_WS_PER_KEY * WMF_RECOMMEND_WIDE_CAP(topn) + WMF_RECOMMEND_WIDE_WS_PER_LIST), L the list count of
+ *   wmf_recommend_wide_workspace_bytes for the same n_users and n_slices.  Pure host code; it does not depend on n_items and grows
+ *   with each of its arguments.
+ * The call only enqueues.  WMF_EINVAL, before any HIP call and with the outputs untouched, for a null group_of, users, items,
+ *   user_idx, out_items or workspace, n_groups, topn or n_slices out of range, a workspace that is too small, and the mask-argument
+ *   refusals of wmf_recommend_topn_filtered.
+ * Measured (MI355X, 1 000 000 items, k = 128 + biases, 10 seen items per row, topn 10, shelves j mod G, whole Python calls;
+ *   profiles/r22_recommend_shelves.json): 2048 users x 16 shelves in 40.8 ms (scan 37.4, selection 1.4) where
+ *   wmf_recommend_topn_filtered with every user repeated 16 times under 16 masks takes 160.8 ms, the arrays identical; 21.7 against
+ *   40.1 ms at 4 shelves, 17.1 against 19.7 at 2, 151 ms at 64 (the repeated rows: 91 ms for 256 of the users).  Over one unfiltered
+ *   wide scan (12.8 ms) that is 1.15 x at one shelf, 1.7 x at 4, 3.2 x at 16 and 11.8 x at 64: the insertions and cuts of G buffers a
+ *   row.  The repeated rows win at one shelf (10.8 against 14.3 ms) and for a handful of rows (16 users x 16 shelves: 5.0 against
+ *   14.1 ms). */
+#define WMF_RECOMMEND_GROUPS_MAX 64
+int64_t wmf_recommend_grouped_workspace_bytes(int64_t n_users, int32_t n_groups, int64_t topn, int32_t n_slices);
+int wmf_recommend_topn_grouped(const float* users, const float* items, int f, int ld, int bias,
+                               const int32_t* user_idx, int64_t n_users, int64_t n_items,
+                               const int64_t* seen_indptr, const int32_t* seen_indices,
+                               const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks, const int32_t* allow_idx,
+                               const int32_t* group_of, int32_t n_groups,
+                               int64_t topn, int32_t n_slices,
+                               int32_t* out_items, float* out_scores, int32_t* out_count,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Inverse row norms over the FEATURE columns, the scales of a cosine (wmf_similar_topn):
  * out[i] = 1 / sqrt(S_i) rounded to float32, S_i = sum over the columns c in [bias, f) of M[i, c]^2 accumulated in float64 in a
  * fixed order (two calls give the same bits); 0 where S_i == 0 or the quotient is not a finite float32.  With bias != 0 column 0

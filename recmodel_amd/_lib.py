@@ -68,6 +68,9 @@ SIGNATURES = {
     "wmf_recommend_wide_workspace_bytes": (c_i64, [c_i64, c_i64, c_int]),
     "wmf_recommend_topn_wide": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_int, c_vp,
                                         c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "wmf_recommend_grouped_workspace_bytes": (c_i64, [c_i64, c_int, c_i64, c_int]),
+    "wmf_recommend_topn_grouped": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_int, c_vp,
+                                           c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "wmf_similar_topn_filtered": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_i64,
                                           c_int, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "wmf_row_inv_norms": (c_int, [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp]),

@@ -767,6 +767,29 @@ int wmf_recommend_topn_wide(const float* users, const float* items, int f, int l
                         "wmf_recommend_topn_wide", f, ld, "");
 }
 
+int64_t wmf_recommend_grouped_workspace_bytes(int64_t n_users, int32_t n_groups, int64_t topn, int32_t n_slices) {
+    return wmf_recommend_grouped_ws_bytes(n_users, n_groups, topn, n_slices);
+}
+
+int wmf_recommend_topn_grouped(const float* users, const float* items, int f, int ld, int bias, const int32_t* user_idx, int64_t n_users,
+                               int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* allow_bits,
+                               int64_t allow_words, int32_t n_masks, const int32_t* allow_idx, const int32_t* group_of, int32_t n_groups,
+                               int64_t topn, int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* workspace,
+                               int64_t workspace_bytes, void* stream) {
+    int rc = check_shape(f, ld);
+    if (rc) return rc;
+    const char* own = filter_refusal(allow_bits, allow_words, n_masks, allow_idx, n_items, nullptr, 0);
+    if (!own && !group_of) own = "null group_of";
+    if (!own && (n_groups < 1 || n_groups > WMF_RECOMMEND_GROUPS_MAX)) own = "need 1 <= n_groups <= WMF_RECOMMEND_GROUPS_MAX (64)";
+    if ((rc = check_scan_call("wmf_recommend_topn_grouped", users, items, user_idx, out_items, workspace, "null pointer", own, "n_users", n_users,
+                              "n_items", n_items, &topn, n_slices, workspace_bytes,
+                              [&] { return wmf_recommend_grouped_ws_bytes(n_users, n_groups, topn, n_slices); }))) return rc;
+    return launch_error(wmf_launch_recommend_grouped(users, items, ld, bias, user_idx, n_users, n_items, seen_indptr, seen_indices, allow_bits,
+                                                     allow_words, allow_idx, group_of, n_groups, topn, n_slices, out_items, out_scores,
+                                                     out_count, workspace, (hipStream_t)stream),
+                        "wmf_recommend_topn_grouped", f, ld, "");
+}
+
 int wmf_row_inv_norms(const float* M, int64_t n, int f, int ld, int bias, float* out, void* stream) {
     int rc = check_shape(f, ld);
     if (rc) return rc;

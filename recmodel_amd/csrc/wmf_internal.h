@@ -257,6 +257,13 @@ int wmf_launch_recommend_wide(const float* users, const float* items, int ld, in
                               int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* allow_bits,
                               int64_t allow_words, const int32_t* allow_idx, const int32_t* cand_idx, int64_t n_cand, int64_t topn,
                               int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* ws, hipStream_t st);
+// (... one list per (row, group) from one scan: group_of[j] = the group of item j, the mask form or no filter)
+int64_t wmf_recommend_grouped_ws_bytes(int64_t n_users, int32_t n_groups, int64_t topn, int32_t n_slices);
+int wmf_recommend_grouped_slices(int64_t n_users, int64_t n_items, int32_t n_groups, int64_t topn, int32_t n_slices);
+int wmf_launch_recommend_grouped(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
+                                 int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* allow_bits,
+                                 int64_t allow_words, const int32_t* allow_idx, const int32_t* group_of, int32_t n_groups, int64_t topn,
+                                 int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* ws, hipStream_t st);
 // wmf_similar.hip: inverse row norms, and the neighbours of rows of one factor matrix among the rows of another (dot or cosine)
 void wmf_launch_row_inv_norms(const float* M, int64_t n, int f, int ld, int bias, float* out, hipStream_t st);
 int wmf_launch_similar(const float* queries, const float* catalogue, int ld, int bias, const float* q_inv_norm, const float* c_inv_norm,

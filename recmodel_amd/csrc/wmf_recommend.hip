@@ -16,6 +16,8 @@
 //   * recommend_scan_wide_kernel, recommend_select_wide_kernel -- the same scan for 1 <= topn <= 4096 (wmf_recommend_topn_wide): the
 //                               keys of a (user, slice) pair in the workspace, cut back by an exact select (wmf_topn_wide.h), and the
 //                               selection and sort of the topn best of a user's slices.
+//   * recommend_scan_grouped_kernel -- one list per (user, group) from one scan (wmf_recommend_topn_grouped): the wide scan with a
+//                               buffer per (user, group, slice) (wmf_topn_grouped.h); recommend_select_wide_kernel finishes them.
 // The keys of a user are pairwise distinct, so the result is a function of the scores alone: it cannot depend on the number of
 // slices, the grid or the order in which workgroups, waves or LDS atomics finish.  No float atomics.
 
@@ -24,6 +26,7 @@
 #include "wmf_scan.h"
 #include "wmf_topn.h"
 #include "wmf_topn_wide.h"
+#include "wmf_topn_grouped.h"
 
 #define WMF_REC_MERGE_GRID 1024      /* workgroups of the merge, four users each */
 #define WMF_REC_SLICE_TILES 64       /* an automatic slice holds at least this many 16-item tiles */
@@ -185,6 +188,25 @@ __global__ __launch_bounds__(256) void recommend_select_wide_kernel(const unsign
     }
 }
 
+// ---- one list per (row, group): wmf_recommend_topn_grouped ----------------------------------------------------------------------
+// The wide scan with the epilogue of wmf_topn_grouped.h: the same width classes, waves and WmfModelScore, so the same score bits; a
+// row's keys in n_groups x n_slices buffers of the workspace, laid out as recommend_select_wide_kernel reads them for n_users *
+// n_groups rows.  MASK: the mask form.  There is no list form.
+template <int NIT, int TPS, int NW, bool MASK>
+__global__ __launch_bounds__(64 * NW) void recommend_scan_grouped_kernel(const float* __restrict__ users, const float* __restrict__ items, int ld,
+                                                                         int bias, const int32_t* __restrict__ user_idx, int64_t n_users,
+                                                                         int64_t n_items, const int64_t* __restrict__ seen_indptr,
+                                                                         const int32_t* __restrict__ seen_indices,
+                                                                         const uint32_t* __restrict__ allow_bits, int64_t allow_words,
+                                                                         const int32_t* __restrict__ allow_idx,
+                                                                         const int32_t* __restrict__ group_of, int n_groups, int topn, int cap,
+                                                                         int n_slices, int64_t tiles_per_slice, int64_t n_work,
+                                                                         unsigned long long* keys_ws, int32_t* counts_ws) {
+    RecTopNGrouped<TPS, NW, MASK> p{seen_indptr, seen_indices, n_users, topn, cap, n_slices, keys_ws, counts_ws, group_of, n_items, n_groups};
+    p.allow_bits = allow_bits; p.allow_words = allow_words; p.allow_idx = allow_idx;
+    wmf_catalogue_scan<NIT, TPS, NW>(users, items, ld, bias, user_idx, n_users, n_items, n_slices, tiles_per_slice, n_work, p);
+}
+
 // ---- launcher ---------------------------------------------------------------------------------------------------------------
 int64_t wmf_recommend_ws_bytes(int64_t n_users, int64_t topn, int32_t n_slices) {
     if (n_users < 1 || topn < 1 || n_slices < 0) return 256;
@@ -332,6 +354,55 @@ int wmf_launch_recommend_wide(const float* users, const float* items, int ld, in
     if (rc) return rc;
     const int64_t grid = n_users < WMF_REC_MERGE_GRID ? n_users : WMF_REC_MERGE_GRID;    // rows beyond it take another trip
     WMF_LAUNCH("recommend_select_wide_kernel", recommend_select_wide_kernel, dim3((unsigned)grid), dim3(256), 0, st, keys, counts, n_users,
+               a.n_slices, n, cap, out_items, out_scores, out_count);
+    return WMF_L_OK;
+}
+
+// ---- the grouped launcher ---------------------------------------------------------------------------------------------------
+int64_t wmf_recommend_grouped_ws_bytes(int64_t n_users, int32_t n_groups, int64_t topn, int32_t n_slices) {
+    if (n_users < 1 || n_groups < 1 || topn < 1 || n_slices < 0) return WMF_RECOMMEND_WIDE_WS_BASE;
+    const int64_t lists = n_slices == 0 ? rec_wide_auto_lists(n_users) : n_users * n_slices;
+    return WMF_RECOMMEND_WIDE_WS_BASE +
+           n_groups * lists * (WMF_RECOMMEND_WIDE_WS_PER_KEY * WMF_RECOMMEND_WIDE_CAP(topn) + WMF_RECOMMEND_WIDE_WS_PER_LIST);
+}
+
+// the slices of a grouped call: the wide rule with topn * n_groups for the minimum slice length (with even groups a slice then
+// holds at least WMF_RECOMMEND_WIDE_SLICE_TOPNS x topn items of every group)
+int wmf_recommend_grouped_slices(int64_t n_users, int64_t n_items, int32_t n_groups, int64_t topn, int32_t n_slices) {
+    return wmf_recommend_wide_slices(n_users, n_items, topn * n_groups, n_slices);
+}
+
+// allow_bits: the mask form, or NULL.  The selection runs over the n_users * n_groups virtual rows.
+int wmf_launch_recommend_grouped(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
+                                 int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* allow_bits,
+                                 int64_t allow_words, const int32_t* allow_idx, const int32_t* group_of, int32_t n_groups, int64_t topn,
+                                 int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* ws, hipStream_t st) {
+    WmfScanArgs a = {users, items, ld, bias, user_idx, n_users, n_items, wmf_recommend_grouped_slices(n_users, n_items, n_groups, topn, n_slices), st};
+    const int n = (int)topn, cap = WMF_RECOMMEND_WIDE_CAP(n);
+    const int64_t n_virtual = n_users * n_groups;
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws);
+    int32_t* counts = reinterpret_cast<int32_t*>(keys + (size_t)n_virtual * a.n_slices * cap);
+    constexpr int NW = WMF_REC_WIDE_WAVES;
+    const int rc = wmf_dispatch_scan(ld, [&](auto nit, auto tps) {
+        constexpr int NIT = decltype(nit)::value, TPS = decltype(tps)::value;
+        wmf_scan_geometry(a, NW);
+        const size_t lds = wmf_scan_stage_bytes(TPS, ld) + rec_grouped_lds_bytes(NW, n_groups);
+        if (allow_bits) {
+            static const char* name = wmf_kname("recommend_scan_grouped_mask_kernel<%d, %d, %d>", NIT, TPS, NW);
+            WMF_LAUNCH_LDS(name, (recommend_scan_grouped_kernel<NIT, TPS, NW, true>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW), lds, st,
+                           a.users, a.items, a.ld, a.bias, a.user_idx, a.n_rows, a.n_items, seen_indptr, seen_indices, allow_bits, allow_words,
+                           allow_idx, group_of, (int)n_groups, n, cap, a.n_slices, a.tiles_per_slice, a.n_work, keys, counts);
+        } else {
+            static const char* name = wmf_kname("recommend_scan_grouped_kernel<%d, %d, %d>", NIT, TPS, NW);
+            WMF_LAUNCH_LDS(name, (recommend_scan_grouped_kernel<NIT, TPS, NW, false>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW), lds, st,
+                           a.users, a.items, a.ld, a.bias, a.user_idx, a.n_rows, a.n_items, seen_indptr, seen_indices, nullptr, (int64_t)0,
+                           nullptr, group_of, (int)n_groups, n, cap, a.n_slices, a.tiles_per_slice, a.n_work, keys, counts);
+        }
+        return (int)WMF_L_OK;
+    });
+    if (rc) return rc;
+    const int64_t grid = n_virtual < WMF_REC_MERGE_GRID ? n_virtual : WMF_REC_MERGE_GRID;    // rows beyond it take another trip
+    WMF_LAUNCH("recommend_select_wide_kernel", recommend_select_wide_kernel, dim3((unsigned)grid), dim3(256), 0, st, keys, counts, n_virtual,
                a.n_slices, n, cap, out_items, out_scores, out_count);
     return WMF_L_OK;
 }

@@ -36,7 +36,8 @@ RECOMMEND_BATCH_USERS = 4096      # users per wmf_recommend_topn call of WMF.rec
 RECOMMEND_MAX_TOPN = 128          # WMF_RECOMMEND_MAX_TOPN of include/wmf_hip.h: beyond it recommend() takes the kernels of candidates()
 CANDIDATES_MAX = 4096             # WMF_RECOMMEND_WIDE_MAX_TOPN of include/wmf_hip.h: the limit of candidates() and of recommend()'s device path
 CANDIDATES_WS_BYTES = 1 << 30     # the workspace of one wmf_recommend_topn_wide call at most: candidates() takes fewer rows per call
-MMR_MAX_POOL = 4096               # WMF_MMR_MAX_POOL of include/wmf_hip.h: the largest pool rerank_mmr() and recommend_diverse() take
+SHELVES_MAX = 64                  # WMF_RECOMMEND_GROUPS_MAX of include/wmf_hip.h: the shelves of one recommend_shelves() call
+MMR_MAX_POOL = 4096             # WMF_MMR_MAX_POOL of include/wmf_hip.h: the largest pool rerank_mmr() and recommend_diverse() take
 ILS_MAX_WIDTH = 128               # WMF_ILS_MAX_WIDTH of include/wmf_hip.h: the longest list of intra_list_similarity()
 RANKPOS_MAX_TARGETS = 16          # WMF_RANKPOS_MAX_TARGETS of include/wmf_hip.h: rank_positions() splits longer rows
 EXPLAIN_MAX_TARGETS = 16          # WMF_EXPLAIN_MAX_TARGETS of include/wmf_hip.h: explain() splits longer target lists
@@ -226,6 +227,7 @@ class WMF(RecModel):
         self._dev = None           # (key, users_t, items_t, f, ld): device copies of the public arrays for predict() / rank()
         self._inv_norms = {}       # {"users" / "items": float32 [rows] on the device}: inverse feature norms of the copies in _dev
         self._white = {}           # {gamma: W_white [f, ld] on the device}: whitening of the item copy in _dev (explain)
+        self._groups = {}          # {id(array): (array, int32 [items] on the device)}: shelf assignments, kept as long as _dev is
 
     # ------------------------------------------------------------------ engine plumbing
     def _new_engine(self):
@@ -251,6 +253,7 @@ class WMF(RecModel):
             self._dev = (key, up(self.users), up(self.items), f, ld)
             self._inv_norms = {}
             self._white = {}
+            self._groups = {}
         return self._dev[1:]
 
     def _device_inv_norms(self, side):
@@ -420,6 +423,130 @@ class WMF(RecModel):
         if n < 1 or n > CANDIDATES_MAX:
             raise ValueError(f"n must be between 1 and {CANDIDATES_MAX}, not {n}")
         return self._recommend(users, n, exclude, return_scores, allow, allow_idx, True)
+
+    # ------------------------------------------------------------------ a17: one list per shelf
+    def recommend_shelves(self, users, groups, topn=10, exclude=None, return_scores=False, allow=None, allow_idx=None, n_groups=None):
+        """The ``topn`` best items of EVERY SHELF for each of ``users``, from one scan of the catalogue (wmf_recommend_topn_grouped):
+        ``groups`` is an integer array of length items, ``groups[j]`` the shelf (genre, department, carousel) of item j, a negative
+        value: on no shelf, never returned.  G = ``n_groups``, or ``groups.max() + 1``; 1 <= G <= SHELVES_MAX (64), 1 <= topn <=
+        RECOMMEND_MAX_TOPN (128), no id >= ``n_groups``, ``groups`` of an integer dtype and one entry per item: a ValueError
+        otherwise, before the GPU is asked for.  Returns int64 [len(users), G, topn], best first within a shelf, padded with -1
+        where a shelf has fewer eligible items; with ``return_scores`` also the float32 scores, padded with -inf.  An int user gives
+        [G, topn].  ``users``, ``exclude`` and the order are those of ``recommend``; ``allow`` / ``allow_idx`` take its two mask
+        forms, and an id list is turned into a mask on the host.  List (u, g) is, bit for bit, what ``recommend`` returns for u
+        under the mask ``groups == g`` (and the row's allow mask): the route of ``recommend``'s docstring -- every user repeated
+        once per shelf under a 2-D mask -- scores the catalogue G times, this call once.  Rows per call are bounded by
+        RECOMMEND_BATCH_USERS and by CANDIDATES_WS_BYTES of the grouped workspace; the uploaded ``groups`` is kept beside the
+        device copies of the factors while those are kept, when it is a read-only array (a writable one is uploaded per call).
+        Which route (MI355X, a million items, k = 128 + biases, topn 10, 10 seen items per row; profiles/r22_recommend_shelves.json,
+        DESIGN.md section 5): 2048 users x 16 shelves take 40.8 ms here and 160.8 ms as repeated rows under masks, 21.7 against
+        40.1 ms at 4 shelves, 17.1 against 19.7 ms at 2, 151 ms at 64 (repeated rows: 91 ms for 256 of the users); over one plain
+        scan (12.8 ms) that is 1.7 x at 4 shelves, 3.2 x at 16, 11.8 x at 64.  Use this call for batches from two shelves on; the
+        repeated rows of ``recommend`` are faster for a single shelf (10.8 against 14.3 ms) and for a handful of users (16 users x
+        16 shelves: 5.0 against 14.1 ms), whose repeated rows fill the device where one 16-row wave per slice does not."""
+        n_users_model, n_items = self.users.shape[0], self.items.shape[0]
+        g32, G, topn = self._shelf_arguments(groups, n_groups, topn, n_items)
+        if exclude is not None:
+            if not scipy.sparse.issparse(exclude) or exclude.shape != (n_users_model, n_items):
+                raise ValueError(f"exclude must be a sparse matrix of shape {(n_users_model, n_items)}, got {getattr(exclude, 'shape', None)}")
+        one = np.ndim(users) == 0
+        u = _wrapped_ids(np.atleast_1d(np.asarray(users)).reshape(-1).astype(np.int64), n_users_model, "user", np.int64)
+        filt = None if allow is None and allow_idx is None else _Allow(allow, allow_idx, n_items, len(u), "item", as_mask=True)
+        _lib.require_gpu()
+        out_items = np.full((len(u), G, topn), -1, dtype=np.int64)
+        out_scores = np.full((len(u), G, topn), -np.inf, dtype=np.float32)
+        if len(u) and not (filt is not None and filt.empty):
+            seen = None
+            if exclude is not None:
+                seen = scipy.sparse.csr_matrix(exclude)[u]            # the requested rows, a copy
+                seen.sort_indices()
+            users_t, items_t, f, ld = self._device_factors()
+            out_items[:], scores = self._shelves_scan(users_t, items_t, f, ld, u, groups, g32, G, topn, seen, return_scores, filt)
+            if return_scores:
+                out_scores[:] = scores
+        if one:
+            out_items, out_scores = out_items[0], out_scores[0]
+        return (out_items, out_scores) if return_scores else out_items
+
+    def recommend_capped(self, users, groups, topn=10, per_group=2, exclude=None, return_scores=False, allow=None, allow_idx=None):
+        """The ``topn`` best items overall with at most ``per_group`` of any shelf -- the commonest business rule on top of
+        ``recommend_shelves``, whose ``users``, ``groups`` (G = ``groups.max() + 1``), ``exclude`` and ``allow`` it takes.  Exact by
+        construction: an item of the capped list is among its shelf's min(per_group, topn) best, so the list is the merge of
+        ``recommend_shelves(..., topn=min(per_group, topn))`` -- a row's G x q keys sorted by (score descending, -0.0 equal to +0.0;
+        item ascending) on the host, the first ``topn`` taken.  Items on no shelf (a negative group) are NOT eligible: give them a
+        shelf of their own to keep them.  ``per_group >= topn`` with every item on one shelf is ``recommend``.  Returns int64
+        [len(users), topn] padded with -1, with ``return_scores`` also the float32 scores padded with -inf; an int user gives one
+        row."""
+        topn, per_group = int(topn), int(per_group)
+        if topn < 1 or topn > RECOMMEND_MAX_TOPN:
+            raise ValueError(f"topn must be between 1 and {RECOMMEND_MAX_TOPN}, not {topn}")
+        if per_group < 1:
+            raise ValueError(f"per_group must be at least 1, not {per_group}")
+        one = np.ndim(users) == 0
+        items, scores = self.recommend_shelves(np.atleast_1d(np.asarray(users)).reshape(-1), groups, min(per_group, topn), exclude, True,
+                                               allow, allow_idx)
+        B = items.shape[0]
+        items, scores = items.reshape(B, -1), scores.reshape(B, -1)
+        last = np.where(items < 0, np.iinfo(np.int64).max, items)     # padding behind every item, whatever its score
+        order = np.lexsort((last, -(scores + np.float32(0))), axis=-1)[:, :topn]
+        out_items = np.full((B, topn), -1, dtype=np.int64)
+        out_scores = np.full((B, topn), -np.inf, dtype=np.float32)
+        out_items[:, :order.shape[1]] = np.take_along_axis(items, order, axis=1)
+        out_scores[:, :order.shape[1]] = np.take_along_axis(scores, order, axis=1)
+        if one:
+            out_items, out_scores = out_items[0], out_scores[0]
+        return (out_items, out_scores) if return_scores else out_items
+
+    @staticmethod
+    def _shelf_arguments(groups, n_groups, topn, n_items):
+        """The checks the shelf calls share, before the GPU is asked for; returns (groups as int32 with every no-shelf value -1, G,
+        topn)."""
+        g = np.asarray(groups)
+        if g.dtype == bool or not np.issubdtype(g.dtype, np.integer) or g.ndim != 1:
+            raise ValueError("groups must be a 1-D integer array: the shelf of every item, negative for none")
+        if len(g) != n_items:
+            raise ValueError(f"groups has one entry per item ({n_items}), not {len(g)}")
+        top = int(g.max()) if len(g) else -1
+        G = int(n_groups) if n_groups is not None else top + 1
+        if G < 1 or G > SHELVES_MAX:
+            raise ValueError(f"the number of shelves must be between 1 and {SHELVES_MAX}, not {G}")
+        if top >= G:
+            raise ValueError(f"groups holds the id {top}, beyond n_groups = {G}")
+        topn = int(topn)
+        if topn < 1 or topn > RECOMMEND_MAX_TOPN:
+            raise ValueError(f"topn must be between 1 and {RECOMMEND_MAX_TOPN}, not {topn}")
+        return np.where(g < 0, -1, g).astype(np.int32), G, topn
+
+    def _device_groups(self, groups, g32):
+        """The device copy of a shelf assignment (after _device_factors): kept beside the factors' copies, under their rule -- by
+        identity for a read-only array, while the factors' copies are kept; a writable array is uploaded on every call."""
+        if isinstance(groups, np.ndarray) and not groups.flags.writeable and not (self.users.flags.writeable or self.items.flags.writeable):
+            hit = self._groups.get(id(groups))
+            if hit is None or hit[0] is not groups:
+                hit = self._groups[id(groups)] = (groups, torch.from_numpy(g32).cuda())     # (the array is held: its id stays its own)
+            return hit[1]
+        return torch.from_numpy(g32).cuda()
+
+    def _shelves_scan(self, users_t, items_t, f, ld, u, groups, g32, G, topn, seen, want_scores, filt):
+        """wmf_recommend_topn_grouped on the rows ``u`` of the device matrix ``users_t`` in batches (_scan_batches), in windows
+        whose workspace stays within CANDIDATES_WS_BYTES (one row at least).  Returns the host (items [B, G, topn], scores or
+        None)."""
+        lib = _lib.load()
+        n_items = self.items.shape[0]
+        items_d = torch.empty(len(u), G, topn, dtype=torch.int32, device="cuda")
+        scores_d = torch.empty(len(u), G, topn, dtype=torch.float32, device="cuda") if want_scores else None
+        head = (_ptr(users_t), _ptr(items_t), f, ld, int(self.bias is True))
+        groups_d = self._device_groups(groups, g32)
+        at = filt.upload() if filt is not None else (lambda b0: (None, 0, 0, None))
+        need = lambda rows: int(lib.wmf_recommend_grouped_workspace_bytes(rows, G, topn, 0))   # noqa: E731
+        rows = max(1, min(len(u), int(RECOMMEND_BATCH_USERS)))
+        while rows > 1 and need(rows) > CANDIDATES_WS_BYTES:       # (it grows with the rows: halve until a window fits)
+            rows //= 2
+
+        def call(b0, nb, ids, csrs, *ws):
+            return lib.wmf_recommend_topn_grouped(*head, ids, nb, n_items, *csrs[0], *at(b0)[:4], _ptr(groups_d), G, topn, 0,
+                                                  _ptr(items_d[b0:]), _ptr(scores_d[b0:]) if scores_d is not None else None, None, *ws)
+        return self._scan_batches(u, [None if seen is None else (seen.indptr, seen.indices)], need, [items_d, scores_d], call, rows)
 
     # ------------------------------------------------------------------ a15: diversified lists
     @staticmethod
@@ -1056,6 +1183,35 @@ class WMF(RecModel):
             raise ValueError(f"pool ({pool}) must be at least topn ({topn})")
         return self._recommend_for(count_rows, topn, RECOMMEND_MAX_TOPN, "topn", exclude_history, return_scores, alpha, beta,
                                    pre_process_count, allow, allow_idx, mmr=(pool, lam, cosine))
+
+    def recommend_shelves_for(self, count_rows, groups, topn=10, exclude_history=True, return_scores=False, alpha=10, beta=1,
+                              pre_process_count='log', allow=None, allow_idx=None, n_groups=None):
+        """``recommend_shelves`` for histories instead of user ids, as ``candidates_for`` is to ``candidates``: the rows of
+        ``count_rows`` are folded in on the device -- the factors never leave it -- and the ``topn`` best items of every shelf are
+        found for each in one scan.  The arguments of ``recommend_for`` and of ``recommend_shelves``; returns int64 [B, G, topn]
+        (and the float32 scores); a row whose fold-in failed is all -1 / -inf.  Bit for bit the output of ``recommend_shelves`` on
+        a model whose ``users`` are ``fold_in(count_rows)``."""
+        mat, mode = self._foldin_arguments(count_rows, pre_process_count)
+        n_items = self.items.shape[0]
+        g32, G, topn = self._shelf_arguments(groups, n_groups, topn, n_items)
+        B = mat.shape[0]
+        filt = None if allow is None and allow_idx is None else _Allow(allow, allow_idx, n_items, B, "item", as_mask=True)
+        _lib.require_gpu()
+        out_items = np.full((B, G, topn), -1, dtype=np.int64)
+        out_scores = np.full((B, G, topn), -np.inf, dtype=np.float32)
+        if B and not (filt is not None and filt.empty):
+            X_d, items_t, f, ld = self._fold_in_device(mat, alpha, beta, mode)
+            seen = None
+            if exclude_history:
+                seen = mat.copy()                                  # the seen list as ``recommend`` prepares ``exclude``
+                seen.sort_indices()
+            got_items, got_scores = self._shelves_scan(X_d, items_t, f, ld, np.arange(B, dtype=np.int64), groups, g32, G, topn, seen,
+                                                       return_scores, filt)
+            good = ~torch.isnan(X_d[:, :f]).any(dim=1).cpu().numpy()
+            out_items[good] = got_items[good]
+            if return_scores:
+                out_scores[good] = got_scores[good]
+        return (out_items, out_scores) if return_scores else out_items
 
     def _recommend_for(self, count_rows, topn, limit, name, exclude_history, return_scores, alpha, beta, pre_process_count, allow, allow_idx,
                        mmr=None):

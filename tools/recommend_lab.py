@@ -27,7 +27,15 @@ biases, 10 seen items per row, 2048 and 16 users, every pair of routes in altern
 topn 200, this commit's recommend against the parent's, the host loop over rank() and predict(), which is still the code beyond
 CANDIDATES_MAX and is reached by lowering that constant for the call; (2) topn 128 through wmf_recommend_topn and through the wide
 kernels, scan and selection kernel apart from the library's wmf_profile_* table; (3) the ladder topn 129 .. 4096 with the automatic
-slice count, the workspace and the rows of a call; (4) the mask form at a 1 % pass rate and the list form of 10 000 ids at topn 1000."""
+slice count, the workspace and the rows of a call; (4) the mask form at a 1 % pass rate and the list form of 10 000 ids at topn 1000.
+
+--shelves: WMF.recommend_shelves (wmf_recommend_topn_grouped, one scan for all shelves) at 1 000 000 items, k = 128 + biases, 10 seen
+items per row, topn 10, shelves assigned j % G and, once, Zipf-sized: against the route it replaces -- WMF.recommend with every user
+repeated once per shelf under G masks (wmf_recommend_topn_filtered; at 64 shelves on 256 of the 2048 users and scaled, which the
+record says) -- and against one unfiltered wide scan at topn 10 (WMF.candidates), the floor.  The three routes of a shape in
+alternating repetitions of one process after a warm-up of each, a host clock ending in a synchronise, median and spread; the arrays
+of the first two compared for identity; scan and selection kernel apart from the library's wmf_profile_* table.  The gate: at 2048
+users and 16 shelves the new call's median is below the repeated rows' by more than the larger spread, and the arrays are identical."""
 import argparse
 import json
 import statistics
@@ -343,6 +351,63 @@ def run_wide(n_items, k, bias, reps):
     return rec
 
 
+SHELF_SHAPES = ((2048, 1, "mod"), (2048, 2, "mod"), (2048, 4, "mod"), (2048, 16, "mod"), (2048, 16, "zipf"), (2048, 64, "mod"), (16, 16, "mod"))
+SHELF_SCALED_ROWS = 256             # rows of the repeated-rows route at 64 shelves (2048 x 64 rows would be 64 scans a repetition)
+
+
+def run_shelves(n_items, k, bias, topn, reps):
+    rng = np.random.default_rng(1000 * k + bias)
+    f = k + bias
+    n_all = max(s[0] for s in SHELF_SHAPES)
+    m = WMF(num_items=8, num_users=n_all, dim=k, gamma=0.1, weighted=True, bias=bool(bias))
+    m.users, m.items = rng.standard_normal((n_all, f), dtype=np.float32), rng.standard_normal((n_items, f), dtype=np.float32)
+    m.num_items = n_items
+    m.users.flags.writeable = m.items.flags.writeable = False
+    seen = sp.csr_matrix((np.ones(10 * n_all, dtype=np.float32), rng.integers(0, n_items, 10 * n_all), 10 * np.arange(n_all + 1)),
+                         shape=(n_all, n_items))
+    seen.sum_duplicates()
+    lib = _lib.load()
+    rec = {"items": n_items, "k": k, "bias": bias, "topn": topn, "seen_per_user": 10, "shapes": []}
+    for n_users, G, how in SHELF_SHAPES:
+        if how == "mod":
+            groups = np.arange(n_items) % G
+        else:                                                       # Zipf-sized shelves: shelf g holds a share proportional to 1 / (g + 1)
+            share = 1.0 / np.arange(1, G + 1)
+            groups = rng.permutation(np.minimum(np.searchsorted(np.cumsum(share / share.sum()), (np.arange(n_items) + 0.5) / n_items), G - 1))
+        groups.flags.writeable = False
+        masks = np.stack([groups == g for g in range(G)])
+        users = np.arange(n_users)
+        rows_b = n_users if G < 64 else min(n_users, SHELF_SCALED_ROWS)
+        rep, idx = np.repeat(users[:rows_b], G), np.tile(np.arange(G), rows_b)
+        routes = {"shelves": lambda: m.recommend_shelves(users, groups, topn, exclude=seen, return_scores=True),
+                  "repeated_rows": lambda: m.recommend(rep, topn, exclude=seen, return_scores=True, allow=masks, allow_idx=idx),
+                  "one_wide_scan": lambda: m.candidates(users, topn, exclude=seen, return_scores=True)}
+        a, b = routes["shelves"](), routes["repeated_rows"]()
+        entry = {"users": n_users, "groups": G, "assignment": how, "group_sizes_min_max": [int(np.bincount(groups).min()), int(np.bincount(groups).max())],
+                 "repeated_rows_users": rows_b, "repeated_rows_scaled": rows_b != n_users,
+                 "identical_arrays": same_bits([x[:rows_b].reshape(rows_b * G, topn) for x in a], b), **alternate(routes, reps)}
+        assert entry["identical_arrays"], (n_users, G, how)
+        for name, fn in routes.items():
+            scan, tail, names = kernel_split(lib, fn)
+            entry[name + "_kernels"] = {"scan_s": scan, "select_or_merge_s": tail, "names": names}
+        med = {name: entry[name]["median_s"] for name in routes}
+        entry["shelves_over_one_wide_scan"] = med["shelves"] / med["one_wide_scan"]
+        entry["shelves_scan_over_wide_scan"] = entry["shelves_kernels"]["scan_s"] / entry["one_wide_scan_kernels"]["scan_s"]
+        entry["repeated_rows_over_shelves"] = med["repeated_rows"] * (n_users / rows_b) / med["shelves"]
+        entry["shelves_faster_beyond_spread"] = bool(not entry["repeated_rows_scaled"] and med["repeated_rows"] - med["shelves"]
+                                                     > max(entry["shelves"]["spread_s"], entry["repeated_rows"]["spread_s"]))
+        rec["shapes"].append(entry)
+        print(json.dumps({key: (v["median_s"] if isinstance(v, dict) and "median_s" in v else v) for key, v in entry.items()
+                          if not key.endswith("_kernels")}), flush=True)
+    gate = next(e for e in rec["shapes"] if (e["users"], e["groups"], e["assignment"]) == (2048, 16, "mod"))
+    rec["gate"] = {"shape": "2048 users, 16 shelves", "passed": bool(gate["shelves_faster_beyond_spread"] and gate["identical_arrays"]),
+                   "shelves_median_s": gate["shelves"]["median_s"], "repeated_rows_median_s": gate["repeated_rows"]["median_s"]}
+    rec["repeated_rows_wins_at_groups"] = [e["groups"] for e in rec["shapes"]
+                                           if e["users"] == 2048 and not e["repeated_rows_scaled"] and e["repeated_rows"]["median_s"] < e["shelves"]["median_s"]]
+    print(json.dumps({"gate": rec["gate"], "repeated_rows_wins_at_groups": rec["repeated_rows_wins_at_groups"]}), flush=True)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the full record to this file")
@@ -350,8 +415,16 @@ def main():
     ap.add_argument("--topn", type=int, default=10)
     ap.add_argument("--filters", action="store_true", help="the catalogue filters at one shape (default 2048,1000000,128,1)")
     ap.add_argument("--wide", action="store_true", help="candidates() and recommend() beyond 128 (default 1000000,128,1)")
+    ap.add_argument("--shelves", action="store_true", help="recommend_shelves() against repeated rows under masks (default 1000000,128,1)")
     ap.add_argument("shapes", nargs="*", default=None)
     args = ap.parse_args()
+    if args.shelves:
+        n_items, k, bias = (int(x) for x in (args.shapes or ["1000000,128,1"])[0].split(","))
+        out = {"device": torch.cuda.get_device_name(0), "method": __doc__.split("\n\n")[5], "shelves": run_shelves(n_items, k, bias, args.topn, args.reps)}
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(out, fh, indent=1)
+        return
     if args.wide:
         n_items, k, bias = (int(x) for x in (args.shapes or ["1000000,128,1"])[0].split(","))
         out = {"device": torch.cuda.get_device_name(0), "method": __doc__.split("\n\n")[4], "wide": run_wide(n_items, k, bias, args.reps)}
