@@ -86,6 +86,40 @@ static int check_scan_call(const char* what, const void* users, const void* item
     return WMF_OK;
 }
 
+// what a call's filter arguments break, or NULL (check_scan_call's `own`); n_items: the catalogue the mask covers
+static const char* filter_refusal(const WmfRowFilter& flt, int32_t n_masks, int64_t n_items, int64_t n_cand) {
+    if (flt.allow_bits && flt.cand_idx) return "allow_bits and cand_idx: one form per call";
+    if (flt.allow_bits && (n_masks < 1 || n_items < 1 || flt.allow_words < (n_items + 31) / 32)) return "need n_masks >= 1 and allow_words >= ceil(n_items / 32)";
+    if (!flt.allow_bits && flt.allow_idx) return "allow_idx without allow_bits";
+    if (flt.cand_idx && (n_cand < 1 || n_cand > n_items)) return "need 1 <= n_cand <= n_items";
+    return nullptr;
+}
+
+// A top-N call as its entry point describes it, by name: the matrices and outputs check_scan_call looks at, the names its messages
+// print for the two sizes, the filter with the two counts filter_refusal needs, and the call's own pointer rules -- the refusal that
+// comes before the filter's and the one that comes after it, or NULL.
+struct TopnCall {
+    const char* what; int f, ld;
+    const void* rows_mat; const void* cat_mat; const void* row_idx; const void* out; const void* workspace;
+    const char* rows_name; int64_t n_rows; const char* cat_name; int64_t n_cat;
+    int64_t topn; int32_t n_slices; int64_t workspace_bytes; int max_topn;
+    WmfRowFilter flt; int32_t n_masks; int64_t n_cand;
+    const char* before; const char* after;
+};
+// What the six top-N entry points do, before any HIP call and in this order: the shape; the first broken one of the call's pointer
+// rules (before, the filter's, after); check_scan_call with need() for the workspace; then launch(), which hands c.flt to its launcher
+// (the empty filter is the unfiltered call).
+template <class Need, class Launch>
+static int topn_call(const TopnCall& c, Need&& need, Launch&& launch) {
+    int rc = check_shape(c.f, c.ld);
+    if (rc) return rc;
+    const char* own = c.before ? c.before : filter_refusal(c.flt, c.n_masks, c.n_cat, c.n_cand);
+    if (!own) own = c.after;
+    if ((rc = check_scan_call(c.what, c.rows_mat, c.cat_mat, c.row_idx, c.out, c.workspace, "null pointer", own, c.rows_name, c.n_rows, c.cat_name,
+                              c.n_cat, &c.topn, c.n_slices, c.workspace_bytes, need, c.max_topn))) return rc;
+    return launch_error(launch(), c.what, c.f, c.ld, "");
+}
+
 // The number of compute units of the current device, asked once (as WMF_LDS_CEILING asks once per kernel).
 int wmf_cu_count() {
     static const int n = [] {
@@ -705,26 +739,33 @@ int wmf_rank_topn_batch(const float* users, const float* items, int f, int ld, i
 
 int64_t wmf_recommend_workspace_bytes(int64_t n_users, int64_t topn, int32_t n_slices) { return wmf_recommend_ws_bytes(n_users, topn, n_slices); }
 
+int64_t wmf_recommend_wide_workspace_bytes(int64_t n_users, int64_t topn, int32_t n_slices) { return wmf_recommend_wide_ws_bytes(n_users, topn, n_slices); }
+int64_t wmf_recommend_grouped_workspace_bytes(int64_t n_users, int32_t n_groups, int64_t topn, int32_t n_slices) {
+    return wmf_recommend_grouped_ws_bytes(n_users, n_groups, topn, n_slices);
+}
+
+// wmf_recommend_topn, _filtered and _wide.  wide: every topn runs the wide kernels -- for topn <= WMF_RECOMMEND_MAX_TOPN the LDS
+// kernels are the cross-check, bit for bit
+static int recommend_call(const char* what, bool wide, const float* users, const float* items, int f, int ld, int bias, const int32_t* user_idx,
+                          int64_t n_users, int64_t n_items, const WmfRowFilter& flt, int32_t n_masks, int64_t n_cand, int64_t topn,
+                          int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* workspace, int64_t workspace_bytes,
+                          void* stream) {
+    const TopnCall c{.what = what, .f = f, .ld = ld, .rows_mat = users, .cat_mat = items, .row_idx = user_idx, .out = out_items, .workspace = workspace,
+                     .rows_name = "n_users", .n_rows = n_users, .cat_name = "n_items", .n_cat = n_items, .topn = topn, .n_slices = n_slices,
+                     .workspace_bytes = workspace_bytes, .max_topn = wide ? WMF_RECOMMEND_WIDE_MAX_TOPN : WMF_RECOMMEND_MAX_TOPN, .flt = flt,
+                     .n_masks = n_masks, .n_cand = n_cand};
+    const auto ws_bytes = wide ? wmf_recommend_wide_ws_bytes : wmf_recommend_ws_bytes;
+    const auto launcher = wide ? wmf_launch_recommend_wide : wmf_launch_recommend;
+    return topn_call(c, [&] { return ws_bytes(n_users, topn, n_slices); },
+                     [&] { return launcher(users, items, ld, bias, user_idx, n_users, n_items, flt, n_cand, topn, n_slices, out_items, out_scores, out_count,
+                                           workspace, (hipStream_t)stream); });
+}
+
 int wmf_recommend_topn(const float* users, const float* items, int f, int ld, int bias, const int32_t* user_idx, int64_t n_users,
                        int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, int64_t topn, int32_t n_slices,
                        int32_t* out_items, float* out_scores, int32_t* out_count, void* workspace, int64_t workspace_bytes, void* stream) {
-    int rc = check_shape(f, ld);
-    if (rc) return rc;
-    if ((rc = check_scan_call("wmf_recommend_topn", users, items, user_idx, out_items, workspace, "null pointer", nullptr, "n_users", n_users, "n_items",
-                              n_items, &topn, n_slices, workspace_bytes, [&] { return wmf_recommend_ws_bytes(n_users, topn, n_slices); }))) return rc;
-    return launch_error(wmf_launch_recommend(users, items, ld, bias, user_idx, n_users, n_items, seen_indptr, seen_indices, topn, n_slices,
-                                             out_items, out_scores, out_count, workspace, (hipStream_t)stream),
-                        "wmf_recommend_topn", f, ld, "");
-}
-
-// what a call's filter arguments break, or NULL (check_scan_call's `own`); n_items: the catalogue the mask covers
-static const char* filter_refusal(const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks, const int32_t* allow_idx, int64_t n_items,
-                                  const int32_t* cand_idx, int64_t n_cand) {
-    if (allow_bits && cand_idx) return "allow_bits and cand_idx: one form per call";
-    if (allow_bits && (n_masks < 1 || n_items < 1 || allow_words < (n_items + 31) / 32)) return "need n_masks >= 1 and allow_words >= ceil(n_items / 32)";
-    if (!allow_bits && allow_idx) return "allow_idx without allow_bits";
-    if (cand_idx && (n_cand < 1 || n_cand > n_items)) return "need 1 <= n_cand <= n_items";
-    return nullptr;
+    return recommend_call("wmf_recommend_topn", false, users, items, f, ld, bias, user_idx, n_users, n_items, WmfRowFilter{seen_indptr, seen_indices},
+                          0, 0, topn, n_slices, out_items, out_scores, out_count, workspace, workspace_bytes, stream);
 }
 
 int wmf_recommend_topn_filtered(const float* users, const float* items, int f, int ld, int bias, const int32_t* user_idx, int64_t n_users,
@@ -732,43 +773,19 @@ int wmf_recommend_topn_filtered(const float* users, const float* items, int f, i
                                 int64_t allow_words, int32_t n_masks, const int32_t* allow_idx, const int32_t* cand_idx, int64_t n_cand,
                                 int64_t topn, int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* workspace,
                                 int64_t workspace_bytes, void* stream) {
-    int rc = check_shape(f, ld);
-    if (rc) return rc;
-    const char* own = filter_refusal(allow_bits, allow_words, n_masks, allow_idx, n_items, cand_idx, n_cand);
-    if ((rc = check_scan_call("wmf_recommend_topn_filtered", users, items, user_idx, out_items, workspace, "null pointer", own, "n_users", n_users,
-                              "n_items", n_items, &topn, n_slices, workspace_bytes, [&] { return wmf_recommend_ws_bytes(n_users, topn, n_slices); }))) return rc;
-    if (!allow_bits && !cand_idx)                                  // neither form: wmf_recommend_topn
-        return launch_error(wmf_launch_recommend(users, items, ld, bias, user_idx, n_users, n_items, seen_indptr, seen_indices, topn, n_slices,
-                                                 out_items, out_scores, out_count, workspace, (hipStream_t)stream),
-                            "wmf_recommend_topn_filtered", f, ld, "");
-    return launch_error(wmf_launch_recommend_filtered(users, items, ld, bias, user_idx, n_users, n_items, seen_indptr, seen_indices, allow_bits,
-                                                      allow_words, allow_idx, cand_idx, n_cand, topn, n_slices, out_items, out_scores, out_count,
-                                                      workspace, (hipStream_t)stream),
-                        "wmf_recommend_topn_filtered", f, ld, "");
+    return recommend_call("wmf_recommend_topn_filtered", false, users, items, f, ld, bias, user_idx, n_users, n_items,
+                          WmfRowFilter{seen_indptr, seen_indices, allow_bits, allow_words, allow_idx, nullptr, cand_idx}, n_masks, n_cand, topn, n_slices,
+                          out_items, out_scores, out_count, workspace, workspace_bytes, stream);
 }
 
-int64_t wmf_recommend_wide_workspace_bytes(int64_t n_users, int64_t topn, int32_t n_slices) { return wmf_recommend_wide_ws_bytes(n_users, topn, n_slices); }
-
-// every topn runs the wide kernels: for topn <= WMF_RECOMMEND_MAX_TOPN the entry points above are the cross-check, bit for bit
 int wmf_recommend_topn_wide(const float* users, const float* items, int f, int ld, int bias, const int32_t* user_idx, int64_t n_users,
                             int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* allow_bits,
                             int64_t allow_words, int32_t n_masks, const int32_t* allow_idx, const int32_t* cand_idx, int64_t n_cand,
                             int64_t topn, int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* workspace,
                             int64_t workspace_bytes, void* stream) {
-    int rc = check_shape(f, ld);
-    if (rc) return rc;
-    const char* own = filter_refusal(allow_bits, allow_words, n_masks, allow_idx, n_items, cand_idx, n_cand);
-    if ((rc = check_scan_call("wmf_recommend_topn_wide", users, items, user_idx, out_items, workspace, "null pointer", own, "n_users", n_users,
-                              "n_items", n_items, &topn, n_slices, workspace_bytes,
-                              [&] { return wmf_recommend_wide_ws_bytes(n_users, topn, n_slices); }, WMF_RECOMMEND_WIDE_MAX_TOPN))) return rc;
-    return launch_error(wmf_launch_recommend_wide(users, items, ld, bias, user_idx, n_users, n_items, seen_indptr, seen_indices, allow_bits,
-                                                  allow_words, allow_idx, cand_idx, n_cand, topn, n_slices, out_items, out_scores, out_count,
-                                                  workspace, (hipStream_t)stream),
-                        "wmf_recommend_topn_wide", f, ld, "");
-}
-
-int64_t wmf_recommend_grouped_workspace_bytes(int64_t n_users, int32_t n_groups, int64_t topn, int32_t n_slices) {
-    return wmf_recommend_grouped_ws_bytes(n_users, n_groups, topn, n_slices);
+    return recommend_call("wmf_recommend_topn_wide", true, users, items, f, ld, bias, user_idx, n_users, n_items,
+                          WmfRowFilter{seen_indptr, seen_indices, allow_bits, allow_words, allow_idx, nullptr, cand_idx}, n_masks, n_cand, topn, n_slices,
+                          out_items, out_scores, out_count, workspace, workspace_bytes, stream);
 }
 
 int wmf_recommend_topn_grouped(const float* users, const float* items, int f, int ld, int bias, const int32_t* user_idx, int64_t n_users,
@@ -776,18 +793,16 @@ int wmf_recommend_topn_grouped(const float* users, const float* items, int f, in
                                int64_t allow_words, int32_t n_masks, const int32_t* allow_idx, const int32_t* group_of, int32_t n_groups,
                                int64_t topn, int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* workspace,
                                int64_t workspace_bytes, void* stream) {
-    int rc = check_shape(f, ld);
-    if (rc) return rc;
-    const char* own = filter_refusal(allow_bits, allow_words, n_masks, allow_idx, n_items, nullptr, 0);
-    if (!own && !group_of) own = "null group_of";
-    if (!own && (n_groups < 1 || n_groups > WMF_RECOMMEND_GROUPS_MAX)) own = "need 1 <= n_groups <= WMF_RECOMMEND_GROUPS_MAX (64)";
-    if ((rc = check_scan_call("wmf_recommend_topn_grouped", users, items, user_idx, out_items, workspace, "null pointer", own, "n_users", n_users,
-                              "n_items", n_items, &topn, n_slices, workspace_bytes,
-                              [&] { return wmf_recommend_grouped_ws_bytes(n_users, n_groups, topn, n_slices); }))) return rc;
-    return launch_error(wmf_launch_recommend_grouped(users, items, ld, bias, user_idx, n_users, n_items, seen_indptr, seen_indices, allow_bits,
-                                                     allow_words, allow_idx, group_of, n_groups, topn, n_slices, out_items, out_scores,
-                                                     out_count, workspace, (hipStream_t)stream),
-                        "wmf_recommend_topn_grouped", f, ld, "");
+    const WmfRowFilter flt{seen_indptr, seen_indices, allow_bits, allow_words, allow_idx};
+    const char* after = !group_of ? "null group_of"
+                        : (n_groups < 1 || n_groups > WMF_RECOMMEND_GROUPS_MAX) ? "need 1 <= n_groups <= WMF_RECOMMEND_GROUPS_MAX (64)" : nullptr;
+    const TopnCall c{.what = "wmf_recommend_topn_grouped", .f = f, .ld = ld, .rows_mat = users, .cat_mat = items, .row_idx = user_idx, .out = out_items,
+                     .workspace = workspace, .rows_name = "n_users", .n_rows = n_users, .cat_name = "n_items", .n_cat = n_items, .topn = topn,
+                     .n_slices = n_slices, .workspace_bytes = workspace_bytes, .max_topn = WMF_RECOMMEND_MAX_TOPN, .flt = flt, .n_masks = n_masks,
+                     .after = after};
+    return topn_call(c, [&] { return wmf_recommend_grouped_ws_bytes(n_users, n_groups, topn, n_slices); },
+                     [&] { return wmf_launch_recommend_grouped(users, items, ld, bias, user_idx, n_users, n_items, flt, group_of, n_groups, topn, n_slices,
+                                                               out_items, out_scores, out_count, workspace, (hipStream_t)stream); });
 }
 
 int wmf_row_inv_norms(const float* M, int64_t n, int f, int ld, int bias, float* out, void* stream) {
@@ -801,20 +816,31 @@ int wmf_row_inv_norms(const float* M, int64_t n, int f, int ld, int bias, float*
 
 int64_t wmf_similar_workspace_bytes(int64_t n_queries, int64_t topn, int32_t n_slices) { return wmf_recommend_ws_bytes(n_queries, topn, n_slices); }
 
+// wmf_similar_topn and _filtered: the exclusion lists are the filter's seen lists, the row itself its self_idx
+static int similar_call(const char* what, const float* queries, const float* catalogue, int f, int ld, int bias, const float* q_inv_norm,
+                        const float* c_inv_norm, const int32_t* query_idx, int64_t n_queries, int64_t n_rows, int32_t exclude_self,
+                        const int64_t* excl_indptr, const int32_t* excl_indices, const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks,
+                        const int32_t* allow_idx, int64_t topn, int32_t n_slices, int32_t* out_rows, float* out_scores, int32_t* out_count,
+                        void* workspace, int64_t workspace_bytes, void* stream) {
+    const WmfRowFilter flt{excl_indptr, excl_indices, allow_bits, allow_words, allow_idx, exclude_self ? query_idx : nullptr};
+    const char* before = (!q_inv_norm != !c_inv_norm || !excl_indptr != !excl_indices)
+                             ? "q_inv_norm and c_inv_norm, excl_indptr and excl_indices: both or neither" : nullptr;
+    const TopnCall c{.what = what, .f = f, .ld = ld, .rows_mat = queries, .cat_mat = catalogue, .row_idx = query_idx, .out = out_rows,
+                     .workspace = workspace, .rows_name = "n_queries", .n_rows = n_queries, .cat_name = "n_rows", .n_cat = n_rows, .topn = topn,
+                     .n_slices = n_slices, .workspace_bytes = workspace_bytes, .max_topn = WMF_RECOMMEND_MAX_TOPN, .flt = flt, .n_masks = n_masks,
+                     .before = before};
+    return topn_call(c, [&] { return wmf_recommend_ws_bytes(n_queries, topn, n_slices); },
+                     [&] { return wmf_launch_similar(queries, catalogue, ld, bias, q_inv_norm, c_inv_norm, query_idx, n_queries, n_rows, flt, topn,
+                                                     n_slices, out_rows, out_scores, out_count, workspace, (hipStream_t)stream); });
+}
+
 int wmf_similar_topn(const float* queries, const float* catalogue, int f, int ld, int bias, const float* q_inv_norm, const float* c_inv_norm,
                      const int32_t* query_idx, int64_t n_queries, int64_t n_rows, int32_t exclude_self, const int64_t* excl_indptr,
                      const int32_t* excl_indices, int64_t topn, int32_t n_slices, int32_t* out_rows, float* out_scores, int32_t* out_count,
                      void* workspace, int64_t workspace_bytes, void* stream) {
-    int rc = check_shape(f, ld);
-    if (rc) return rc;
-    const char* own = (!q_inv_norm != !c_inv_norm || !excl_indptr != !excl_indices)
-                          ? "q_inv_norm and c_inv_norm, excl_indptr and excl_indices: both or neither" : nullptr;
-    if ((rc = check_scan_call("wmf_similar_topn", queries, catalogue, query_idx, out_rows, workspace, "null pointer", own, "n_queries", n_queries,
-                              "n_rows", n_rows, &topn, n_slices, workspace_bytes, [&] { return wmf_recommend_ws_bytes(n_queries, topn, n_slices); }))) return rc;
-    return launch_error(wmf_launch_similar(queries, catalogue, ld, bias, q_inv_norm, c_inv_norm, query_idx, n_queries, n_rows, exclude_self,
-                                           excl_indptr, excl_indices, topn, n_slices, out_rows, out_scores, out_count, workspace,
-                                           (hipStream_t)stream),
-                        "wmf_similar_topn", f, ld, "");
+    return similar_call("wmf_similar_topn", queries, catalogue, f, ld, bias, q_inv_norm, c_inv_norm, query_idx, n_queries, n_rows, exclude_self,
+                        excl_indptr, excl_indices, nullptr, 0, 0, nullptr, topn, n_slices, out_rows, out_scores, out_count, workspace,
+                        workspace_bytes, stream);
 }
 
 int wmf_similar_topn_filtered(const float* queries, const float* catalogue, int f, int ld, int bias, const float* q_inv_norm,
@@ -822,23 +848,9 @@ int wmf_similar_topn_filtered(const float* queries, const float* catalogue, int 
                               const int64_t* excl_indptr, const int32_t* excl_indices, const uint32_t* allow_bits, int64_t allow_words,
                               int32_t n_masks, const int32_t* allow_idx, int64_t topn, int32_t n_slices, int32_t* out_rows, float* out_scores,
                               int32_t* out_count, void* workspace, int64_t workspace_bytes, void* stream) {
-    int rc = check_shape(f, ld);
-    if (rc) return rc;
-    const char* own = (!q_inv_norm != !c_inv_norm || !excl_indptr != !excl_indices)
-                          ? "q_inv_norm and c_inv_norm, excl_indptr and excl_indices: both or neither"
-                          : filter_refusal(allow_bits, allow_words, n_masks, allow_idx, n_rows, nullptr, 0);
-    if ((rc = check_scan_call("wmf_similar_topn_filtered", queries, catalogue, query_idx, out_rows, workspace, "null pointer", own, "n_queries",
-                              n_queries, "n_rows", n_rows, &topn, n_slices, workspace_bytes,
-                              [&] { return wmf_recommend_ws_bytes(n_queries, topn, n_slices); }))) return rc;
-    if (!allow_bits)                                               // no mask: wmf_similar_topn
-        return launch_error(wmf_launch_similar(queries, catalogue, ld, bias, q_inv_norm, c_inv_norm, query_idx, n_queries, n_rows, exclude_self,
-                                               excl_indptr, excl_indices, topn, n_slices, out_rows, out_scores, out_count, workspace,
-                                               (hipStream_t)stream),
-                            "wmf_similar_topn_filtered", f, ld, "");
-    return launch_error(wmf_launch_similar_filtered(queries, catalogue, ld, bias, q_inv_norm, c_inv_norm, query_idx, n_queries, n_rows,
-                                                    exclude_self, excl_indptr, excl_indices, allow_bits, allow_words, allow_idx, topn, n_slices,
-                                                    out_rows, out_scores, out_count, workspace, (hipStream_t)stream),
-                        "wmf_similar_topn_filtered", f, ld, "");
+    return similar_call("wmf_similar_topn_filtered", queries, catalogue, f, ld, bias, q_inv_norm, c_inv_norm, query_idx, n_queries, n_rows,
+                        exclude_self, excl_indptr, excl_indices, allow_bits, allow_words, n_masks, allow_idx, topn, n_slices, out_rows, out_scores,
+                        out_count, workspace, workspace_bytes, stream);
 }
 
 int64_t wmf_rerank_mmr_resident_pool(int f, int ld) { return wmf_mmr_resident_pool(f, ld); }

@@ -5,6 +5,7 @@
 #include <type_traits>
 #include <utility>
 #include "../../include/wmf_hip.h"
+#include "wmf_filter.h"
 
 #define WMF_GRAM_MAX_WAVES 4096
 #define WMF_EVAL_MAX_BLOCKS 2048
@@ -237,14 +238,11 @@ int wmf_launch_rank_batch(const float* users, const float* items, int f, int ld,
                           const int32_t* cand, int64_t nc, int64_t topn, int32_t* out_pos, float* out_scores, void* ws, hipStream_t st);
 // wmf_recommend.hip: full-catalogue top-n with per-user exclusions (workspace: n_slices = 0 is sized for the automatic cap)
 int64_t wmf_recommend_ws_bytes(int64_t n_users, int64_t topn, int32_t n_slices);
+// (flt, here and below: what restricts a row's list -- seen lists, allow masks or a list of n_cand candidate rows, the row itself;
+// the empty filter is the unfiltered call)
 int wmf_launch_recommend(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
-                         int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, int64_t topn, int32_t n_slices,
-                         int32_t* out_items, float* out_scores, int32_t* out_count, void* ws, hipStream_t st);
-// (... restricted by allow masks, or to a list of candidate rows: exactly one of allow_bits and cand_idx is given)
-int wmf_launch_recommend_filtered(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
-                                  int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* allow_bits,
-                                  int64_t allow_words, const int32_t* allow_idx, const int32_t* cand_idx, int64_t n_cand, int64_t topn,
-                                  int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* ws, hipStream_t st);
+                         int64_t n_items, const WmfRowFilter& flt, int64_t n_cand, int64_t topn, int32_t n_slices, int32_t* out_items,
+                         float* out_scores, int32_t* out_count, void* ws, hipStream_t st);
 // (the sorted partial lists of a scan with the top-n epilogue of wmf_topn.h, n_slices a row, merged into the outputs)
 void wmf_launch_topn_merge(const unsigned long long* partial, int64_t n_rows, int n_slices, int topn, int32_t* out_rows, float* out_scores,
                            int32_t* out_count, hipStream_t st);
@@ -254,27 +252,19 @@ int wmf_recommend_slices(int64_t n_users, int64_t n_items, int64_t topn, int32_t
 int64_t wmf_recommend_wide_ws_bytes(int64_t n_users, int64_t topn, int32_t n_slices);
 int wmf_recommend_wide_slices(int64_t n_users, int64_t n_scan, int64_t topn, int32_t n_slices);
 int wmf_launch_recommend_wide(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
-                              int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* allow_bits,
-                              int64_t allow_words, const int32_t* allow_idx, const int32_t* cand_idx, int64_t n_cand, int64_t topn,
-                              int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* ws, hipStream_t st);
+                              int64_t n_items, const WmfRowFilter& flt, int64_t n_cand, int64_t topn, int32_t n_slices, int32_t* out_items,
+                              float* out_scores, int32_t* out_count, void* ws, hipStream_t st);
 // (... one list per (row, group) from one scan: group_of[j] = the group of item j, the mask form or no filter)
 int64_t wmf_recommend_grouped_ws_bytes(int64_t n_users, int32_t n_groups, int64_t topn, int32_t n_slices);
 int wmf_recommend_grouped_slices(int64_t n_users, int64_t n_items, int32_t n_groups, int64_t topn, int32_t n_slices);
 int wmf_launch_recommend_grouped(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
-                                 int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* allow_bits,
-                                 int64_t allow_words, const int32_t* allow_idx, const int32_t* group_of, int32_t n_groups, int64_t topn,
+                                 int64_t n_items, const WmfRowFilter& flt, const int32_t* group_of, int32_t n_groups, int64_t topn,
                                  int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* ws, hipStream_t st);
 // wmf_similar.hip: inverse row norms, and the neighbours of rows of one factor matrix among the rows of another (dot or cosine)
 void wmf_launch_row_inv_norms(const float* M, int64_t n, int f, int ld, int bias, float* out, hipStream_t st);
 int wmf_launch_similar(const float* queries, const float* catalogue, int ld, int bias, const float* q_inv_norm, const float* c_inv_norm,
-                       const int32_t* query_idx, int64_t n_queries, int64_t n_rows, int exclude_self, const int64_t* excl_indptr,
-                       const int32_t* excl_indices, int64_t topn, int32_t n_slices, int32_t* out_rows, float* out_scores,
-                       int32_t* out_count, void* ws, hipStream_t st);
-int wmf_launch_similar_filtered(const float* queries, const float* catalogue, int ld, int bias, const float* q_inv_norm, const float* c_inv_norm,
-                                const int32_t* query_idx, int64_t n_queries, int64_t n_rows, int exclude_self, const int64_t* excl_indptr,
-                                const int32_t* excl_indices, const uint32_t* allow_bits, int64_t allow_words, const int32_t* allow_idx,
-                                int64_t topn, int32_t n_slices, int32_t* out_rows, float* out_scores, int32_t* out_count, void* ws,
-                                hipStream_t st);
+                       const int32_t* query_idx, int64_t n_queries, int64_t n_rows, const WmfRowFilter& flt, int64_t topn, int32_t n_slices,
+                       int32_t* out_rows, float* out_scores, int32_t* out_count, void* ws, hipStream_t st);
 // wmf_mmr.hip: greedy MMR re-ranking of a row's candidate pool (the resident kernel for pool <= wmf_mmr_resident_pool, the
 // streaming one beyond), and the intra-list similarity of finished lists
 int64_t wmf_mmr_resident_pool(int f, int ld);

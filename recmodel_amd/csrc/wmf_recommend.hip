@@ -20,6 +20,13 @@
 //                               buffer per (user, group, slice) (wmf_topn_grouped.h); recommend_select_wide_kernel finishes them.
 // The keys of a user are pairwise distinct, so the result is a function of the scores alone: it cannot depend on the number of
 // slices, the grid or the order in which workgroups, waves or LDS atomics finish.  No float atomics.
+//
+// What the three scans share exists once.  Which items may enter a list -- the row's own id, its allow mask, its seen list, tested in
+// that order after the threshold -- is WmfRowFilter / WmfRowEligible (wmf_filter.h), which also says how the filter crosses a launch; the form of a
+// call's filter (none, mask, list) is a template argument of each scan and the suffix of its profile name (rec_form below).  The
+// in-place cut of a workspace buffer and its overwrite argument are rec_wide_cut_buffer (wmf_topn_wide.h).  A key is decoded into the
+// outputs by rec_write_slot.  Each family has one launch site, its instantiation chosen by wmf_dispatch_scan x wmf_dispatch_list; the
+// wide and the grouped launcher share the workspace split and the selection (rec_wide_scan_select).
 
 #include "wmf_common.h"
 #include "wmf_internal.h"
@@ -31,38 +38,34 @@
 #define WMF_REC_MERGE_GRID 1024      /* workgroups of the merge, four users each */
 #define WMF_REC_SLICE_TILES 64       /* an automatic slice holds at least this many 16-item tiles */
 
+// The forms of a call's filter (WmfRowFilter, wmf_filter.h), a template argument of every scan below and the suffix of its profile
+// name.  0, none: the whole catalogue, the seen lists only.  1, the mask form: the whole catalogue, an item inserted only where the
+// row's allow mask has its bit (the epilogue's MASK).  2, the list form: the positions of cand_idx (n_items of them) instead of the
+// catalogue (the scan's GATHER, two stages of 16 TPS ids past the epilogue's LDS), keys and seen lookups by the real id.  All score
+// in one arithmetic: a score does not depend on the item's place in a tile, so forms 1 and 2 give the bits of form 0 with the
+// ineligible items appended to every seen row.  The entry points refuse a call with both a mask and a list.
+static inline int rec_form(const WmfRowFilter& flt) { return flt.cand_idx ? 2 : flt.allow_bits ? 1 : 0; }
+static const char* const REC_FORM_NAME[3] = {"", "mask_", "list_"};
+static constexpr size_t rec_form_lds(int tps, int form) { return form == 2 ? (size_t)2 * tps * 16 * 4 : 0; }
+
 // NIT, TPS: the scan's width class; NW: waves of a workgroup (the key buffers of 16 NW users share the LDS with the stages)
-template <int NIT, int TPS, int NW>
+template <int NIT, int TPS, int NW, int FORM>
 __global__ __launch_bounds__(64 * NW) void recommend_scan_kernel(const float* __restrict__ users, const float* __restrict__ items, int ld,
                                                                  int bias, const int32_t* __restrict__ user_idx, int64_t n_users,
-                                                                 int64_t n_items, const int64_t* __restrict__ seen_indptr,
-                                                                 const int32_t* __restrict__ seen_indices, int topn, int cap,
-                                                                 int n_slices, int64_t tiles_per_slice, int64_t n_work,
+                                                                 int64_t n_items, WMF_FILTER_PARAMS, int topn, int cap, int n_slices,
+                                                                 int64_t tiles_per_slice, int64_t n_work,
                                                                  unsigned long long* __restrict__ partial) {
-    RecTopN<NW> p{seen_indptr, seen_indices, n_users, topn, cap, n_slices, partial};
-    wmf_catalogue_scan<NIT, TPS, NW>(users, items, ld, bias, user_idx, n_users, n_items, n_slices, tiles_per_slice, n_work, p);
-}
-
-// The filtered scans.  GATHER false, the mask form: the whole catalogue, an item inserted only where the row's allow mask has its
-// bit (RecTopN's MASK).  GATHER true, the list form: the positions of cand_idx (n_items of them) instead of the catalogue, keys and
-// seen lookups by the real id.  Either scores in the arithmetic of recommend_scan_kernel: a score does not depend on the item's
-// place in a tile, so both give the bits of that kernel with the ineligible items appended to every seen row.
-template <int NIT, int TPS, int NW, bool GATHER>
-__global__ __launch_bounds__(64 * NW) void recommend_scan_filtered_kernel(const float* __restrict__ users, const float* __restrict__ items, int ld,
-                                                                          int bias, const int32_t* __restrict__ user_idx, int64_t n_users,
-                                                                          int64_t n_items, const int64_t* __restrict__ seen_indptr,
-                                                                          const int32_t* __restrict__ seen_indices,
-                                                                          const uint32_t* __restrict__ allow_bits, int64_t allow_words,
-                                                                          const int32_t* __restrict__ allow_idx,
-                                                                          const int32_t* __restrict__ cand_idx, int topn, int cap, int n_slices,
-                                                                          int64_t tiles_per_slice, int64_t n_work,
-                                                                          unsigned long long* __restrict__ partial) {
     extern __shared__ __align__(16) unsigned char wmf_scan_smem[];
-    RecTopN<NW, false, !GATHER> p{seen_indptr, seen_indices, n_users, topn, cap, n_slices, partial};
-    p.allow_bits = allow_bits; p.allow_words = allow_words; p.allow_idx = allow_idx;
-    wmf_catalogue_scan<NIT, TPS, NW, decltype(p), WmfModelScore, GATHER>(
+    RecTopN<NW, false, FORM == 1> p{WMF_FILTER_FROM_PARAMS, n_users, topn, cap, n_slices, partial};
+    wmf_catalogue_scan<NIT, TPS, NW, decltype(p), WmfModelScore, FORM == 2>(
         users, items, ld, bias, user_idx, n_users, n_items, n_slices, tiles_per_slice, n_work, p, WmfModelScore(), cand_idx,
         reinterpret_cast<int32_t*>(wmf_scan_smem + wmf_scan_stage_bytes(TPS, ld) + rec_lds_bytes(NW, cap)));
+}
+
+// slot `at` of the outputs: the item and the score of `key`, or the padding for 0 (no key of an item is 0: its low word is ~id)
+__device__ __forceinline__ void rec_write_slot(int32_t* __restrict__ out_items, float* __restrict__ out_scores, int64_t at, unsigned long long key) {
+    out_items[at] = key ? (int32_t)(~(uint32_t)(key & 0xFFFFFFFFull)) : -1;
+    if (out_scores) out_scores[at] = key ? wmf_key_float((uint32_t)(key >> 32)) : -__builtin_inff();
 }
 
 // keys of `list` (topn of them, descending, 0 = none) above `key`
@@ -90,39 +93,27 @@ __global__ __launch_bounds__(256) void recommend_merge_kernel(const unsigned lon
             ++mine;
             int place = 0;
             for (int s = 0; s < n_slices && place < topn; ++s) place += rec_count_above(P + s * topn, topn, key);
-            if (place < topn) {
-                out_items[b * topn + place] = (int32_t)(~(uint32_t)(key & 0xFFFFFFFFull));
-                if (out_scores) out_scores[b * topn + place] = wmf_key_float((uint32_t)(key >> 32));
-            }
+            if (place < topn) rec_write_slot(out_items, out_scores, b * topn + place, key);
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
         const int count = min(mine, topn);
-        for (int k = count + lane; k < topn; k += 64) {
-            out_items[b * topn + k] = -1;
-            if (out_scores) out_scores[b * topn + k] = -__builtin_inff();
-        }
+        for (int k = count + lane; k < topn; k += 64) rec_write_slot(out_items, out_scores, b * topn + k, 0ull);
         if (lane == 0 && out_count) out_count[b] = count;
     }
 }
 
 // ---- beyond the LDS buffers: wmf_recommend_topn_wide -----------------------------------------------------------------------------
 // The same scans -- the same width classes, WmfModelScore, GATHER for the list form, so the same score bits -- with the epilogue of
-// wmf_topn_wide.h: the keys of a (batch position, slice) pair in the workspace, cut back by an exact select.  FORM 0: unfiltered,
-// 1: the mask form, 2: the list form.
+// wmf_topn_wide.h: the keys of a (batch position, slice) pair in the workspace, cut back by an exact select.  Any FORM.
 template <int NIT, int TPS, int NW, int FORM>
 __global__ __launch_bounds__(64 * NW) void recommend_scan_wide_kernel(const float* __restrict__ users, const float* __restrict__ items, int ld,
                                                                       int bias, const int32_t* __restrict__ user_idx, int64_t n_users,
-                                                                      int64_t n_items, const int64_t* __restrict__ seen_indptr,
-                                                                      const int32_t* __restrict__ seen_indices,
-                                                                      const uint32_t* __restrict__ allow_bits, int64_t allow_words,
-                                                                      const int32_t* __restrict__ allow_idx,
-                                                                      const int32_t* __restrict__ cand_idx, int topn, int cap, int n_slices,
+                                                                      int64_t n_items, WMF_FILTER_PARAMS, int topn, int cap, int n_slices,
                                                                       int64_t tiles_per_slice, int64_t n_work, unsigned long long* keys_ws,
                                                                       int32_t* counts_ws) {
     extern __shared__ __align__(16) unsigned char wmf_scan_smem[];
-    RecTopNWide<NW, FORM == 1> p{seen_indptr, seen_indices, n_users, topn, cap, n_slices, keys_ws, counts_ws};
-    p.allow_bits = allow_bits; p.allow_words = allow_words; p.allow_idx = allow_idx;
+    RecTopNWide<NW, FORM == 1> p{WMF_FILTER_FROM_PARAMS, n_users, topn, cap, n_slices, keys_ws, counts_ws};
     wmf_catalogue_scan<NIT, TPS, NW, decltype(p), WmfModelScore, FORM == 2>(
         users, items, ld, bias, user_idx, n_users, n_items, n_slices, tiles_per_slice, n_work, p, WmfModelScore(), cand_idx,
         reinterpret_cast<int32_t*>(wmf_scan_smem + wmf_scan_stage_bytes(TPS, ld) + rec_wide_lds_bytes(NW)));
@@ -178,11 +169,7 @@ __global__ __launch_bounds__(256) void recommend_select_wide_kernel(const unsign
                 __syncthreads();
             }
         }
-        for (int k = t; k < topn; k += 256) {
-            const unsigned long long key = k < count ? sel[k] : 0ull;
-            out_items[b * topn + k] = k < count ? (int32_t)(~(uint32_t)(key & 0xFFFFFFFFull)) : -1;
-            if (out_scores) out_scores[b * topn + k] = k < count ? wmf_key_float((uint32_t)(key >> 32)) : -__builtin_inff();
-        }
+        for (int k = t; k < topn; k += 256) rec_write_slot(out_items, out_scores, b * topn + k, k < count ? sel[k] : 0ull);
         if (t == 0 && out_count) out_count[b] = count;
         __syncthreads();                                           // sel and the counters are read before the next row resets them
     }
@@ -195,15 +182,11 @@ __global__ __launch_bounds__(256) void recommend_select_wide_kernel(const unsign
 template <int NIT, int TPS, int NW, bool MASK>
 __global__ __launch_bounds__(64 * NW) void recommend_scan_grouped_kernel(const float* __restrict__ users, const float* __restrict__ items, int ld,
                                                                          int bias, const int32_t* __restrict__ user_idx, int64_t n_users,
-                                                                         int64_t n_items, const int64_t* __restrict__ seen_indptr,
-                                                                         const int32_t* __restrict__ seen_indices,
-                                                                         const uint32_t* __restrict__ allow_bits, int64_t allow_words,
-                                                                         const int32_t* __restrict__ allow_idx,
+                                                                         int64_t n_items, WMF_FILTER_PARAMS,
                                                                          const int32_t* __restrict__ group_of, int n_groups, int topn, int cap,
                                                                          int n_slices, int64_t tiles_per_slice, int64_t n_work,
                                                                          unsigned long long* keys_ws, int32_t* counts_ws) {
-    RecTopNGrouped<TPS, NW, MASK> p{seen_indptr, seen_indices, n_users, topn, cap, n_slices, keys_ws, counts_ws, group_of, n_items, n_groups};
-    p.allow_bits = allow_bits; p.allow_words = allow_words; p.allow_idx = allow_idx;
+    RecTopNGrouped<TPS, NW, MASK> p{WMF_FILTER_FROM_PARAMS, n_users, topn, cap, n_slices, keys_ws, counts_ws, group_of, n_items, n_groups};
     wmf_catalogue_scan<NIT, TPS, NW>(users, items, ld, bias, user_idx, n_users, n_items, n_slices, tiles_per_slice, n_work, p);
 }
 
@@ -234,54 +217,25 @@ void wmf_launch_topn_merge(const unsigned long long* partial, int64_t n_rows, in
                out_rows, out_scores, out_count);
 }
 
+// every form of the LDS path; the list form cuts its slices and tiles from the n_cand positions
 int wmf_launch_recommend(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
-                         int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, int64_t topn, int32_t n_slices,
-                         int32_t* out_items, float* out_scores, int32_t* out_count, void* ws, hipStream_t st) {
-    WmfScanArgs a = {users, items, ld, bias, user_idx, n_users, n_items, wmf_recommend_slices(n_users, n_items, topn, n_slices), st};
-    unsigned long long* partial = reinterpret_cast<unsigned long long*>(ws);
-    const int n = (int)topn, cap = rec_cap(topn);
-    const int rc = wmf_dispatch_scan(ld, [&](auto nit, auto tps) {
-        return wmf_dispatch_list<4, 2>(rec_waves(topn), [&](auto nw) {
-            constexpr int NIT = decltype(nit)::value, TPS = decltype(tps)::value, NW = decltype(nw)::value;
-            wmf_scan_geometry(a, NW);
-            static const char* name = wmf_kname("recommend_scan_kernel<%d, %d, %d>", NIT, TPS, NW);
-            WMF_LAUNCH_LDS(name, (recommend_scan_kernel<NIT, TPS, NW>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW),
-                           wmf_scan_stage_bytes(TPS, ld) + rec_lds_bytes(NW, cap), st, a.users, a.items, a.ld, a.bias, a.user_idx, a.n_rows,
-                           a.n_items, seen_indptr, seen_indices, n, cap, a.n_slices, a.tiles_per_slice, a.n_work, partial);
-            return (int)WMF_L_OK;
-        });
-    });
-    if (rc) return rc;
-    wmf_launch_topn_merge(partial, n_users, a.n_slices, n, out_items, out_scores, out_count, st);
-    return WMF_L_OK;
-}
-
-// allow_bits: the mask form; cand_idx: the list form (slices and tiles are cut from the n_cand positions); exactly one of the two
-int wmf_launch_recommend_filtered(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
-                                  int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* allow_bits,
-                                  int64_t allow_words, const int32_t* allow_idx, const int32_t* cand_idx, int64_t n_cand, int64_t topn,
-                                  int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* ws, hipStream_t st) {
-    const int64_t n_scan = cand_idx ? n_cand : n_items;
+                         int64_t n_items, const WmfRowFilter& flt, int64_t n_cand, int64_t topn, int32_t n_slices, int32_t* out_items,
+                         float* out_scores, int32_t* out_count, void* ws, hipStream_t st) {
+    const int64_t n_scan = flt.cand_idx ? n_cand : n_items;
     WmfScanArgs a = {users, items, ld, bias, user_idx, n_users, n_scan, wmf_recommend_slices(n_users, n_scan, topn, n_slices), st};
     unsigned long long* partial = reinterpret_cast<unsigned long long*>(ws);
     const int n = (int)topn, cap = rec_cap(topn);
     const int rc = wmf_dispatch_scan(ld, [&](auto nit, auto tps) {
         return wmf_dispatch_list<4, 2>(rec_waves(topn), [&](auto nw) {
-            constexpr int NIT = decltype(nit)::value, TPS = decltype(tps)::value, NW = decltype(nw)::value;
-            wmf_scan_geometry(a, NW);
-            const size_t lds = wmf_scan_stage_bytes(TPS, ld) + rec_lds_bytes(NW, cap);
-            if (cand_idx) {
-                static const char* name = wmf_kname("recommend_scan_list_kernel<%d, %d, %d>", NIT, TPS, NW);
-                WMF_LAUNCH_LDS(name, (recommend_scan_filtered_kernel<NIT, TPS, NW, true>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW),
-                               lds + (size_t)2 * TPS * 16 * 4, st, a.users, a.items, a.ld, a.bias, a.user_idx, a.n_rows, a.n_items, seen_indptr,
-                               seen_indices, nullptr, (int64_t)0, nullptr, cand_idx, n, cap, a.n_slices, a.tiles_per_slice, a.n_work, partial);
-            } else {
-                static const char* name = wmf_kname("recommend_scan_mask_kernel<%d, %d, %d>", NIT, TPS, NW);
-                WMF_LAUNCH_LDS(name, (recommend_scan_filtered_kernel<NIT, TPS, NW, false>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW),
-                               lds, st, a.users, a.items, a.ld, a.bias, a.user_idx, a.n_rows, a.n_items, seen_indptr, seen_indices, allow_bits,
-                               allow_words, allow_idx, nullptr, n, cap, a.n_slices, a.tiles_per_slice, a.n_work, partial);
-            }
-            return (int)WMF_L_OK;
+            return wmf_dispatch_list<0, 1, 2>(rec_form(flt), [&](auto form) {
+                constexpr int NIT = decltype(nit)::value, TPS = decltype(tps)::value, NW = decltype(nw)::value, FORM = decltype(form)::value;
+                wmf_scan_geometry(a, NW);
+                static const char* name = wmf_kname("recommend_scan_%skernel<%d, %d, %d>", REC_FORM_NAME[FORM], NIT, TPS, NW);
+                WMF_LAUNCH_LDS(name, (recommend_scan_kernel<NIT, TPS, NW, FORM>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW),
+                               wmf_scan_stage_bytes(TPS, ld) + rec_lds_bytes(NW, cap) + rec_form_lds(TPS, FORM), st, a.users, a.items, a.ld,
+                               a.bias, a.user_idx, a.n_rows, a.n_items, WMF_FILTER_ARGS(flt), n, cap, a.n_slices, a.tiles_per_slice, a.n_work, partial);
+                return (int)WMF_L_OK;
+            });
         });
     });
     if (rc) return rc;
@@ -318,44 +272,42 @@ int wmf_recommend_wide_slices(int64_t n_users, int64_t n_scan, int64_t topn, int
     return (int)(s < 1 ? 1 : s);
 }
 
-// allow_bits: the mask form; cand_idx: the list form; neither: the whole catalogue.  Never both (the entry point refuses it).
-int wmf_launch_recommend_wide(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
-                              int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* allow_bits,
-                              int64_t allow_words, const int32_t* allow_idx, const int32_t* cand_idx, int64_t n_cand, int64_t topn,
-                              int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* ws, hipStream_t st) {
-    const int64_t n_scan = cand_idx ? n_cand : n_items;
-    WmfScanArgs a = {users, items, ld, bias, user_idx, n_users, n_scan, wmf_recommend_wide_slices(n_users, n_scan, topn, n_slices), st};
-    const int n = (int)topn, cap = WMF_RECOMMEND_WIDE_CAP(n);
+// What the launchers of the workspace buffers share: the workspace as [keys: n_virtual x n_slices buffers of cap][counts: one per
+// buffer], scan(keys, counts, cap) -- the launcher's own scan, a WmfLaunchRc -- and the selection over the n_virtual rows.
+template <class Scan>
+static int rec_wide_scan_select(void* ws, int64_t n_virtual, int n_slices, int topn, int32_t* out_items, float* out_scores,
+                                int32_t* out_count, hipStream_t st, Scan&& scan) {
+    const int cap = WMF_RECOMMEND_WIDE_CAP(topn);
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws);
-    int32_t* counts = reinterpret_cast<int32_t*>(keys + (size_t)n_users * a.n_slices * cap);
-    constexpr int NW = WMF_REC_WIDE_WAVES;
-    const int rc = wmf_dispatch_scan(ld, [&](auto nit, auto tps) {
-        constexpr int NIT = decltype(nit)::value, TPS = decltype(tps)::value;
-        wmf_scan_geometry(a, NW);
-        const size_t lds = wmf_scan_stage_bytes(TPS, ld) + rec_wide_lds_bytes(NW);
-        if (cand_idx) {
-            static const char* name = wmf_kname("recommend_scan_wide_list_kernel<%d, %d, %d>", NIT, TPS, NW);
-            WMF_LAUNCH_LDS(name, (recommend_scan_wide_kernel<NIT, TPS, NW, 2>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW),
-                           lds + (size_t)2 * TPS * 16 * 4, st, a.users, a.items, a.ld, a.bias, a.user_idx, a.n_rows, a.n_items, seen_indptr,
-                           seen_indices, nullptr, (int64_t)0, nullptr, cand_idx, n, cap, a.n_slices, a.tiles_per_slice, a.n_work, keys, counts);
-        } else if (allow_bits) {
-            static const char* name = wmf_kname("recommend_scan_wide_mask_kernel<%d, %d, %d>", NIT, TPS, NW);
-            WMF_LAUNCH_LDS(name, (recommend_scan_wide_kernel<NIT, TPS, NW, 1>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW), lds, st,
-                           a.users, a.items, a.ld, a.bias, a.user_idx, a.n_rows, a.n_items, seen_indptr, seen_indices, allow_bits, allow_words,
-                           allow_idx, nullptr, n, cap, a.n_slices, a.tiles_per_slice, a.n_work, keys, counts);
-        } else {
-            static const char* name = wmf_kname("recommend_scan_wide_kernel<%d, %d, %d>", NIT, TPS, NW);
-            WMF_LAUNCH_LDS(name, (recommend_scan_wide_kernel<NIT, TPS, NW, 0>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW), lds, st,
-                           a.users, a.items, a.ld, a.bias, a.user_idx, a.n_rows, a.n_items, seen_indptr, seen_indices, nullptr, (int64_t)0,
-                           nullptr, nullptr, n, cap, a.n_slices, a.tiles_per_slice, a.n_work, keys, counts);
-        }
-        return (int)WMF_L_OK;
-    });
+    int32_t* counts = reinterpret_cast<int32_t*>(keys + (size_t)n_virtual * n_slices * cap);
+    const int rc = scan(keys, counts, cap);
     if (rc) return rc;
-    const int64_t grid = n_users < WMF_REC_MERGE_GRID ? n_users : WMF_REC_MERGE_GRID;    // rows beyond it take another trip
-    WMF_LAUNCH("recommend_select_wide_kernel", recommend_select_wide_kernel, dim3((unsigned)grid), dim3(256), 0, st, keys, counts, n_users,
-               a.n_slices, n, cap, out_items, out_scores, out_count);
+    const int64_t grid = n_virtual < WMF_REC_MERGE_GRID ? n_virtual : WMF_REC_MERGE_GRID;    // rows beyond it take another trip
+    WMF_LAUNCH("recommend_select_wide_kernel", recommend_select_wide_kernel, dim3((unsigned)grid), dim3(256), 0, st, keys, counts, n_virtual,
+               n_slices, topn, cap, out_items, out_scores, out_count);
     return WMF_L_OK;
+}
+
+// any form of the filter
+int wmf_launch_recommend_wide(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
+                              int64_t n_items, const WmfRowFilter& flt, int64_t n_cand, int64_t topn, int32_t n_slices, int32_t* out_items,
+                              float* out_scores, int32_t* out_count, void* ws, hipStream_t st) {
+    const int64_t n_scan = flt.cand_idx ? n_cand : n_items;
+    WmfScanArgs a = {users, items, ld, bias, user_idx, n_users, n_scan, wmf_recommend_wide_slices(n_users, n_scan, topn, n_slices), st};
+    constexpr int NW = WMF_REC_WIDE_WAVES;
+    wmf_scan_geometry(a, NW);
+    return rec_wide_scan_select(ws, n_users, a.n_slices, (int)topn, out_items, out_scores, out_count, st, [&](auto* keys, auto* counts, int cap) {
+        return wmf_dispatch_scan(ld, [&](auto nit, auto tps) {
+            return wmf_dispatch_list<0, 1, 2>(rec_form(flt), [&](auto form) {
+                constexpr int NIT = decltype(nit)::value, TPS = decltype(tps)::value, FORM = decltype(form)::value;
+                static const char* name = wmf_kname("recommend_scan_wide_%skernel<%d, %d, %d>", REC_FORM_NAME[FORM], NIT, TPS, NW);
+                WMF_LAUNCH_LDS(name, (recommend_scan_wide_kernel<NIT, TPS, NW, FORM>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW),
+                               wmf_scan_stage_bytes(TPS, ld) + rec_wide_lds_bytes(NW) + rec_form_lds(TPS, FORM), st, a.users, a.items, a.ld,
+                               a.bias, a.user_idx, a.n_rows, a.n_items, WMF_FILTER_ARGS(flt), (int)topn, cap, a.n_slices, a.tiles_per_slice, a.n_work, keys, counts);
+                return (int)WMF_L_OK;
+            });
+        });
+    });
 }
 
 // ---- the grouped launcher ---------------------------------------------------------------------------------------------------
@@ -372,37 +324,26 @@ int wmf_recommend_grouped_slices(int64_t n_users, int64_t n_items, int32_t n_gro
     return wmf_recommend_wide_slices(n_users, n_items, topn * n_groups, n_slices);
 }
 
-// allow_bits: the mask form, or NULL.  The selection runs over the n_users * n_groups virtual rows.
+// the mask form or no filter; the selection runs over the n_users * n_groups virtual rows
 int wmf_launch_recommend_grouped(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
-                                 int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* allow_bits,
-                                 int64_t allow_words, const int32_t* allow_idx, const int32_t* group_of, int32_t n_groups, int64_t topn,
+                                 int64_t n_items, const WmfRowFilter& flt, const int32_t* group_of, int32_t n_groups, int64_t topn,
                                  int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* ws, hipStream_t st) {
     WmfScanArgs a = {users, items, ld, bias, user_idx, n_users, n_items, wmf_recommend_grouped_slices(n_users, n_items, n_groups, topn, n_slices), st};
-    const int n = (int)topn, cap = WMF_RECOMMEND_WIDE_CAP(n);
-    const int64_t n_virtual = n_users * n_groups;
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws);
-    int32_t* counts = reinterpret_cast<int32_t*>(keys + (size_t)n_virtual * a.n_slices * cap);
     constexpr int NW = WMF_REC_WIDE_WAVES;
-    const int rc = wmf_dispatch_scan(ld, [&](auto nit, auto tps) {
-        constexpr int NIT = decltype(nit)::value, TPS = decltype(tps)::value;
-        wmf_scan_geometry(a, NW);
-        const size_t lds = wmf_scan_stage_bytes(TPS, ld) + rec_grouped_lds_bytes(NW, n_groups);
-        if (allow_bits) {
-            static const char* name = wmf_kname("recommend_scan_grouped_mask_kernel<%d, %d, %d>", NIT, TPS, NW);
-            WMF_LAUNCH_LDS(name, (recommend_scan_grouped_kernel<NIT, TPS, NW, true>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW), lds, st,
-                           a.users, a.items, a.ld, a.bias, a.user_idx, a.n_rows, a.n_items, seen_indptr, seen_indices, allow_bits, allow_words,
-                           allow_idx, group_of, (int)n_groups, n, cap, a.n_slices, a.tiles_per_slice, a.n_work, keys, counts);
-        } else {
-            static const char* name = wmf_kname("recommend_scan_grouped_kernel<%d, %d, %d>", NIT, TPS, NW);
-            WMF_LAUNCH_LDS(name, (recommend_scan_grouped_kernel<NIT, TPS, NW, false>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW), lds, st,
-                           a.users, a.items, a.ld, a.bias, a.user_idx, a.n_rows, a.n_items, seen_indptr, seen_indices, nullptr, (int64_t)0,
-                           nullptr, group_of, (int)n_groups, n, cap, a.n_slices, a.tiles_per_slice, a.n_work, keys, counts);
-        }
-        return (int)WMF_L_OK;
+    wmf_scan_geometry(a, NW);
+    return rec_wide_scan_select(ws, n_users * n_groups, a.n_slices, (int)topn, out_items, out_scores, out_count, st,
+                                [&](auto* keys, auto* counts, int cap) {
+        return wmf_dispatch_scan(ld, [&](auto nit, auto tps) {
+            return wmf_dispatch_list<0, 1>(rec_form(flt), [&](auto form) {
+                constexpr int NIT = decltype(nit)::value, TPS = decltype(tps)::value;
+                constexpr bool MASK = decltype(form)::value == 1;
+                static const char* name = wmf_kname("recommend_scan_grouped_%skernel<%d, %d, %d>", REC_FORM_NAME[MASK], NIT, TPS, NW);
+                WMF_LAUNCH_LDS(name, (recommend_scan_grouped_kernel<NIT, TPS, NW, MASK>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW),
+                               wmf_scan_stage_bytes(TPS, ld) + rec_grouped_lds_bytes(NW, n_groups), st, a.users, a.items, a.ld, a.bias, a.user_idx,
+                               a.n_rows, a.n_items, WMF_FILTER_ARGS(flt), group_of, (int)n_groups, (int)topn, cap, a.n_slices, a.tiles_per_slice, a.n_work, keys,
+                               counts);
+                return (int)WMF_L_OK;
+            });
+        });
     });
-    if (rc) return rc;
-    const int64_t grid = n_virtual < WMF_REC_MERGE_GRID ? n_virtual : WMF_REC_MERGE_GRID;    // rows beyond it take another trip
-    WMF_LAUNCH("recommend_select_wide_kernel", recommend_select_wide_kernel, dim3((unsigned)grid), dim3(256), 0, st, keys, counts, n_virtual,
-               a.n_slices, n, cap, out_items, out_scores, out_count);
-    return WMF_L_OK;
 }

@@ -79,36 +79,17 @@ struct WmfScaledScore {
     __device__ __forceinline__ float score(float acc, float rs, float is) { return (acc * rs) * is; }
 };
 
-// NIT, TPS, NW: as recommend_scan_kernel
-template <int NIT, int TPS, int NW>
+// NIT, TPS, NW: as recommend_scan_kernel.  The row's own id (self_idx) is always tested; MASK: an allow mask per query as well
+// (wmf_filter.h), and the row's own id is still refused when the mask allows it.  There is no list form.
+template <int NIT, int TPS, int NW, bool MASK>
 __global__ __launch_bounds__(64 * NW) void similar_scan_kernel(const float* __restrict__ queries, const float* __restrict__ catalogue, int ld,
                                                                int bias, const float* __restrict__ q_scale, const float* __restrict__ c_scale,
                                                                const int32_t* __restrict__ query_idx, int64_t n_queries, int64_t n_rows,
-                                                               const int32_t* __restrict__ self_idx, const int64_t* __restrict__ excl_indptr,
-                                                               const int32_t* __restrict__ excl_indices, int topn, int cap, int n_slices,
+                                                               WMF_FILTER_PARAMS, int topn, int cap, int n_slices,
                                                                int64_t tiles_per_slice, int64_t n_work, unsigned long long* __restrict__ partial) {
     extern __shared__ __align__(16) unsigned char wmf_scan_smem[];
     static_assert(TPS * 16 <= 64 * NW, "one thread per catalogue scale of a stage");
-    RecTopN<NW, true> p{excl_indptr, excl_indices, n_queries, topn, cap, n_slices, partial, self_idx};
-    WmfScaledScore<TPS> sp{q_scale, c_scale, reinterpret_cast<float*>(wmf_scan_smem + wmf_scan_stage_bytes(TPS, ld) + rec_lds_bytes(NW, cap))};
-    wmf_catalogue_scan<NIT, TPS, NW>(queries, catalogue, ld, bias, query_idx, n_queries, n_rows, n_slices, tiles_per_slice, n_work, p, sp);
-}
-
-// ... with an allow mask per query (RecTopN's MASK): a row is inserted only where the query's mask has its bit; the row's own id is
-// still refused when the mask allows it
-template <int NIT, int TPS, int NW>
-__global__ __launch_bounds__(64 * NW) void similar_scan_filtered_kernel(const float* __restrict__ queries, const float* __restrict__ catalogue, int ld,
-                                                                        int bias, const float* __restrict__ q_scale, const float* __restrict__ c_scale,
-                                                                        const int32_t* __restrict__ query_idx, int64_t n_queries, int64_t n_rows,
-                                                                        const int32_t* __restrict__ self_idx, const int64_t* __restrict__ excl_indptr,
-                                                                        const int32_t* __restrict__ excl_indices,
-                                                                        const uint32_t* __restrict__ allow_bits, int64_t allow_words,
-                                                                        const int32_t* __restrict__ allow_idx, int topn, int cap, int n_slices,
-                                                                        int64_t tiles_per_slice, int64_t n_work, unsigned long long* __restrict__ partial) {
-    extern __shared__ __align__(16) unsigned char wmf_scan_smem[];
-    static_assert(TPS * 16 <= 64 * NW, "one thread per catalogue scale of a stage");
-    RecTopN<NW, true, true> p{excl_indptr, excl_indices, n_queries, topn, cap, n_slices, partial, self_idx};
-    p.allow_bits = allow_bits; p.allow_words = allow_words; p.allow_idx = allow_idx;
+    RecTopN<NW, true, MASK> p{WMF_FILTER_FROM_PARAMS, n_queries, topn, cap, n_slices, partial};
     WmfScaledScore<TPS> sp{q_scale, c_scale, reinterpret_cast<float*>(wmf_scan_smem + wmf_scan_stage_bytes(TPS, ld) + rec_lds_bytes(NW, cap))};
     wmf_catalogue_scan<NIT, TPS, NW>(queries, catalogue, ld, bias, query_idx, n_queries, n_rows, n_slices, tiles_per_slice, n_work, p, sp);
 }
@@ -120,50 +101,26 @@ void wmf_launch_row_inv_norms(const float* M, int64_t n, int f, int ld, int bias
     WMF_LAUNCH("row_inv_norms_kernel", row_inv_norms_kernel, dim3((unsigned)grid), dim3(256), 0, st, M, n, f, ld, bias ? 1 : 0, out);
 }
 
+// flt: the exclusion lists as its seen lists, self_idx = query_idx to leave every row out of its own list, allow masks or none
 int wmf_launch_similar(const float* queries, const float* catalogue, int ld, int bias, const float* q_inv_norm, const float* c_inv_norm,
-                       const int32_t* query_idx, int64_t n_queries, int64_t n_rows, int exclude_self, const int64_t* excl_indptr,
-                       const int32_t* excl_indices, int64_t topn, int32_t n_slices, int32_t* out_rows, float* out_scores,
-                       int32_t* out_count, void* ws, hipStream_t st) {
+                       const int32_t* query_idx, int64_t n_queries, int64_t n_rows, const WmfRowFilter& flt, int64_t topn, int32_t n_slices,
+                       int32_t* out_rows, float* out_scores, int32_t* out_count, void* ws, hipStream_t st) {
     WmfScanArgs a = {queries, catalogue, ld, bias, query_idx, n_queries, n_rows, wmf_recommend_slices(n_queries, n_rows, topn, n_slices), st};
     unsigned long long* partial = reinterpret_cast<unsigned long long*>(ws);
-    const int32_t* self_idx = exclude_self ? query_idx : nullptr;
     const int n = (int)topn, cap = rec_cap(topn);
     const int rc = wmf_dispatch_scan(ld, [&](auto nit, auto tps) {
         return wmf_dispatch_list<4, 2>(rec_waves(topn), [&](auto nw) {
-            constexpr int NIT = decltype(nit)::value, TPS = decltype(tps)::value, NW = decltype(nw)::value;
-            wmf_scan_geometry(a, NW);
-            static const char* name = wmf_kname("similar_scan_kernel<%d, %d, %d>", NIT, TPS, NW);
-            WMF_LAUNCH_LDS(name, (similar_scan_kernel<NIT, TPS, NW>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW),
-                           wmf_scan_stage_bytes(TPS, ld) + rec_lds_bytes(NW, cap) + (size_t)2 * TPS * 16 * 4, st, a.users, a.items, a.ld, a.bias,
-                           q_inv_norm, c_inv_norm, a.user_idx, a.n_rows, a.n_items, self_idx, excl_indptr, excl_indices, n, cap, a.n_slices,
-                           a.tiles_per_slice, a.n_work, partial);
-            return (int)WMF_L_OK;
-        });
-    });
-    if (rc) return rc;
-    wmf_launch_topn_merge(partial, n_queries, a.n_slices, n, out_rows, out_scores, out_count, st);
-    return WMF_L_OK;
-}
-
-int wmf_launch_similar_filtered(const float* queries, const float* catalogue, int ld, int bias, const float* q_inv_norm, const float* c_inv_norm,
-                                const int32_t* query_idx, int64_t n_queries, int64_t n_rows, int exclude_self, const int64_t* excl_indptr,
-                                const int32_t* excl_indices, const uint32_t* allow_bits, int64_t allow_words, const int32_t* allow_idx,
-                                int64_t topn, int32_t n_slices, int32_t* out_rows, float* out_scores, int32_t* out_count, void* ws,
-                                hipStream_t st) {
-    WmfScanArgs a = {queries, catalogue, ld, bias, query_idx, n_queries, n_rows, wmf_recommend_slices(n_queries, n_rows, topn, n_slices), st};
-    unsigned long long* partial = reinterpret_cast<unsigned long long*>(ws);
-    const int32_t* self_idx = exclude_self ? query_idx : nullptr;
-    const int n = (int)topn, cap = rec_cap(topn);
-    const int rc = wmf_dispatch_scan(ld, [&](auto nit, auto tps) {
-        return wmf_dispatch_list<4, 2>(rec_waves(topn), [&](auto nw) {
-            constexpr int NIT = decltype(nit)::value, TPS = decltype(tps)::value, NW = decltype(nw)::value;
-            wmf_scan_geometry(a, NW);
-            static const char* name = wmf_kname("similar_scan_mask_kernel<%d, %d, %d>", NIT, TPS, NW);
-            WMF_LAUNCH_LDS(name, (similar_scan_filtered_kernel<NIT, TPS, NW>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW),
-                           wmf_scan_stage_bytes(TPS, ld) + rec_lds_bytes(NW, cap) + (size_t)2 * TPS * 16 * 4, st, a.users, a.items, a.ld, a.bias,
-                           q_inv_norm, c_inv_norm, a.user_idx, a.n_rows, a.n_items, self_idx, excl_indptr, excl_indices, allow_bits, allow_words,
-                           allow_idx, n, cap, a.n_slices, a.tiles_per_slice, a.n_work, partial);
-            return (int)WMF_L_OK;
+            return wmf_dispatch_list<0, 1>(flt.allow_bits ? 1 : 0, [&](auto form) {
+                constexpr int NIT = decltype(nit)::value, TPS = decltype(tps)::value, NW = decltype(nw)::value;
+                constexpr bool MASK = decltype(form)::value == 1;
+                wmf_scan_geometry(a, NW);
+                static const char* name = wmf_kname("similar_scan_%skernel<%d, %d, %d>", MASK ? "mask_" : "", NIT, TPS, NW);
+                WMF_LAUNCH_LDS(name, (similar_scan_kernel<NIT, TPS, NW, MASK>), 112 * 1024, dim3((unsigned)a.grid), dim3(64 * NW),
+                               wmf_scan_stage_bytes(TPS, ld) + rec_lds_bytes(NW, cap) + (size_t)2 * TPS * 16 * 4, st, a.users, a.items, a.ld, a.bias,
+                               q_inv_norm, c_inv_norm, a.user_idx, a.n_rows, a.n_items, WMF_FILTER_ARGS(flt), n, cap, a.n_slices, a.tiles_per_slice, a.n_work,
+                               partial);
+                return (int)WMF_L_OK;
+            });
         });
     });
     if (rc) return rc;

@@ -1,8 +1,10 @@
 // The running top-n of a catalogue scan (gfx950): the epilogue policy that wmf_recommend.hip and wmf_similar.hip hand to
 // wmf_catalogue_scan, and the sizes of its LDS buffers.  The partial lists it writes are merged by recommend_merge_kernel
-// (wmf_recommend.hip, wmf_launch_topn_merge).
+// (wmf_recommend.hip, wmf_launch_topn_merge).  Which keys may enter a list, and in what order that is tested, is wmf_filter.h's;
+// the epilogues here and in wmf_topn_wide.h / wmf_topn_grouped.h compare with their threshold and ask WmfRowEligible::pass.
 #pragma once
 #include "wmf_scan.h"
+#include "wmf_filter.h"
 
 // The buffers of the wave's users in `mask` (bit u = user u of 16) cut back to their topn best, sorted best first; thr[u] = the
 // topn-th best once there are that many.  A key's place is the number of keys above it (the keys are distinct): every lane
@@ -41,25 +43,18 @@ __device__ __forceinline__ void rec_compact(unsigned mask, unsigned long long* _
 
 // The scan's epilogue: a running top-n per user.  LDS past the stages: [keys: 16 users x cap per wave][thresholds][counts].
 // partial[(b * n_slices + slice) * topn + k]: the k-th best key of batch position b in that slice, 0 = none.
-// SELF: the row's own id (self_idx[b], the catalogue row that batch position b is) is never inserted; self_idx == NULL: no such row.
-// MASK: an allow mask per row, allow_bits[allow_idx[b]][allow_words] (allow_idx == NULL: mask 0 for every row; allow_idx[b] == -1:
-// row b has none): item j may be inserted only when bit j & 31 of word j >> 5 is set.  Tested at insertion, after the threshold and
-// before the seen list (one load against the search's twenty): a masked-out item never enters a buffer or raises a threshold.
+// SELF, MASK: the tests of WmfRowEligible (wmf_filter.h) this instantiation runs besides the seen list; without them its code is
+// that of the plain kernel.
 template <int NW, bool SELF = false, bool MASK = false>
 struct RecTopN {
-    const int64_t* __restrict__ seen_indptr; const int32_t* __restrict__ seen_indices;
+    WmfRowFilter filter;
     int64_t n_users; int topn, cap, n_slices;
     unsigned long long* __restrict__ partial;
-    const int32_t* __restrict__ self_idx = nullptr;               // (self_idx and self[] are dead without SELF: the kernels' code is the same)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
     unsigned long long* keys; unsigned long long* thr_l; int* cnt;
     int64_t u0; int sl;
     unsigned long long thr[4];
-    int64_t seen_lo[4], seen_hi[4];
-    int32_t self[4];
-    // (MASK; set by the kernel after the aggregate's members above, and dead without MASK like self[])
-    const uint32_t* __restrict__ allow_bits = nullptr; int64_t allow_words = 0; const int32_t* __restrict__ allow_idx = nullptr;
-    const uint32_t* words[4];
+    WmfRowEligible<SELF, MASK> ok;
 
     __device__ __forceinline__ void begin(unsigned char* lds, int64_t u0_, int sl_) {
         u0 = u0_; sl = sl_;
@@ -68,34 +63,13 @@ struct RecTopN {
         cnt = reinterpret_cast<int*>(lds + ((size_t)NW * 16 * cap + NW * 16) * 8) + wave * 16;
         if (lane < 16) { cnt[lane] = 0; thr_l[lane] = 0ull; }
 #pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            thr[reg] = 0ull; seen_lo[reg] = 0; seen_hi[reg] = 0;
-            const int64_t b = u0 + 4 * q + reg;
-            if (seen_indptr && b < n_users) { seen_lo[reg] = seen_indptr[b]; seen_hi[reg] = seen_indptr[b + 1]; }
-            if constexpr (SELF) self[reg] = (self_idx && b < n_users) ? self_idx[b] : -1;
-            if constexpr (MASK) {
-                const int32_t g = b < n_users ? (allow_idx ? allow_idx[b] : 0) : -1;
-                words[reg] = g >= 0 ? allow_bits + (int64_t)g * allow_words : nullptr;
-            }
-        }
+        for (int reg = 0; reg < 4; ++reg) thr[reg] = 0ull;
+        ok.begin(filter, u0, q, n_users);
         wmf_wave_sync();
     }
-    // A key that beats the user's threshold is looked up in the user's sorted seen list and, if it is not there, appended
+    // A key that beats the user's threshold and passes the filter is appended
     __device__ __forceinline__ void score(int reg, int, int64_t item, unsigned long long key, bool in_range) {
-        bool take = in_range && u0 + 4 * q + reg < n_users && key > thr[reg];
-        if constexpr (SELF) take = take && (int32_t)item != self[reg];
-        if constexpr (MASK) {
-            if (take && words[reg]) take = (words[reg][item >> 5] >> (item & 31)) & 1u;
-        }
-        if (take && seen_lo[reg] < seen_hi[reg]) {
-            int64_t lo = seen_lo[reg], hi = seen_hi[reg];
-            while (lo < hi) {                                      // first entry >= item
-                const int64_t mid = (lo + hi) >> 1;
-                if (seen_indices[mid] < (int32_t)item) lo = mid + 1; else hi = mid;
-            }
-            take = !(lo < seen_hi[reg] && seen_indices[lo] == (int32_t)item);
-        }
-        if (take) {
+        if (in_range && u0 + 4 * q + reg < n_users && key > thr[reg] && ok.pass(reg, item)) {
             const int slot = atomicAdd(&cnt[4 * q + reg], 1);      // at most 16 per user and tile: below cap
             if (slot < cap) keys[(4 * q + reg) * cap + slot] = key;
         }

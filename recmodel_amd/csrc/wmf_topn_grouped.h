@@ -9,7 +9,7 @@
 // The overflow bound carries over: a tile adds at most 16 keys to a row, hence at most 16 to any one of the row's buffers, so a buffer
 // holding <= cap - 16 keys before a tile cannot overflow within it.  A lane whose append returns a slot >= cap - 16 (the count has
 // passed cap - 16) marks its (row, group); after the tile the wave cuts every marked buffer back to its topn best (<= cap - 16) with
-// rec_wide_kth and RecTopNWide's in-place compaction, re-checking the count so that a buffer marked by several lanes is cut once.
+// rec_wide_cut_buffer (wmf_topn_wide.h: the select and the in-place compaction), re-checking the count so that a buffer marked by several lanes is cut once.
 // Who owns what is unchanged: one wave owns all buffers of its 16 rows for the whole work unit.
 //
 // The group ids travel one stage ahead of their tiles: at the first tile of a stage, lane (r, q) asks for the id of item row r of
@@ -22,7 +22,7 @@
 // RecTopN.  TPS: the scan's tiles per stage.
 template <int TPS, int NW, bool MASK = false>
 struct RecTopNGrouped {
-    const int64_t* __restrict__ seen_indptr; const int32_t* __restrict__ seen_indices;
+    WmfRowFilter filter;
     int64_t n_users; int topn, cap, n_slices;
     unsigned long long* keys_ws; int32_t* counts_ws;              // (not restrict: lanes read what other lanes of the wave wrote)
     const int32_t* __restrict__ group_of; int64_t n_items; int n_groups;
@@ -30,9 +30,7 @@ struct RecTopNGrouped {
     unsigned long long* thr_l; int* cnt; unsigned* hist;
     int64_t u0; int sl;
     unsigned long long* buf0; int64_t row_stride, group_stride;    // the buffer of (row u0 + 4 q + reg, group g): buf0 + reg * row_stride + g * group_stride
-    int64_t seen_lo[4], seen_hi[4];
-    const uint32_t* __restrict__ allow_bits = nullptr; int64_t allow_words = 0; const int32_t* __restrict__ allow_idx = nullptr;
-    const uint32_t* words[4];
+    WmfRowEligible<false, MASK> ok;
     int32_t gvec, gpre; int64_t pre_base;                          // the ids of this stage's tiles and of the next one's, and where those start
     int32_t g; unsigned marked;                                    // this tile: the lane's group id; bit reg: (row 4 q + reg, g) has passed cap - 16
 
@@ -50,16 +48,7 @@ struct RecTopNGrouped {
         row_stride = group_stride * n_groups;
         buf0 = row_buf(u0 + 4 * q, 0);                             // (rows past the batch: never dereferenced)
         pre_base = -1; gvec = -1; gpre = -1; g = -1; marked = 0u;
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            seen_lo[reg] = 0; seen_hi[reg] = 0;
-            const int64_t b = u0 + 4 * q + reg;
-            if (seen_indptr && b < n_users) { seen_lo[reg] = seen_indptr[b]; seen_hi[reg] = seen_indptr[b + 1]; }
-            if constexpr (MASK) {
-                const int32_t m = b < n_users ? (allow_idx ? allow_idx[b] : 0) : -1;
-                words[reg] = m >= 0 ? allow_bits + (int64_t)m * allow_words : nullptr;
-            }
-        }
+        ok.begin(filter, u0, q, n_users);
         wmf_wave_sync();
     }
     // the group id of this lane's item of the stage's j-th tile (item = 16 tile + r: this policy has no list form)
@@ -78,25 +67,13 @@ struct RecTopNGrouped {
         if (reg == 0) fetch(j, item);
         bool take = in_range && u0 + 4 * q + reg < n_users && (unsigned)g < (unsigned)n_groups;   // unsigned: -1 and its like are no shelf
         const int li = (4 * q + reg) * n_groups + (take ? g : 0);
-        if (take) take = key > thr_l[li];
-        if constexpr (MASK) {
-            if (take && words[reg]) take = (words[reg][item >> 5] >> (item & 31)) & 1u;
-        }
-        if (take && seen_lo[reg] < seen_hi[reg]) {
-            int64_t lo = seen_lo[reg], hi = seen_hi[reg];
-            while (lo < hi) {                                      // first entry >= item
-                const int64_t mid = (lo + hi) >> 1;
-                if (seen_indices[mid] < (int32_t)item) lo = mid + 1; else hi = mid;
-            }
-            take = !(lo < seen_hi[reg] && seen_indices[lo] == (int32_t)item);
-        }
-        if (take) {
+        if (take && key > thr_l[li] && ok.pass(reg, item)) {       // (the buffer's threshold lives in LDS: one per (row, group))
             const int slot = atomicAdd(&cnt[li], 1);               // at most 16 per buffer and tile: below cap
             if (slot < cap) buf0[reg * row_stride + g * group_stride + slot] = key;
             if (slot >= cap - 16) marked |= 1u << reg;
         }
     }
-    // The buffers the lanes of `who` marked, cut back to their topn best as RecTopNWide::cut does it; the new threshold goes to LDS.
+    // The buffers the lanes of `who` marked, cut back to their topn best (rec_wide_cut_buffer); the new threshold goes to LDS.
     __device__ __forceinline__ void cut(unsigned long long who) {
         rec_wide_drain();                                          // the keys other lanes appended
         while (who) {
@@ -110,17 +87,7 @@ struct RecTopNGrouped {
                 const int li = u * n_groups + grp;
                 const int have = __builtin_amdgcn_readfirstlane(cnt[li]);
                 if (have <= cap - 16) continue;                    // another lane marked it too: it is cut already
-                unsigned long long* ku = row_buf(u0 + u, grp);
-                const int n = min(have, cap);
-                const unsigned long long T = rec_wide_kth<64>(ku, nullptr, 1, 0, n, cap, topn, hist, lane);
-                int out = 0;
-                for (int e0 = 0; e0 < n; e0 += 64) {
-                    const unsigned long long key = e0 + lane < n ? ku[e0 + lane] : 0ull;
-                    const bool keep = key >= T && e0 + lane < n;
-                    const unsigned long long mm = __ballot(keep);
-                    if (keep) ku[out + __popcll(mm & ((1ull << lane) - 1ull))] = key;
-                    out += __popcll(mm);
-                }
+                const unsigned long long T = rec_wide_cut_buffer(row_buf(u0 + u, grp), min(have, cap), cap, topn, hist, lane);
                 if (lane == 0) { cnt[li] = topn; thr_l[li] = T; }
                 wmf_wave_sync();                                   // the count before the next look at it
             }

@@ -2,13 +2,14 @@
 // WMF_RECOMMEND_WIDE_MAX_TOPN.  A row's keys live in the WORKSPACE, one buffer of `cap` keys per (batch position, slice) pair; counts
 // and thresholds stay in LDS and registers as in RecTopN (wmf_topn.h).  A buffer that the next tile could overflow is cut back to its
 // topn best by an exact radix select of the topn-th largest key (the keys of a row are pairwise distinct, so that key is unique) and
-// one in-place compaction pass; nothing is sorted during the scan.  recommend_select_wide_kernel (wmf_recommend.hip) selects and
-// sorts the topn best of a row's slices with the same select.
+// one in-place compaction pass (rec_wide_cut_buffer, which RecTopNGrouped calls too); nothing is sorted during the scan.
+// recommend_select_wide_kernel (wmf_recommend.hip) selects and sorts the topn best of a row's slices with the same select.
 //
 // Who owns what: one wave owns the buffers of its 16 rows for the whole launch, and no other wave of the grid reads or writes them
 // before the kernel ends.  What orders the wave's own global accesses: see rec_wide_drain.
 #pragma once
 #include "wmf_scan.h"
+#include "wmf_filter.h"
 
 // A lane's global store followed by ANOTHER lane's load of the same address, both of one wave.  A wave issues its vector-memory
 // instructions in program order and all of them go through the one vector L1 of its CU, which writes through to L2; VM_CNT counts a
@@ -78,12 +79,29 @@ __device__ __forceinline__ unsigned long long rec_wide_kth(const unsigned long l
     return prefix;
 }
 
+// A buffer of n keys (n <= cap) cut back, in place, to its topn best, by one wave: the topn-th largest key T (returned), then the keys
+// >= T moved to the front, 64 at a time.  THE overwrite argument of every in-place cut: a chunk is loaded before any of its keys is
+// stored (the store's data depends on the load), and it is stored at or below where it was read, so no key is overwritten before it
+// is read.  The caller drains (rec_wide_drain) before -- the keys other lanes appended -- and after, and keeps the count and threshold.
+__device__ __forceinline__ unsigned long long rec_wide_cut_buffer(unsigned long long* ku, int n, int cap, int topn, unsigned* hist, int lane) {
+    const unsigned long long T = rec_wide_kth<64>(ku, nullptr, 1, 0, n, cap, topn, hist, lane);
+    int out = 0;
+    for (int e0 = 0; e0 < n; e0 += 64) {
+        const unsigned long long key = e0 + lane < n ? ku[e0 + lane] : 0ull;
+        const bool keep = key >= T && e0 + lane < n;
+        const unsigned long long m = __ballot(keep);
+        if (keep) ku[out + __popcll(m & ((1ull << lane) - 1ull))] = key;
+        out += __popcll(m);
+    }
+    return T;
+}
+
 // The scan's epilogue.  Workspace: keys[(b * n_slices + slice) * cap + e], e < counts[b * n_slices + slice], in no order, the topn
 // best eligible keys of that slice among them.  LDS past the stages: [thresholds: 16 per wave, 8 B][counts: 16 per wave][histogram:
 // 256 per wave].  MASK as in RecTopN.
 template <int NW, bool MASK = false>
 struct RecTopNWide {
-    const int64_t* __restrict__ seen_indptr; const int32_t* __restrict__ seen_indices;
+    WmfRowFilter filter;
     int64_t n_users; int topn, cap, n_slices;
     unsigned long long* keys_ws; int32_t* counts_ws;              // (not restrict: lanes read what other lanes of the wave wrote)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
@@ -91,9 +109,7 @@ struct RecTopNWide {
     int64_t u0; int sl;
     unsigned long long thr[4];
     unsigned long long* buf0; int64_t row_stride;                  // the buffer of row u0 + 4 q + reg: buf0 + reg * row_stride
-    int64_t seen_lo[4], seen_hi[4];
-    const uint32_t* __restrict__ allow_bits = nullptr; int64_t allow_words = 0; const int32_t* __restrict__ allow_idx = nullptr;
-    const uint32_t* words[4];
+    WmfRowEligible<false, MASK> ok;
 
     __device__ __forceinline__ unsigned long long* row_buf(int64_t b) const { return keys_ws + ((size_t)b * n_slices + sl) * (size_t)cap; }
     __device__ __forceinline__ void begin(unsigned char* lds, int64_t u0_, int sl_) {
@@ -105,54 +121,23 @@ struct RecTopNWide {
         buf0 = row_buf(u0 + 4 * q);                                // (rows past the batch: never dereferenced)
         row_stride = (int64_t)n_slices * cap;
 #pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            thr[reg] = 0ull; seen_lo[reg] = 0; seen_hi[reg] = 0;
-            const int64_t b = u0 + 4 * q + reg;
-            if (seen_indptr && b < n_users) { seen_lo[reg] = seen_indptr[b]; seen_hi[reg] = seen_indptr[b + 1]; }
-            if constexpr (MASK) {
-                const int32_t g = b < n_users ? (allow_idx ? allow_idx[b] : 0) : -1;
-                words[reg] = g >= 0 ? allow_bits + (int64_t)g * allow_words : nullptr;
-            }
-        }
+        for (int reg = 0; reg < 4; ++reg) thr[reg] = 0ull;
+        ok.begin(filter, u0, q, n_users);
         wmf_wave_sync();
     }
     __device__ __forceinline__ void score(int reg, int, int64_t item, unsigned long long key, bool in_range) {
-        bool take = in_range && u0 + 4 * q + reg < n_users && key > thr[reg];
-        if constexpr (MASK) {
-            if (take && words[reg]) take = (words[reg][item >> 5] >> (item & 31)) & 1u;
-        }
-        if (take && seen_lo[reg] < seen_hi[reg]) {
-            int64_t lo = seen_lo[reg], hi = seen_hi[reg];
-            while (lo < hi) {                                      // first entry >= item
-                const int64_t mid = (lo + hi) >> 1;
-                if (seen_indices[mid] < (int32_t)item) lo = mid + 1; else hi = mid;
-            }
-            take = !(lo < seen_hi[reg] && seen_indices[lo] == (int32_t)item);
-        }
-        if (take) {
+        if (in_range && u0 + 4 * q + reg < n_users && key > thr[reg] && ok.pass(reg, item)) {
             const int slot = atomicAdd(&cnt[4 * q + reg], 1);      // at most 16 per row and tile: below cap
             if (slot < cap) buf0[reg * row_stride + slot] = key;
         }
     }
-    // The buffers of the wave's rows in `full` (bit u = row u of 16) cut back to their topn best: the topn-th largest key T, then the
-    // keys >= T moved to the front, 64 at a time.  A chunk is loaded before any of its keys is stored (the store's data depends on
-    // the load), and it is stored at or below where it was read, so no key is overwritten before it is read.
+    // The buffers of the wave's rows in `full` (bit u = row u of 16) cut back to their topn best (rec_wide_cut_buffer)
     __device__ __forceinline__ void cut(unsigned full) {
         rec_wide_drain();                                          // the keys other lanes appended
         while (full) {
             const int u = __builtin_ctz(full);
             full &= full - 1;
-            unsigned long long* ku = row_buf(u0 + u);
-            const int n = min(cnt[u], cap);
-            const unsigned long long T = rec_wide_kth<64>(ku, nullptr, 1, 0, n, cap, topn, hist, lane);
-            int out = 0;
-            for (int e0 = 0; e0 < n; e0 += 64) {
-                const unsigned long long key = e0 + lane < n ? ku[e0 + lane] : 0ull;
-                const bool keep = key >= T && e0 + lane < n;
-                const unsigned long long m = __ballot(keep);
-                if (keep) ku[out + __popcll(m & ((1ull << lane) - 1ull))] = key;
-                out += __popcll(m);
-            }
+            const unsigned long long T = rec_wide_cut_buffer(row_buf(u0 + u), min(cnt[u], cap), cap, topn, hist, lane);
             if (lane == 0) { cnt[u] = topn; thr_l[u] = T; }
         }
         rec_wide_drain();                                          // the compacted keys before the next appends and the next cut

@@ -124,6 +124,36 @@ class _Allow:
         idx_d = None if self.idx is None else torch.from_numpy(self.idx).cuda()
         return lambda b0: (_ptr(bits_d), bits.shape[1], bits.shape[0], None if idx_d is None else _ptr(idx_d[b0:]), None, 0)
 
+    @staticmethod
+    def at(filt):
+        """``filt.upload()``, or for None the filter arguments of a call without a filter."""
+        return filt.upload() if filt is not None else (lambda b0: (None, 0, 0, None, None, 0))
+
+
+def _padded(*shape):
+    """The outputs every top-n call fills: int64 items padded with -1 and float32 scores padded with -inf, of ``shape``."""
+    return np.full(shape, -1, dtype=np.int64), np.full(shape, -np.inf, dtype=np.float32)
+
+
+def _topn_result(out_items, out_scores, one, return_scores):
+    """... and what it returns: the items, with ``return_scores`` (items, scores); ``one``: the argument was an int, the leading
+    axis goes."""
+    if one:
+        out_items, out_scores = out_items[0], out_scores[0]
+    return (out_items, out_scores) if return_scores else out_items
+
+
+def _topn_call(entry, head, n_cat, mid, topn, items_d, scores_d, count_d=None, moving=True):
+    """``call`` of WMF._scan_batches for a top-n entry point of the library: entry(*head, ids, nb, n_cat, the first CSR's window if
+    there is one, *mid(b0), topn, n_slices = 0, out_items, out_scores, out_count, workspace, its bytes, stream).  ``mid(b0)``: what
+    the entry point takes between the seen lists and topn for a batch from b0 on -- the filter's tuple and the call's own.  The
+    outputs are written from row b0 on; ``moving`` False: from row 0 (buffers of one window)."""
+    def call(b0, nb, ids, csrs, *ws):
+        o = b0 if moving else 0
+        return entry(*head, ids, nb, n_cat, *(csrs[0] if csrs else ()), *mid(b0), topn, 0, _ptr(items_d[o:]),
+                     _ptr(scores_d[o:]) if scores_d is not None else None, _ptr(count_d), *ws)
+    return call
+
 
 def _transformed_dtype(count_dtype, alpha, beta, pre_process_count):
     """dtype of the confidence weights the reference ends up with (wmf_model.py:119-123), by NumPy's own rules."""
@@ -376,23 +406,15 @@ class WMF(RecModel):
         beyond) and ``candidates`` (wide True: the wide kernels for every topn).  ``mmr``: the checked (pool, lam, cosine) of
         ``recommend_diverse`` -- the pool of ``candidates`` re-ranked on the device (_diverse_scan); topn is then at most
         RECOMMEND_MAX_TOPN."""
-        n_users_model, n_items = self.users.shape[0], self.items.shape[0]
-        seen = None
-        if exclude is not None:
-            if not scipy.sparse.issparse(exclude) or exclude.shape != (n_users_model, n_items):
-                raise ValueError(f"exclude must be a sparse matrix of shape {(n_users_model, n_items)}, got {getattr(exclude, 'shape', None)}")
-        one = np.ndim(users) == 0
-        u = _wrapped_ids(np.atleast_1d(np.asarray(users)).reshape(-1).astype(np.int64), n_users_model, "user", np.int64)
+        n_items = self.items.shape[0]
+        one, u = self._checked_users(users, exclude)
         topn = int(topn)
         if topn < 1:
             raise ValueError(f"topn must be at least 1, not {topn}")
         filt = None if allow is None and allow_idx is None else _Allow(allow, allow_idx, n_items, len(u), "item")
         _lib.require_gpu()
-        out_items = np.full((len(u), topn), -1, dtype=np.int64)
-        out_scores = np.full((len(u), topn), -np.inf, dtype=np.float32)
-        if exclude is not None and len(u):
-            seen = scipy.sparse.csr_matrix(exclude)[u]            # the requested rows, a copy
-            seen.sort_indices()
+        out_items, out_scores = _padded(len(u), topn)
+        seen = self._seen_rows(exclude, u)
         if len(u) == 0 or (filt is not None and filt.empty):
             pass
         elif topn > CANDIDATES_MAX:
@@ -409,9 +431,25 @@ class WMF(RecModel):
         else:                                                      # (beyond RECOMMEND_MAX_TOPN: the wide kernels, as candidates())
             self._recommend_fused(u, topn, seen, out_items, out_scores if return_scores else None, filt, wide=wide or topn > RECOMMEND_MAX_TOPN,
                                   mmr=mmr)
-        if one:
-            out_items, out_scores = out_items[0], out_scores[0]
-        return (out_items, out_scores) if return_scores else out_items
+        return _topn_result(out_items, out_scores, one, return_scores)
+
+    def _checked_users(self, users, exclude):
+        """The checks ``recommend`` and ``recommend_shelves`` make of ``users`` and ``exclude``, in their order: the ValueError of an
+        ``exclude`` that is no sparse [users of the model, items], then the IndexError of a user outside the model.  Returns
+        (``users`` was an int, the row of every batch position as int64)."""
+        shape = (self.users.shape[0], self.items.shape[0])
+        if exclude is not None and (not scipy.sparse.issparse(exclude) or exclude.shape != shape):
+            raise ValueError(f"exclude must be a sparse matrix of shape {shape}, got {getattr(exclude, 'shape', None)}")
+        return np.ndim(users) == 0, _wrapped_ids(np.atleast_1d(np.asarray(users)).reshape(-1).astype(np.int64), shape[0], "user", np.int64)
+
+    @staticmethod
+    def _seen_rows(exclude, u):
+        """The rows ``u`` of a checked ``exclude``, a copy with sorted indices: the seen lists of the batch (None without either)."""
+        if exclude is None or len(u) == 0:
+            return None
+        seen = scipy.sparse.csr_matrix(exclude)[u]
+        seen.sort_indices()
+        return seen
 
     def candidates(self, users, n=1000, exclude=None, return_scores=False, allow=None, allow_idx=None):
         """The candidate pool of a two-stage recommender, the lists behind Recall@500: the ``n`` best items of the whole catalogue
@@ -444,29 +482,18 @@ class WMF(RecModel):
         scan (12.8 ms) that is 1.7 x at 4 shelves, 3.2 x at 16, 11.8 x at 64.  Use this call for batches from two shelves on; the
         repeated rows of ``recommend`` are faster for a single shelf (10.8 against 14.3 ms) and for a handful of users (16 users x
         16 shelves: 5.0 against 14.1 ms), whose repeated rows fill the device where one 16-row wave per slice does not."""
-        n_users_model, n_items = self.users.shape[0], self.items.shape[0]
+        n_items = self.items.shape[0]
         g32, G, topn = self._shelf_arguments(groups, n_groups, topn, n_items)
-        if exclude is not None:
-            if not scipy.sparse.issparse(exclude) or exclude.shape != (n_users_model, n_items):
-                raise ValueError(f"exclude must be a sparse matrix of shape {(n_users_model, n_items)}, got {getattr(exclude, 'shape', None)}")
-        one = np.ndim(users) == 0
-        u = _wrapped_ids(np.atleast_1d(np.asarray(users)).reshape(-1).astype(np.int64), n_users_model, "user", np.int64)
+        one, u = self._checked_users(users, exclude)
         filt = None if allow is None and allow_idx is None else _Allow(allow, allow_idx, n_items, len(u), "item", as_mask=True)
         _lib.require_gpu()
-        out_items = np.full((len(u), G, topn), -1, dtype=np.int64)
-        out_scores = np.full((len(u), G, topn), -np.inf, dtype=np.float32)
+        out_items, out_scores = _padded(len(u), G, topn)
         if len(u) and not (filt is not None and filt.empty):
-            seen = None
-            if exclude is not None:
-                seen = scipy.sparse.csr_matrix(exclude)[u]            # the requested rows, a copy
-                seen.sort_indices()
             users_t, items_t, f, ld = self._device_factors()
-            out_items[:], scores = self._shelves_scan(users_t, items_t, f, ld, u, groups, g32, G, topn, seen, return_scores, filt)
+            out_items[:], scores = self._shelves_scan(users_t, items_t, f, ld, u, groups, g32, G, topn, self._seen_rows(exclude, u), return_scores, filt)
             if return_scores:
                 out_scores[:] = scores
-        if one:
-            out_items, out_scores = out_items[0], out_scores[0]
-        return (out_items, out_scores) if return_scores else out_items
+        return _topn_result(out_items, out_scores, one, return_scores)
 
     def recommend_capped(self, users, groups, topn=10, per_group=2, exclude=None, return_scores=False, allow=None, allow_idx=None):
         """The ``topn`` best items overall with at most ``per_group`` of any shelf -- the commonest business rule on top of
@@ -489,13 +516,10 @@ class WMF(RecModel):
         items, scores = items.reshape(B, -1), scores.reshape(B, -1)
         last = np.where(items < 0, np.iinfo(np.int64).max, items)     # padding behind every item, whatever its score
         order = np.lexsort((last, -(scores + np.float32(0))), axis=-1)[:, :topn]
-        out_items = np.full((B, topn), -1, dtype=np.int64)
-        out_scores = np.full((B, topn), -np.inf, dtype=np.float32)
+        out_items, out_scores = _padded(B, topn)
         out_items[:, :order.shape[1]] = np.take_along_axis(items, order, axis=1)
         out_scores[:, :order.shape[1]] = np.take_along_axis(scores, order, axis=1)
-        if one:
-            out_items, out_scores = out_items[0], out_scores[0]
-        return (out_items, out_scores) if return_scores else out_items
+        return _topn_result(out_items, out_scores, one, return_scores)
 
     @staticmethod
     def _shelf_arguments(groups, n_groups, topn, n_items):
@@ -537,16 +561,11 @@ class WMF(RecModel):
         scores_d = torch.empty(len(u), G, topn, dtype=torch.float32, device="cuda") if want_scores else None
         head = (_ptr(users_t), _ptr(items_t), f, ld, int(self.bias is True))
         groups_d = self._device_groups(groups, g32)
-        at = filt.upload() if filt is not None else (lambda b0: (None, 0, 0, None))
+        at = _Allow.at(filt)
         need = lambda rows: int(lib.wmf_recommend_grouped_workspace_bytes(rows, G, topn, 0))   # noqa: E731
-        rows = max(1, min(len(u), int(RECOMMEND_BATCH_USERS)))
-        while rows > 1 and need(rows) > CANDIDATES_WS_BYTES:       # (it grows with the rows: halve until a window fits)
-            rows //= 2
-
-        def call(b0, nb, ids, csrs, *ws):
-            return lib.wmf_recommend_topn_grouped(*head, ids, nb, n_items, *csrs[0], *at(b0)[:4], _ptr(groups_d), G, topn, 0,
-                                                  _ptr(items_d[b0:]), _ptr(scores_d[b0:]) if scores_d is not None else None, None, *ws)
-        return self._scan_batches(u, [None if seen is None else (seen.indptr, seen.indices)], need, [items_d, scores_d], call, rows)
+        call = _topn_call(lib.wmf_recommend_topn_grouped, head, n_items, lambda b0: (*at(b0)[:4], _ptr(groups_d), G), topn, items_d, scores_d)
+        return self._scan_batches(u, [None if seen is None else (seen.indptr, seen.indices)], need, [items_d, scores_d], call,
+                                  self._windows(len(u), need))
 
     # ------------------------------------------------------------------ a15: diversified lists
     @staticmethod
@@ -627,8 +646,7 @@ class WMF(RecModel):
             elif pool_count.dtype != torch.int32 or not pool_count.is_cuda:
                 raise ValueError("a device pool_count is int32 on the GPU")
         _lib.require_gpu()
-        out_items = np.full((B, topn), -1, dtype=np.int64)
-        out_scores = np.full((B, topn), -np.inf, dtype=np.float32)
+        out_items, out_scores = _padded(B, topn)
         if B:
             if cosine:
                 _, items_t, f, ld, norms = self._device_inv_norms("items")
@@ -649,9 +667,7 @@ class WMF(RecModel):
             out_items[:] = items_d.cpu().numpy()
             if return_scores:
                 out_scores[:] = scores_d.cpu().numpy()
-        if one:
-            out_items, out_scores = out_items[0], out_scores[0]
-        return (out_items, out_scores) if return_scores else out_items
+        return _topn_result(out_items, out_scores, one, return_scores)
 
     def intra_list_similarity(self, item_lists, metric='cosine'):
         """How alike the items of each list are, the measure a diversified list is judged by: for every row of ``item_lists``
@@ -725,15 +741,14 @@ class WMF(RecModel):
         if out_scores is not None:
             out_scores[:] = scores
 
-    def _wide_rows(self, n, topn):
-        """(need, rows): the workspace of a wmf_recommend_topn_wide call as a function of its rows, and the rows of a window of
-        ``n`` positions whose workspace stays within CANDIDATES_WS_BYTES (one row at least)."""
-        lib = _lib.load()
-        need = lambda rows: int(lib.wmf_recommend_wide_workspace_bytes(rows, topn, 0))   # noqa: E731
+    @staticmethod
+    def _windows(n, need):
+        """The rows of a window of ``n`` positions whose workspace ``need(rows)`` stays within CANDIDATES_WS_BYTES (one row at
+        least): the wide, diversified and shelf scans hand it to _scan_batches."""
         rows = max(1, min(n, int(RECOMMEND_BATCH_USERS)))
         while rows > 1 and need(rows) > CANDIDATES_WS_BYTES:       # (it grows with the rows: halve until a window fits)
             rows //= 2
-        return need, rows
+        return rows
 
     def _diverse_scan(self, users_t, items_t, f, ld, u, topn, seen, want_scores, filt, mmr):
         """``candidates`` re-ranked without leaving the device: per window of _scan_batches, wmf_recommend_topn_wide(topn = pool)
@@ -742,18 +757,19 @@ class WMF(RecModel):
         pool, lam, cosine = mmr
         lib = _lib.load()
         norms = self._device_inv_norms("items")[4] if cosine else None
-        need, rows = self._wide_rows(len(u), pool)
+        need = lambda rows: int(lib.wmf_recommend_wide_workspace_bytes(rows, pool, 0))   # noqa: E731
+        rows = self._windows(len(u), need)
         pool_i = torch.empty(rows, pool, dtype=torch.int32, device="cuda")
         pool_s = torch.empty(rows, pool, dtype=torch.float32, device="cuda")
         pool_c = torch.empty(rows, dtype=torch.int32, device="cuda")
         items_d = torch.empty(len(u), topn, dtype=torch.int32, device="cuda")
         scores_d = torch.empty(len(u), topn, dtype=torch.float32, device="cuda") if want_scores else None
-        head = (_ptr(users_t), _ptr(items_t), f, ld, int(self.bias is True))
         n_items = self.items.shape[0]
-        at = filt.upload() if filt is not None else (lambda b0: (None, 0, 0, None, None, 0))
+        scan = _topn_call(lib.wmf_recommend_topn_wide, (_ptr(users_t), _ptr(items_t), f, ld, int(self.bias is True)), n_items, _Allow.at(filt),
+                          pool, pool_i, pool_s, pool_c, moving=False)
 
         def call(b0, nb, ids, csrs, *ws):
-            rc = lib.wmf_recommend_topn_wide(*head, ids, nb, n_items, *csrs[0], *at(b0), pool, 0, _ptr(pool_i), _ptr(pool_s), _ptr(pool_c), *ws)
+            rc = scan(b0, nb, ids, csrs, *ws)
             if rc != _lib.WMF_OK:
                 return rc
             return lib.wmf_rerank_mmr(_ptr(items_t), n_items, f, ld, int(self.bias is True), _ptr(norms), _ptr(pool_i), _ptr(pool_s), _ptr(pool_c),
@@ -771,27 +787,16 @@ class WMF(RecModel):
         lib = _lib.load()
         items_d = torch.empty(len(u), topn, dtype=torch.int32, device="cuda")
         scores_d = torch.empty(len(u), topn, dtype=torch.float32, device="cuda") if want_scores else None
-        head = (_ptr(users_t), _ptr(items_t), f, ld, int(self.bias is True))
         if wide:
-            at = filt.upload() if filt is not None else (lambda b0: (None, 0, 0, None, None, 0))
-
-            def call(b0, nb, ids, csrs, *ws):
-                return lib.wmf_recommend_topn_wide(*head, ids, nb, self.items.shape[0], *csrs[0], *at(b0), topn, 0, _ptr(items_d[b0:]),
-                                                   _ptr(scores_d[b0:]) if scores_d is not None else None, None, *ws)
-            need, rows = self._wide_rows(len(u), topn)
-            return self._scan_batches(u, [None if seen is None else (seen.indptr, seen.indices)], need, [items_d, scores_d], call, rows)
-        if filt is None:
-            def call(b0, nb, ids, csrs, *ws):
-                return lib.wmf_recommend_topn(*head, ids, nb, self.items.shape[0], *csrs[0], topn, 0, _ptr(items_d[b0:]),
-                                              _ptr(scores_d[b0:]) if scores_d is not None else None, None, *ws)
+            entry, mid, ws_bytes = lib.wmf_recommend_topn_wide, _Allow.at(filt), lib.wmf_recommend_wide_workspace_bytes
+        elif filt is not None:
+            entry, mid, ws_bytes = lib.wmf_recommend_topn_filtered, filt.upload(), lib.wmf_recommend_workspace_bytes
         else:
-            at = filt.upload()
-
-            def call(b0, nb, ids, csrs, *ws):
-                return lib.wmf_recommend_topn_filtered(*head, ids, nb, self.items.shape[0], *csrs[0], *at(b0), topn, 0, _ptr(items_d[b0:]),
-                                                       _ptr(scores_d[b0:]) if scores_d is not None else None, None, *ws)
-        return self._scan_batches(u, [None if seen is None else (seen.indptr, seen.indices)],
-                                  lambda rows: lib.wmf_recommend_workspace_bytes(rows, topn, 0), [items_d, scores_d], call)
+            entry, mid, ws_bytes = lib.wmf_recommend_topn, lambda b0: (), lib.wmf_recommend_workspace_bytes
+        need = lambda rows: int(ws_bytes(rows, topn, 0))   # noqa: E731
+        call = _topn_call(entry, (_ptr(users_t), _ptr(items_t), f, ld, int(self.bias is True)), self.items.shape[0], mid, topn, items_d, scores_d)
+        return self._scan_batches(u, [None if seen is None else (seen.indptr, seen.indices)], need, [items_d, scores_d], call,
+                                  self._windows(len(u), need) if wide else None)
 
     # ------------------------------------------------------------------ a14: similar_items, similar_users
     def similar_items(self, items, topn=10, metric='cosine', exclude_self=True, return_scores=False, allow=None, allow_idx=None):
@@ -828,13 +833,10 @@ class WMF(RecModel):
         q = _wrapped_ids(np.atleast_1d(np.asarray(ids)).reshape(-1).astype(np.int64), n_rows, side[:-1], np.int64)
         filt = None if allow is None and allow_idx is None else _Allow(allow, allow_idx, n_rows, len(q), side[:-1], as_mask=True)
         _lib.require_gpu()
-        out_rows = np.full((len(q), topn), -1, dtype=np.int64)
-        out_scores = np.full((len(q), topn), -np.inf, dtype=np.float32)
+        out_rows, out_scores = _padded(len(q), topn)
         if len(q) and not (filt is not None and filt.empty):
             self._similar_fused(side, q, topn, metric == 'cosine', bool(exclude_self), out_rows, out_scores if return_scores else None, filt)
-        if one:
-            out_rows, out_scores = out_rows[0], out_scores[0]
-        return (out_rows, out_scores) if return_scores else out_rows
+        return _topn_result(out_rows, out_scores, one, return_scores)
 
     def _similar_fused(self, side, q, topn, cosine, exclude_self, out_rows, out_scores, filt=None):
         """wmf_similar_topn in batches (_scan_batches): the rows ``q`` of ``side`` against all of its rows.  ``filt``: an _Allow in
@@ -849,16 +851,13 @@ class WMF(RecModel):
         rows_d = torch.empty(len(q), topn, dtype=torch.int32, device="cuda")
         scores_d = torch.empty(len(q), topn, dtype=torch.float32, device="cuda") if out_scores is not None else None
         head = (_ptr(mat), _ptr(mat), f, ld, int(self.bias is True), _ptr(norms) if cosine else None, _ptr(norms) if cosine else None)
+        own = (int(exclude_self), None, None)                      # (no exclusion lists: _scan_batches gets no CSR)
         if filt is None:
-            def call(b0, nb, ids, csrs, *ws):
-                return lib.wmf_similar_topn(*head, ids, nb, mat.shape[0], int(exclude_self), None, None, topn, 0, _ptr(rows_d[b0:]),
-                                            _ptr(scores_d[b0:]) if scores_d is not None else None, None, *ws)
+            entry, mid = lib.wmf_similar_topn, lambda b0: own
         else:
             at = filt.upload()
-
-            def call(b0, nb, ids, csrs, *ws):
-                return lib.wmf_similar_topn_filtered(*head, ids, nb, mat.shape[0], int(exclude_self), None, None, *at(b0)[:4], topn, 0,
-                                                     _ptr(rows_d[b0:]), _ptr(scores_d[b0:]) if scores_d is not None else None, None, *ws)
+            entry, mid = lib.wmf_similar_topn_filtered, lambda b0: (*own, *at(b0)[:4])
+        call = _topn_call(entry, head, mat.shape[0], mid, topn, rows_d, scores_d)
         out_rows[:], scores = self._scan_batches(q, [], lambda rows: lib.wmf_similar_workspace_bytes(rows, topn, 0), [rows_d, scores_d], call)
         if out_scores is not None:
             out_scores[:] = scores
@@ -1197,8 +1196,7 @@ class WMF(RecModel):
         B = mat.shape[0]
         filt = None if allow is None and allow_idx is None else _Allow(allow, allow_idx, n_items, B, "item", as_mask=True)
         _lib.require_gpu()
-        out_items = np.full((B, G, topn), -1, dtype=np.int64)
-        out_scores = np.full((B, G, topn), -np.inf, dtype=np.float32)
+        out_items, out_scores = _padded(B, G, topn)
         if B and not (filt is not None and filt.empty):
             X_d, items_t, f, ld = self._fold_in_device(mat, alpha, beta, mode)
             seen = None
@@ -1224,8 +1222,7 @@ class WMF(RecModel):
         B = mat.shape[0]
         filt = None if allow is None and allow_idx is None else _Allow(allow, allow_idx, self.items.shape[0], B, "item")
         _lib.require_gpu()
-        out_items = np.full((B, topn), -1, dtype=np.int64)
-        out_scores = np.full((B, topn), -np.inf, dtype=np.float32)
+        out_items, out_scores = _padded(B, topn)
         if B and not (filt is not None and filt.empty):
             X_d, items_t, f, ld = self._fold_in_device(mat, alpha, beta, mode)
             seen = None

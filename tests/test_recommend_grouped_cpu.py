@@ -128,8 +128,14 @@ def test_the_scan_fits_its_lds_at_64_groups_in_every_width_class():
     grouped = open(os.path.join(ROOT, "recmodel_amd", "csrc", "wmf_topn_grouped.h")).read()
     assert "(size_t)nw * 16 * n_groups * 12 + (size_t)nw * 256 * 4" in grouped
     launch = open(os.path.join(ROOT, "recmodel_amd", "csrc", "wmf_recommend.hip")).read()
-    assert launch.count("recommend_scan_grouped_kernel<NIT, TPS, NW, true>), 112 * 1024") == 1
-    assert launch.count("recommend_scan_grouped_kernel<NIT, TPS, NW, false>), 112 * 1024") == 1
+    # the one launch site of the grouped scan: under the 112 KB ceiling, with the LDS of rec_grouped_lds_bytes, and MASK both
+    # false and true -- the forms 0 and 1 of the dispatch it sits in
+    assert launch.count("recommend_scan_grouped_kernel<NIT, TPS, NW, MASK>), 112 * 1024") == 1
+    site = launch[launch.index("int wmf_launch_recommend_grouped("):]
+    site = site[:site.index("recommend_scan_grouped_kernel<NIT, TPS, NW, MASK>), 112 * 1024") + 400]
+    assert site.count("wmf_dispatch_list<0, 1>(rec_form(flt), [&](auto form) {") == 1
+    assert site.count("constexpr bool MASK = decltype(form)::value == 1;") == 1
+    assert site.count("wmf_scan_stage_bytes(TPS, ld) + rec_grouped_lds_bytes(NW, n_groups), st,") == 1
     for tps, ld in gref.WIDTH_CLASSES:
         assert gref.scan_lds_bytes(tps, ld, waves, 64) <= 112 * 1024, (tps, ld)
         assert gref.scan_lds_bytes(tps, ld, waves, 64) - gref.scan_lds_bytes(tps, ld, waves, 63) == 768
