@@ -130,7 +130,16 @@ int wmf_gram_whitened(const float* g, int64_t m, int f, int ld, int bias,
  * (its semantics and rounding), then N_ext [(f + bias), ld] fp32 = [T . W_white | U[:, 0]] (column f: the bias; padding zero).
  * rolled != 0 (wmf_rolled_layout_supported): g came from wmf_solve_rows_ex(WMF_SOLVE_ROLLED) and the whitened side is wanted
  * in rolled coordinates -- row p of N_ext belongs to position p of g, column n to position n of the whitened row.
+ * `rolled` is a set of flags: 0 and 1 (WMF_COMPOSE_ROLLED) are the two values above.  WMF_COMPOSE_REVERSED (2) factorises
+ * P^T (G~ + lambda I) P = L L^T with P = diag(1, J) (bias; J reverses features 1 .. f - 1) or P = J (no bias: all f features)
+ * and returns W_white = P L^-T, W_unwhite = L^-1 P^T = W_white^T: a whitening as valid as L^-T (W_white^T (G~ + lambda I)
+ * W_white = I, whitened feature 0 of a bias model still the constant 1 / L[0][0]), whose matrices are anti-triangular in
+ * feature order.  Where exactly one of two consecutive half steps sets the flag, N_ext[i][j] = 0 for i + j < f (bias: i the
+ * feature at a position of g, j the whitened feature; the row of the one and the bias column are dense; i + j < f - 1 without
+ * biases), so wmf_row_transform_chained skips those tiles.  The solved factors do not depend on the choice but for rounding.
  * U [f, ld] may not alias W_white / W_unwhite. */
+#define WMF_COMPOSE_ROLLED 1
+#define WMF_COMPOSE_REVERSED 2
 int wmf_compose_whitening(const double* G_aug, const float* U, int f, int ld, int bias, int rolled, double lambda,
                           float* W_white, float* W_unwhite, float* N_ext, int32_t* info,
                           void* workspace, void* stream);

@@ -132,6 +132,10 @@ DEBUG_FLAGS = {
 SHIPPED_DEBUG_FLAGS = ("WMF_DBG_HEAVY_REG_RING", "WMF_DBG_F32_GRAM", "WMF_DBG_HEAVY_ONE_WAVE", "WMF_DBG_F64_NO_LOW_RANK",
                        "WMF_DBG_NO_ITER", "WMF_DBG_F64_VALU")
 
+# The flags of wmf_compose_whitening's `rolled` argument (include/wmf_hip.h)
+COMPOSE_ROLLED = 1
+COMPOSE_REVERSED = 2
+
 
 def parse_debug_flags(text):
     """A switch mask from a number ("268435456", "0x1000") or from names joined by `|` ("NO_ITER|WMF_DBG_F64_VALU"): what

@@ -323,7 +323,8 @@ int wmf_compose_whitening(const double* G_aug, const float* U, int f, int ld, in
                           float* W_unwhite, float* N_ext, int32_t* info, void* workspace, void* stream) {
     if (check_chained("wmf_compose_whitening", f, ld, bias)) return WMF_EINVAL;
     if (!G_aug || !U || !W_white || !W_unwhite || !N_ext || !info || !workspace) { wmf_set_error("wmf_compose_whitening: null pointer"); return WMF_EINVAL; }
-    if (rolled && !(bias && wmf_rolled_layout(f, ld))) { wmf_set_error("wmf_compose_whitening: rolled needs wmf_rolled_layout_supported(f=%d, ld=%d) and bias", f, ld); return WMF_EINVAL; }
+    if (rolled & ~(WMF_COMPOSE_ROLLED | WMF_COMPOSE_REVERSED)) { wmf_set_error("wmf_compose_whitening: unknown flag in rolled=%d", rolled); return WMF_EINVAL; }
+    if ((rolled & WMF_COMPOSE_ROLLED) && !(bias && wmf_rolled_layout(f, ld))) { wmf_set_error("wmf_compose_whitening: rolled needs wmf_rolled_layout_supported(f=%d, ld=%d) and bias", f, ld); return WMF_EINVAL; }
     if (U == W_unwhite || U == W_white) { wmf_set_error("wmf_compose_whitening: U may not alias an output"); return WMF_EINVAL; }
     // the two small products live where the Gramian kept its partial tiles (at least 1.8 MB)
     wmf_launch_compose(G_aug, U, f, ld, bias, rolled, lambda, W_white, W_unwhite, N_ext, info, (double*)workspace,

@@ -487,12 +487,19 @@ __global__ __launch_bounds__(64, 1) void factorize64m_kernel(const double* __res
     }
 }
 
+// The feature order P a whitening may be computed in (wmf_compose_whitening, WMF_COMPOSE_REVERSED): 0 the
+// identity, 1 diag(1, J) -- feature 0 stays first (the border feature of a bias model), features 1 .. f - 1 reversed --, 2 J, all
+// f reversed.  Each is its own inverse.
+__host__ __device__ __forceinline__ int wmf_perm(int j, int f, int perm) {
+    return perm == 0 ? j : perm == 1 ? (j == 0 ? 0 : f - j) : f - 1 - j;
+}
+
 // ---- 64 < f <= 272, blocked: the same algorithm with the two images in a global workspace (L2 resident) and the
 // independent tile products of each step dealt to the eight waves of one workgroup.  The columns of L^-1 are
 // independent of each other, so each wave substitutes its own columns without further barriers.
 __global__ __launch_bounds__(512, 1) void factorize_blocked_kernel(const double* __restrict__ G, int f, int ld, double lambda,
                                                                    float* __restrict__ Wwhite, float* __restrict__ Wunwhite,
-                                                                   int32_t* __restrict__ info, double* __restrict__ work) {
+                                                                   int32_t* __restrict__ info, double* __restrict__ work, int perm) {
     __shared__ __attribute__((aligned(16))) double Ts[8][16 * 18];   // one scratch tile per wave
     __shared__ int bad;
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 15, q = lane >> 4;
@@ -547,24 +554,25 @@ __global__ __launch_bounds__(512, 1) void factorize_blocked_kernel(const double*
     __syncthreads();
     const bool ok = bad == 0;
     if (tid == 0 && !ok) *info = bad;          // sticky: only the caller resets it (a later success must not hide a failure)
+    // G was given in the order P (perm != 0): W_unwhite = L^-1 P^T and W_white = P L^-T leave in feature order
     for (int e = tid; e < f * ld; e += 512) {
         const int i = e / ld, j = e % ld;
         float wu = 0.f, ww = 0.f;
-        if (j < f && ok) { wu = (float)X[i * LD + j]; ww = (float)X[j * LD + i]; }
+        if (j < f && ok) { wu = (float)X[i * LD + wmf_perm(j, f, perm)]; ww = (float)X[j * LD + wmf_perm(i, f, perm)]; }
         Wunwhite[e] = wu;
         Wwhite[e] = ww;
     }
 }
 
 int wmf_launch_factorize(const double* G_sum, int f, int ld, double lambda, float* Wwhite, float* Wunwhite,
-                         int32_t* info, double* gA, hipStream_t st) {
-    if (f <= 64) {                                   // blocked single-wave version (fp64 MFMA)
+                         int32_t* info, double* gA, hipStream_t st, int perm) {
+    if (f <= 64) {                                   // blocked single-wave version (fp64 MFMA); perm != 0 comes with f >= 97 only
         WmfProfScope ps("factorize64m_kernel", st);
         hipLaunchKernelGGL(factorize64m_kernel, dim3(1), dim3(64), 0, st, G_sum, f, ld, lambda, Wwhite, Wunwhite, info);
         return 0;
     }
     WmfProfScope ps("factorize_blocked_kernel", st);     // blocked workgroup version (fp64 MFMA)
-    hipLaunchKernelGGL(factorize_blocked_kernel, dim3(1), dim3(512), 0, st, G_sum, f, ld, lambda, Wwhite, Wunwhite, info, gA);
+    hipLaunchKernelGGL(factorize_blocked_kernel, dim3(1), dim3(512), 0, st, G_sum, f, ld, lambda, Wwhite, Wunwhite, info, gA, perm);
     return 0;
 }
 
@@ -1004,13 +1012,15 @@ __global__ __launch_bounds__(256) void compose_h_kernel(const double* __restrict
     if (live && (threadIdx.x & 15) == 0) H[e] = s;
 }
 // G~ = T^T . H, f x f; element (i, j) and (j, i) are the same sum (the factorisation reads one triangle)
+// (perm != 0: the output is P^T G~ P, element (i, j) the sum of (P i, P j))
 __global__ __launch_bounds__(256) void compose_g_kernel(const double* __restrict__ H, const float* __restrict__ U, int f, int ld,
-                                                        int bias, int rolled, double* __restrict__ Gt) {
+                                                        int bias, int rolled, double* __restrict__ Gt, int perm) {
     const int f1 = f + (bias ? 1 : 0);
     const int e0 = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const bool live = e0 < f * f;
     const int e = live ? e0 : 0;
     int i = e / f, j = e - i * f;
+    i = wmf_perm(i, f, perm); j = wmf_perm(j, f, perm);
     if (i > j) { const int t = i; i = j; j = t; }
     const double s = compose_dot16(f1, [&](int p) { return compose_t(U, f, ld, bias, rolled, p, i); }, [&](int p) { return H[p * f + j]; });
     if (live && (threadIdx.x & 15) == 0) Gt[e] = s;
@@ -1030,14 +1040,19 @@ __global__ __launch_bounds__(256) void compose_n_kernel(const float* __restrict_
 }
 
 // scratch: (f + bias) * f + f * f doubles (the Gramian's partial tiles are free by now)
-int wmf_launch_compose(const double* G_aug, const float* U, int f, int ld, int bias, int rolled, double lambda, float* Wwhite,
+// flags: WMF_COMPOSE_ROLLED | WMF_COMPOSE_REVERSED.  Reversed: the Gramian is factorised in the order P = diag(1, J) (bias) or J,
+// and the factorisation's store puts W_white = P L^-T and W_unwhite = L^-1 P^T back in feature order, so compose_n_kernel and every
+// later reader are the same code; only the zeros of N_ext move (anti-triangular: DESIGN.md section 5).
+int wmf_launch_compose(const double* G_aug, const float* U, int f, int ld, int bias, int flags, double lambda, float* Wwhite,
                        float* Wunwhite, float* N_ext, int32_t* info, double* scratch, double* gA, hipStream_t st) {
     const int f1 = f + (bias ? 1 : 0);
+    const int rolled = (flags & WMF_COMPOSE_ROLLED) ? 1 : 0;
+    const int perm = !(flags & WMF_COMPOSE_REVERSED) ? 0 : bias ? 1 : 2;
     double* H = scratch;
     double* Gt = scratch + (size_t)f1 * f;
     WMF_LAUNCH("compose_h_kernel", compose_h_kernel, dim3((f1 * f + 15) / 16), dim3(256), 0, st, G_aug, U, f, ld, bias, rolled, H);
-    WMF_LAUNCH("compose_g_kernel", compose_g_kernel, dim3((f * f + 15) / 16), dim3(256), 0, st, H, U, f, ld, bias, rolled, Gt);
-    wmf_launch_factorize(Gt, f, ld, lambda, Wwhite, Wunwhite, info, gA, st);
+    WMF_LAUNCH("compose_g_kernel", compose_g_kernel, dim3((f * f + 15) / 16), dim3(256), 0, st, H, U, f, ld, bias, rolled, Gt, perm);
+    wmf_launch_factorize(Gt, f, ld, lambda, Wwhite, Wunwhite, info, gA, st, perm);
     WMF_LAUNCH("compose_n_kernel", compose_n_kernel, dim3((f1 * ld + 15) / 16), dim3(256), 0, st, U, Wwhite, f, ld, bias, rolled, N_ext);
     return WMF_L_OK;
 }
@@ -1045,7 +1060,9 @@ int wmf_launch_compose(const double* G_aug, const float* U, int f, int ld, int b
 // out = a . N_ext in the layout wmf_row_transform(set_col0_one = mode) writes (0: plain, 1: bias to col0_out, 2: split layout,
 // 3: split layout in rolled coordinates with the bias bits in the body), a = [g, 1]: transform6_kernel's body with input
 // position f read as 1 and the bias of an output row taken from accumulator column f (the last column of N_ext) instead of
-// the input.  N_ext is dense (a lower- times an upper-triangular matrix): all 5 x 9 tile pairs are issued at f = 129.
+// the input.  Tile pairs of N_ext that are all zero are skipped (nz / cmask, as transform6_kernel): a lower- times an upper-
+// triangular matrix is dense, 45 pairs at f = 129 + bias; with one of the two whitenings reversed (wmf_launch_compose) it is
+// anti-triangular, 33 pairs, and 24 once the short last chunk starts the accumulators instead (short_tail).
 // Bytes per row: one row of g read (4 ld), one packed row (4 (f - 1)) and one pair (8) written.
 template <int NFB, int MODE>
 __global__ __launch_bounds__(512) void chain6_kernel(const float* __restrict__ in, int64_t m, int f, int ld,
@@ -1059,9 +1076,22 @@ __global__ __launch_bounds__(512) void chain6_kernel(const float* __restrict__ i
     static_assert(32 * NKC <= KS, "K does not fit the LDS row");
     __bf16* Wt = reinterpret_cast<__bf16*>(smem_raw);             // [3][NP][KS]
     __shared__ int nz[NKC * NFB];
+    __shared__ float ntail[2][NP];                                // rows KB, KB + 1 of N_ext in f32 (the short last chunk, below)
     const int tid = threadIdx.x;
     constexpr bool bias = MODE != 0;
     const int f1 = f + (bias ? 1 : 0);                            // rows and columns of N_ext
+    // The last K chunk holds f1 - KB live positions.  One or two of them (f1 = 129, 130; 97, 98) are not worth nine tile pairs and
+    // the split of eight values: the accumulators START from those rows of N_ext, a[row][KB] N[KB][col] + a[row][KB + 1] N[KB + 1][col]
+    // in plain f32 (with biases and two positions the second value is the one: N[f][col] + g[row][f - 1] N[f - 1][col]), and the
+    // chunk leaves the matrix pipe.  Nothing here depends on where N_ext has zeros.
+    constexpr int KB = 32 * (NKC - 1);
+    const bool short_tail = __builtin_amdgcn_readfirstlane(f1 - KB <= 2 ? 1 : 0) != 0;
+    for (int e = tid; e < 2 * NP; e += 512) {
+        const int k = KB + e / NP, n = e % NP;
+        const bool in_w = k < f1 && n < f1;
+        const float v = W[in_w ? k * ld + n : 0];
+        ntail[e / NP][n] = in_w ? v : 0.f;
+    }
     for (int e = tid; e < NKC * NFB; e += 512) nz[e] = 0;
     __syncthreads();
     typedef __bf16 stage_bf16x8 __attribute__((ext_vector_type(8)));
@@ -1120,10 +1150,31 @@ __global__ __launch_bounds__(512) void chain6_kernel(const float* __restrict__ i
     const int fcol = f & 15;                                         // accumulator column f (the bias) is column fcol of block NFB - 1
     auto block = [&](int64_t blk, float4 (&xc)[2 * NKC]) {
         f32x4 acc[NFB];
+        if (short_tail) {
+            // positions KB, KB + 1 of row blk 16 + r are in the lanes q = 0 (a solved feature, the one, or nothing: replaced, as
+            // below); output row 4 q + reg takes them from lane 4 q + reg
+            const float4 xt = xc[2 * (NKC - 1)];
+            const float v0 = KB < f ? xt.x : (bias && KB == f) ? 1.f : 0.f;
+            const float v1 = KB + 1 < f ? xt.y : (bias && KB + 1 == f) ? 1.f : 0.f;
+            float a0[4], a1[4];
 #pragma unroll
-        for (int nb = 0; nb < NFB; ++nb) acc[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int reg = 0; reg < 4; ++reg) {
+                a0[reg] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((4 * q + reg) * 4, __builtin_bit_cast(int, v0)));
+                a1[reg] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((4 * q + reg) * 4, __builtin_bit_cast(int, v1)));
+            }
+#pragma unroll
+            for (int nb = 0; nb < NFB; ++nb) {
+                const float n0 = ntail[0][16 * nb + r], n1 = ntail[1][16 * nb + r];
+                acc[nb] = f32x4{__builtin_fmaf(a0[0], n0, a1[0] * n1), __builtin_fmaf(a0[1], n0, a1[1] * n1),
+                                __builtin_fmaf(a0[2], n0, a1[2] * n1), __builtin_fmaf(a0[3], n0, a1[3] * n1)};
+            }
+        } else {
+#pragma unroll
+            for (int nb = 0; nb < NFB; ++nb) acc[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
 #pragma unroll
         for (int c = 0; c < NKC; ++c) {
+            if (c == NKC - 1 && short_tail) break;                // (wave-uniform)
             const int k0 = 32 * c + 8 * q;
             float xe[8] = {xc[2 * c].x, xc[2 * c].y, xc[2 * c].z, xc[2 * c].w, xc[2 * c + 1].x, xc[2 * c + 1].y, xc[2 * c + 1].z, xc[2 * c + 1].w};
             // f >= 16 (NFB - 1) in every launch: only the last chunk can hold positions past the f solved features -- the one,

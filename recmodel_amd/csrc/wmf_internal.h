@@ -68,13 +68,13 @@ int wmf_gram_nwaves(int64_t m, int f);
 int wmf_launch_gram(const float* Y, int64_t m, int f, int ld, int bias, double* G_sum, float* partial, double* slices,
                     hipStream_t st);
 int wmf_launch_factorize(const double* G_sum, int f, int ld, double lambda, float* Wwhite, float* Wunwhite,
-                         int32_t* info, double* gA, hipStream_t st);
+                         int32_t* info, double* gA, hipStream_t st, int perm = 0);   // perm: wmf_dense.hip, wmf_perm
 int wmf_launch_transform(const float* in, int64_t m, int f, int ld, const float* W, int set_col0_one, float* out,
                          float* col0_out, hipStream_t st);
 // the chained whitening of a solved side (wmf_dense.hip, "chained")
 int wmf_launch_gram_aug(const float* g, int64_t m, int f, int ld, int bias, double* G_aug, float* partial, double* slices,
                         hipStream_t st);
-int wmf_launch_compose(const double* G_aug, const float* U, int f, int ld, int bias, int rolled, double lambda, float* Wwhite,
+int wmf_launch_compose(const double* G_aug, const float* U, int f, int ld, int bias, int flags, double lambda, float* Wwhite,
                        float* Wunwhite, float* N_ext, int32_t* info, double* scratch, double* gA, hipStream_t st);
 int wmf_launch_transform_chained(const float* g, int64_t m, int f, int ld, int bias, const float* N_ext, int rolled, float* out,
                                  float* col0_out, hipStream_t st);

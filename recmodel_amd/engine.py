@@ -964,7 +964,11 @@ class AlsEngine:
         on g_valid alone, never on whether the factors happen to have been written: the same bits either way)."""
         K, n = self.K, self.n_local[fixed]
         K.gram_whitened(self.g[fixed], n, self.f, self.ld, self.bias, self.G_aug, self.ws)
-        K.compose_whitening(self.G_aug, self.U[fixed], self.f, self.ld, self.bias, self.rolled, self.gamma, self.W_white,
+        # The users' whitening is computed in reversed feature order and the items' is not: N_ext of either side, a product of
+        # one of each, is then anti-triangular instead of dense and the chained pass skips its empty tiles (DESIGN.md section
+        # 5).  W_white / W_unwhite arrive in feature order either way, so nothing that reads U[side] can tell.
+        flags = (_lib.COMPOSE_ROLLED if self.rolled else 0) | (_lib.COMPOSE_REVERSED if fixed == "users" else 0)
+        K.compose_whitening(self.G_aug, self.U[fixed], self.f, self.ld, self.bias, flags, self.gamma, self.W_white,
                             self.W_unwhite, self.N_ext, self.info, self.ws)
         K.row_transform_chained(self.g[fixed], n, self.f, self.ld, self.bias, self.N_ext, self.rolled, self.V[fixed],
                                 self.bias_vec[fixed] if self.bias else None)

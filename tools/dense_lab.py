@@ -2,7 +2,8 @@
 block.  Usage: python tools/dense_lab.py m k bias reps [flags,...]
 (flags: numbers or names, e.g. 0,F32_GRAM; recmodel_amd/_lib.py DEBUG_FLAGS)
 A library with the chained whitening (wmf_chained_supported) is also timed on it: the Gramian of g and the chained pass with a
-dense N_ext, next to the Gramian, the whitening and the un-whitening they replace."""
+dense and with an anti-triangular N_ext, next to the Gramian, the whitening and the un-whitening they replace.  WMF_HIP_LIB
+names the library (recmodel_amd/_lib.py): two runs, one per library, are an A/B."""
 import sys
 import torch
 sys.path.insert(0, '.')
@@ -61,6 +62,21 @@ if hasattr(K, "chained_supported") and K.chained_supported(f, ld, bias):
     Gaug = torch.zeros(f1 * f1, dtype=torch.float64, device=dev)
     N = torch.zeros(f1, ld, device=dev)
     N[:, :f1] = torch.randn(f1, f1, device=dev) * 0.05          # dense: a lower- times an upper-triangular matrix
+    # ... and anti-triangular, as the engine's is with the users' whitening reversed: zero for i + j < f in
+    # feature indices (f - 1 without biases), here in the kernel's positions
+    pos = torch.cat([(torch.arange(f) + 1) % f, torch.arange(f, f1)]) if rolled else torch.arange(f1)
+    N_dense, N_anti = N.clone(), N.clone()
+    N_anti[:, :f1][(pos[:, None] + pos[None, :] < (f if bias else f - 1)).to(dev)] = 0
+    nfb = (f1 + 15) // 16
+    nkc = (16 * nfb + 31) // 32
+
+    def live_pairs(M):
+        """(32-wide K chunk, 16-wide output block) tiles of N_ext that are not all zero, and how many of them lie in a last
+        chunk of one or two live positions (a library that starts the accumulators from that chunk issues none of those)."""
+        P = torch.zeros(32 * nkc, 16 * nfb, device=dev)
+        P[:f1, :f1] = M[:, :f1]
+        live = (P.reshape(nkc, 32, nfb, 16) != 0).any(3).any(1)
+        return int(live.sum()), int(live[-1].sum()) if f1 - 32 * (nkc - 1) <= 2 else 0
     Wl = torch.tril(torch.randn(f, ld, device=dev) * 0.05)
     Wl[:, f:] = 0
 
@@ -73,7 +89,12 @@ if hasattr(K, "chained_supported") and K.chained_supported(f, ld, bias):
         K.gram(out2, m, f, ld, bias, G, ws)
         K.row_transform(out2, m, f, ld, W, (3 if rolled else bias), V, pairs if bias else None)
 
-    for name, trip in (("eager", eager_trip), ("chained", chained_trip)):
+    # (the two shapes of N_ext alternate, twice: the order is not what is measured)
+    for name, trip, M in (("eager", eager_trip, None),) + (("chained, dense N_ext", chained_trip, N_dense),
+                                                          ("chained, anti-triangular N_ext", chained_trip, N_anti)) * 2:
+        if M is not None:
+            N.copy_(M)
+            name += " (live tile pairs %d, %d of them in a short last chunk)" % live_pairs(M)
         trip()
         torch.cuda.synchronize()
         lib.wmf_profile_enable(1)
@@ -82,6 +103,6 @@ if hasattr(K, "chained_supported") and K.chained_supported(f, ld, bias):
         torch.cuda.synchronize()
         lib.wmf_profile_enable(0)
         tab = _lib.profile_table(lib)
-        print(f"{name} (rolled={int(rolled)}): " + ", ".join(f"{nm}={ms / max(n, 1):.3f}ms x{n // reps}" for nm, _, ms, n, _, _ in tab)
+        print(f"{name} (rolled={int(rolled)}): " + ", ".join(f"{nm}={ms / max(n, 1):.3f}ms [{lo:.3f} .. {hi:.3f}] x{n // reps}" for nm, _, ms, n, lo, hi in tab)
               + f"; sum per trip {sum(ms for _, _, ms, _, _, _ in tab) / reps:.3f} ms")
         lib.wmf_profile_reset()
