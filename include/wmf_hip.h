@@ -441,6 +441,74 @@ int wmf_recommend_topn_wide(const float* users, const float* items, int f, int l
                             int32_t* out_items, float* out_scores, int32_t* out_count,
                             void* workspace, int64_t workspace_bytes, void* stream);
 
+/* SAMPLED top-n: n items per row drawn WITHOUT replacement from softmax(score / temperature) over the row's eligible items -- a
+ * Plackett-Luce draw -- in one scan of the catalogue, for exploration slates, hard negatives in proportion to the model's own
+ * softmax, and the propensities of off-policy evaluation (wmf_log_partition).  The Gumbel-top-n identity: the n largest of
+ * z_i = score_i + temperature * g_i, g_i i.i.d. standard Gumbel, are such a draw, in draw order.
+ * The noise is a pure function of (seed, stream, item) -- no generator with state -- so a row's list does not depend on its batch
+ *   position, the other rows, the slice count, the grid or the form of the filter:
+ *     mix(z):  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31      (uint64, wrapping)
+ *     a = mix(seed + 0x9E3779B97F4A7C15 * (stream + 1))             once per row
+ *     h = mix(a    + 0x9E3779B97F4A7C15 * (item   + 1))             item zero-extended from its 32-bit id
+ *     k = h >> 41                                                   23 bits
+ *     u = (2 k + 1) * 2^-24                                         exact in float32, in [2^-24, 1 - 2^-24]
+ *     g = -logf(-logf(u))                                           the accurate logf
+ *   stream: row_stream[b], a uint64 per batch position on the device; row_stream == NULL: stream = b.
+ * The tail is cut off: g lies in [-2.8116, 16.6356] and is never above WMF_SAMPLE_G_MAX, the float32 value of g at k = 2^23 - 1;
+ *   relative probabilities below about e^-16 are not resolved (an item 17 / temperature below the row's best is never drawn first).
+ * Contract: that of wmf_recommend_topn_wide in every respect except the order -- the arguments, the three filter forms, 1 <= n <=
+ *   WMF_RECOMMEND_WIDE_MAX_TOPN, the -1 / -inf padding, out_count, the slice rules and the workspace formula
+ *   (wmf_sample_workspace_bytes = wmf_recommend_wide_workspace_bytes); the call only enqueues, and every refusal (WMF_EINVAL) comes
+ *   before any HIP call and leaves the outputs untouched.
+ * Order: by z = fmaf(temperature, g, score), largest first; equal z goes to the lower id, -0.0 equals +0.0.  In the list form the
+ *   noise is keyed by the item's id, not by its place in the list.
+ * Outputs: out_items; out_scores (may be NULL): the MODEL's score of each pick, the bits wmf_recommend_topn_wide returns for that
+ *   item; out_keys (may be NULL): z; out_count (may be NULL).
+ * temperature: finite and >= 0 (WMF_EINVAL otherwise).  temperature == 0: z = score, and the result is wmf_recommend_topn_wide's bit
+ *   for bit, from these kernels, for any seed.
+ * wmf_sample_noise: g (out_g, may be NULL) and k (out_k, may be NULL) of n_pairs arbitrary (row_stream[i], items[i]) pairs from the
+ *   scan's own device function (row_stream == NULL: stream = i): what the exact tests stand on.  WMF_EINVAL for n_pairs < 0, a null
+ *   items or both outputs null.
+ * Measured (MI355X, 1 000 000 items, k = 128 + biases, 10 seen items per row; profiles/r25_sample.json): 2048 rows at n = 10 / 100 /
+ *   1000 in 15.0 / 19.3 / 36.7 ms at temperature 1 and 13.1 / 17.9 / 36.8 ms at temperature 0, where wmf_recommend_topn_wide takes
+ *   12.2 / 16.2 / 34.0 ms: 1.08 to 1.24 x, with the WMF_SAMPLE_G_MAX skip in; wmf_log_partition of 2048 rows 19.1 ms. */
+#define WMF_SAMPLE_G_MAX 0x1.0a2b24p+4f
+int64_t wmf_sample_workspace_bytes(int64_t n_rows, int64_t n, int32_t n_slices);
+int wmf_sample_topn(const float* users, const float* items, int f, int ld, int bias,
+                    const int32_t* user_idx, int64_t n_rows, int64_t n_items,
+                    const int64_t* seen_indptr, const int32_t* seen_indices,
+                    const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks, const int32_t* allow_idx,
+                    const int32_t* cand_idx, int64_t n_cand,
+                    int64_t n, int32_t n_slices, float temperature, uint64_t seed, const uint64_t* row_stream,
+                    int32_t* out_items, float* out_scores, float* out_keys, int32_t* out_count,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+int wmf_sample_noise(uint64_t seed, const uint64_t* row_stream, const int32_t* items, int64_t n_pairs,
+                     float* out_g, uint32_t* out_k, void* stream);
+
+/* log Z[b] = log sum exp(score / temperature) over the items row b may see: with it, score / temperature - log Z is the log of the
+ * probability with which wmf_sample_topn draws an item FIRST under the same filter.  The rows, the three filter forms and the
+ * slice arguments of wmf_recommend_topn_wide; temperature finite and > 0.  out_logz: float32 per row; out_eligible (may be NULL):
+ * the number of eligible items, exactly.  A row with nothing eligible gets -inf and 0.
+ * Kernels: one scan with a log-sum-exp epilogue -- a running (max, sum) per lane, the max in float32, a term expf((s - max) /
+ *   temperature) in float32, the sum in float64, a lane's partial per (row, slice) in the workspace -- and a merge that combines a
+ *   row's partials in a fixed order in float64 and rounds once.  No floating-point atomics: two runs at one slice count are
+ *   bit-identical; other slice counts agree within the error below.
+ * Error: against the float64 log-sum-exp of float64 scores, |L - L64| <= B / temperature + 4 * 2^-23 * (2 + ln n_eligible) + 2^-23 *
+ *   |L64|, B the float32 score's own error bound: a term's relative error is 2^-23 (1 + |x|), x = (s - max) / temperature, the
+ *   softmax mean of |x| is at most ln n_eligible, and the factor 4 covers the rescales of the running max.
+ * Workspace: wmf_log_partition_workspace_bytes(n_rows, n_slices) = WMF_RECOMMEND_WIDE_WS_BASE + L * 16 *
+ *   WMF_LOG_PARTITION_WS_PER_LANE, L the lists of wmf_recommend_wide_workspace_bytes; the automatic slices are those of
+ *   wmf_recommend_topn_wide at topn 1.  WMF_EINVAL, before any HIP call and with the outputs untouched, as wmf_recommend_topn_wide. */
+#define WMF_LOG_PARTITION_WS_PER_LANE 16
+int64_t wmf_log_partition_workspace_bytes(int64_t n_rows, int32_t n_slices);
+int wmf_log_partition(const float* users, const float* items, int f, int ld, int bias,
+                      const int32_t* user_idx, int64_t n_rows, int64_t n_items,
+                      const int64_t* seen_indptr, const int32_t* seen_indices,
+                      const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks, const int32_t* allow_idx,
+                      const int32_t* cand_idx, int64_t n_cand,
+                      float temperature, int32_t n_slices, float* out_logz, int32_t* out_eligible,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
 /* One list per (row, GROUP) from ONE scan of the catalogue: the topn best items of each of n_groups shelves (genres, departments,
  * carousels) for every row of a batch.  group_of is int32[n_items] on the device: item j is on shelf group_of[j]; any value outside
  * [0, n_groups) -- -1, for instance -- means "on no shelf", and the item is never returned (the test is unsigned: every index

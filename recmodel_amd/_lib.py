@@ -68,6 +68,13 @@ SIGNATURES = {
     "wmf_recommend_wide_workspace_bytes": (c_i64, [c_i64, c_i64, c_int]),
     "wmf_recommend_topn_wide": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_int, c_vp,
                                         c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "wmf_sample_workspace_bytes": (c_i64, [c_i64, c_i64, c_int]),
+    "wmf_sample_topn": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_int, c_vp,
+                                c_vp, c_i64, c_i64, c_int, ctypes.c_float, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "wmf_sample_noise": (c_int, [ctypes.c_uint64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "wmf_log_partition_workspace_bytes": (c_i64, [c_i64, c_int]),
+    "wmf_log_partition": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_int, c_vp,
+                                  c_vp, c_i64, ctypes.c_float, c_int, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "wmf_recommend_grouped_workspace_bytes": (c_i64, [c_i64, c_int, c_i64, c_int]),
     "wmf_recommend_topn_grouped": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_int, c_vp,
                                            c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),

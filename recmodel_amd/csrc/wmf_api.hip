@@ -789,6 +789,48 @@ int wmf_recommend_topn_wide(const float* users, const float* items, int f, int l
                           out_items, out_scores, out_count, workspace, workspace_bytes, stream);
 }
 
+int64_t wmf_sample_workspace_bytes(int64_t n_rows, int64_t n, int32_t n_slices) { return wmf_recommend_wide_ws_bytes(n_rows, n, n_slices); }
+
+int wmf_sample_topn(const float* users, const float* items, int f, int ld, int bias, const int32_t* user_idx, int64_t n_rows, int64_t n_items,
+                    const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks,
+                    const int32_t* allow_idx, const int32_t* cand_idx, int64_t n_cand, int64_t n, int32_t n_slices, float temperature,
+                    uint64_t seed, const uint64_t* row_stream, int32_t* out_items, float* out_scores, float* out_keys, int32_t* out_count,
+                    void* workspace, int64_t workspace_bytes, void* stream) {
+    const WmfRowFilter flt{seen_indptr, seen_indices, allow_bits, allow_words, allow_idx, nullptr, cand_idx};
+    const char* after = (temperature >= 0.f && temperature <= 3.4028234663852886e38f) ? nullptr : "need a finite temperature >= 0";
+    const TopnCall c{.what = "wmf_sample_topn", .f = f, .ld = ld, .rows_mat = users, .cat_mat = items, .row_idx = user_idx, .out = out_items,
+                     .workspace = workspace, .rows_name = "n_rows", .n_rows = n_rows, .cat_name = "n_items", .n_cat = n_items, .topn = n,
+                     .n_slices = n_slices, .workspace_bytes = workspace_bytes, .max_topn = WMF_RECOMMEND_WIDE_MAX_TOPN, .flt = flt, .n_masks = n_masks,
+                     .n_cand = n_cand, .after = after};
+    return topn_call(c, [&] { return wmf_recommend_wide_ws_bytes(n_rows, n, n_slices); },
+                     [&] { return wmf_launch_sample(users, items, ld, bias, user_idx, n_rows, n_items, flt, n_cand, n, n_slices, temperature, seed,
+                                                    row_stream, out_items, out_scores, out_keys, out_count, workspace, (hipStream_t)stream); });
+}
+
+int wmf_sample_noise(uint64_t seed, const uint64_t* row_stream, const int32_t* items, int64_t n_pairs, float* out_g, uint32_t* out_k, void* stream) {
+    if (n_pairs < 0 || !items || (!out_g && !out_k)) { wmf_set_error("wmf_sample_noise: negative n_pairs, null items or no output"); return WMF_EINVAL; }
+    if (n_pairs == 0) return WMF_OK;
+    wmf_launch_sample_noise(seed, row_stream, items, n_pairs, out_g, out_k, (hipStream_t)stream);
+    return check_launch("wmf_sample_noise");
+}
+
+int64_t wmf_log_partition_workspace_bytes(int64_t n_rows, int32_t n_slices) { return wmf_log_partition_ws_bytes(n_rows, n_slices); }
+
+int wmf_log_partition(const float* users, const float* items, int f, int ld, int bias, const int32_t* user_idx, int64_t n_rows, int64_t n_items,
+                      const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks,
+                      const int32_t* allow_idx, const int32_t* cand_idx, int64_t n_cand, float temperature, int32_t n_slices, float* out_logz,
+                      int32_t* out_eligible, void* workspace, int64_t workspace_bytes, void* stream) {
+    int rc = check_shape(f, ld);
+    if (rc) return rc;
+    const WmfRowFilter flt{seen_indptr, seen_indices, allow_bits, allow_words, allow_idx, nullptr, cand_idx};
+    const char* own = filter_refusal(flt, n_masks, n_items, n_cand);
+    if (!own && !(temperature > 0.f && temperature <= 3.4028234663852886e38f)) own = "need a finite temperature > 0";
+    if ((rc = check_scan_call("wmf_log_partition", users, items, user_idx, out_logz, workspace, "null pointer", own, "n_rows", n_rows, "n_items",
+                              n_items, nullptr, n_slices, workspace_bytes, [&] { return wmf_log_partition_ws_bytes(n_rows, n_slices); }))) return rc;
+    return launch_error(wmf_launch_log_partition(users, items, ld, bias, user_idx, n_rows, n_items, flt, n_cand, temperature, n_slices, out_logz,
+                                                 out_eligible, workspace, (hipStream_t)stream), "wmf_log_partition", f, ld, "");
+}
+
 int wmf_recommend_topn_grouped(const float* users, const float* items, int f, int ld, int bias, const int32_t* user_idx, int64_t n_users,
                                int64_t n_items, const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* allow_bits,
                                int64_t allow_words, int32_t n_masks, const int32_t* allow_idx, const int32_t* group_of, int32_t n_groups,

@@ -31,6 +31,16 @@ struct WmfRowFilter {
 #define WMF_FILTER_FROM_PARAMS WmfRowFilter{seen_indptr, seen_indices, allow_bits, allow_words, allow_idx, self_idx, cand_idx}
 #define WMF_FILTER_ARGS(F) (F).seen_indptr, (F).seen_indices, (F).allow_bits, (F).allow_words, (F).allow_idx, (F).self_idx, (F).cand_idx
 
+// The forms of a call's filter, a template argument of every top-n scan (wmf_recommend.hip, wmf_sample.hip) and the suffix of its
+// profile name.  0, none: the whole catalogue, the seen lists only.  1, the mask form: the whole catalogue, an item inserted only where
+// the row's allow mask has its bit (the epilogue's MASK).  2, the list form: the positions of cand_idx (n_items of them) instead of the
+// catalogue (the scan's GATHER, two stages of 16 TPS ids past the epilogue's LDS), keys and seen lookups by the real id.  All score
+// in one arithmetic: a score does not depend on the item's place in a tile, so forms 1 and 2 give the bits of form 0 with the
+// ineligible items appended to every seen row.  The entry points refuse a call with both a mask and a list.
+static inline int rec_form(const WmfRowFilter& flt) { return flt.cand_idx ? 2 : flt.allow_bits ? 1 : 0; }
+static const char* const REC_FORM_NAME[3] = {"", "mask_", "list_"};
+static constexpr size_t rec_form_lds(int tps, int form) { return form == 2 ? (size_t)2 * tps * 16 * 4 : 0; }
+
 // A lane's part of the filter: rows u0 + 4 q + reg, reg < 4, of a batch of n_rows.  Fixed-size arrays under compile-time indices
 // (reg comes from an unrolled loop), so they stay in registers; self[] is dead without SELF and words[] without MASK.
 template <bool SELF, bool MASK>

@@ -251,6 +251,7 @@ int wmf_recommend_slices(int64_t n_users, int64_t n_items, int64_t topn, int32_t
 // (... for 1 <= topn <= WMF_RECOMMEND_WIDE_MAX_TOPN: the keys of a row and slice in the workspace; any of the three forms)
 int64_t wmf_recommend_wide_ws_bytes(int64_t n_users, int64_t topn, int32_t n_slices);
 int wmf_recommend_wide_slices(int64_t n_users, int64_t n_scan, int64_t topn, int32_t n_slices);
+int64_t wmf_recommend_wide_lists(int64_t n_users, int32_t n_slices);     // L of the workspace formula (n_slices = 0: the automatic L0)
 int wmf_launch_recommend_wide(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
                               int64_t n_items, const WmfRowFilter& flt, int64_t n_cand, int64_t topn, int32_t n_slices, int32_t* out_items,
                               float* out_scores, int32_t* out_count, void* ws, hipStream_t st);
@@ -260,6 +261,18 @@ int wmf_recommend_grouped_slices(int64_t n_users, int64_t n_items, int32_t n_gro
 int wmf_launch_recommend_grouped(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users,
                                  int64_t n_items, const WmfRowFilter& flt, const int32_t* group_of, int32_t n_groups, int64_t topn,
                                  int32_t n_slices, int32_t* out_items, float* out_scores, int32_t* out_count, void* ws, hipStream_t st);
+// wmf_sample.hip: the sampled top-n (the wide scan with Gumbel-perturbed keys; workspace and slices: wmf_recommend_topn_wide's), the
+// log-partition of a row's eligible catalogue, and the noise of arbitrary (stream, item) pairs
+int wmf_launch_sample(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_users, int64_t n_items,
+                      const WmfRowFilter& flt, int64_t n_cand, int64_t topn, int32_t n_slices, float temperature, uint64_t seed,
+                      const uint64_t* row_stream, int32_t* out_items, float* out_scores, float* out_keys, int32_t* out_count, void* ws,
+                      hipStream_t st);
+int64_t wmf_log_partition_ws_bytes(int64_t n_rows, int32_t n_slices);
+int wmf_launch_log_partition(const float* users, const float* items, int ld, int bias, const int32_t* user_idx, int64_t n_rows, int64_t n_items,
+                             const WmfRowFilter& flt, int64_t n_cand, float temperature, int32_t n_slices, float* out_logz,
+                             int32_t* out_eligible, void* ws, hipStream_t st);
+void wmf_launch_sample_noise(uint64_t seed, const uint64_t* row_stream, const int32_t* items, int64_t n_pairs, float* out_g, uint32_t* out_k,
+                             hipStream_t st);
 // wmf_similar.hip: inverse row norms, and the neighbours of rows of one factor matrix among the rows of another (dot or cosine)
 void wmf_launch_row_inv_norms(const float* M, int64_t n, int f, int ld, int bias, float* out, hipStream_t st);
 int wmf_launch_similar(const float* queries, const float* catalogue, int ld, int bias, const float* q_inv_norm, const float* c_inv_norm,

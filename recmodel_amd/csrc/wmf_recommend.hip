@@ -23,7 +23,7 @@
 //
 // What the three scans share exists once.  Which items may enter a list -- the row's own id, its allow mask, its seen list, tested in
 // that order after the threshold -- is WmfRowFilter / WmfRowEligible (wmf_filter.h), which also says how the filter crosses a launch; the form of a
-// call's filter (none, mask, list) is a template argument of each scan and the suffix of its profile name (rec_form below).  The
+// call's filter (none, mask, list) is a template argument of each scan and the suffix of its profile name (rec_form, wmf_filter.h).  The
 // in-place cut of a workspace buffer and its overwrite argument are rec_wide_cut_buffer (wmf_topn_wide.h).  A key is decoded into the
 // outputs by rec_write_slot.  Each family has one launch site, its instantiation chosen by wmf_dispatch_scan x wmf_dispatch_list; the
 // wide and the grouped launcher share the workspace split and the selection (rec_wide_scan_select).
@@ -38,15 +38,7 @@
 #define WMF_REC_MERGE_GRID 1024      /* workgroups of the merge, four users each */
 #define WMF_REC_SLICE_TILES 64       /* an automatic slice holds at least this many 16-item tiles */
 
-// The forms of a call's filter (WmfRowFilter, wmf_filter.h), a template argument of every scan below and the suffix of its profile
-// name.  0, none: the whole catalogue, the seen lists only.  1, the mask form: the whole catalogue, an item inserted only where the
-// row's allow mask has its bit (the epilogue's MASK).  2, the list form: the positions of cand_idx (n_items of them) instead of the
-// catalogue (the scan's GATHER, two stages of 16 TPS ids past the epilogue's LDS), keys and seen lookups by the real id.  All score
-// in one arithmetic: a score does not depend on the item's place in a tile, so forms 1 and 2 give the bits of form 0 with the
-// ineligible items appended to every seen row.  The entry points refuse a call with both a mask and a list.
-static inline int rec_form(const WmfRowFilter& flt) { return flt.cand_idx ? 2 : flt.allow_bits ? 1 : 0; }
-static const char* const REC_FORM_NAME[3] = {"", "mask_", "list_"};
-static constexpr size_t rec_form_lds(int tps, int form) { return form == 2 ? (size_t)2 * tps * 16 * 4 : 0; }
+// (the forms of a call's filter -- rec_form, REC_FORM_NAME, rec_form_lds -- are wmf_filter.h's)
 
 // NIT, TPS: the scan's width class; NW: waves of a workgroup (the key buffers of 16 NW users share the LDS with the stages)
 template <int NIT, int TPS, int NW, int FORM>
@@ -60,12 +52,6 @@ __global__ __launch_bounds__(64 * NW) void recommend_scan_kernel(const float* __
     wmf_catalogue_scan<NIT, TPS, NW, decltype(p), WmfModelScore, FORM == 2>(
         users, items, ld, bias, user_idx, n_users, n_items, n_slices, tiles_per_slice, n_work, p, WmfModelScore(), cand_idx,
         reinterpret_cast<int32_t*>(wmf_scan_smem + wmf_scan_stage_bytes(TPS, ld) + rec_lds_bytes(NW, cap)));
-}
-
-// slot `at` of the outputs: the item and the score of `key`, or the padding for 0 (no key of an item is 0: its low word is ~id)
-__device__ __forceinline__ void rec_write_slot(int32_t* __restrict__ out_items, float* __restrict__ out_scores, int64_t at, unsigned long long key) {
-    out_items[at] = key ? (int32_t)(~(uint32_t)(key & 0xFFFFFFFFull)) : -1;
-    if (out_scores) out_scores[at] = key ? wmf_key_float((uint32_t)(key >> 32)) : -__builtin_inff();
 }
 
 // keys of `list` (topn of them, descending, 0 = none) above `key`
@@ -119,56 +105,18 @@ __global__ __launch_bounds__(64 * NW) void recommend_scan_wide_kernel(const floa
         reinterpret_cast<int32_t*>(wmf_scan_smem + wmf_scan_stage_bytes(TPS, ld) + rec_wide_lds_bytes(NW)));
 }
 
-// One workgroup per batch position: the topn best keys of all the row's slices (the exact select of wmf_topn_wide.h over the
-// buffers as the scan left them), sorted best first in LDS (bitonic, the keys are distinct: one result), then items, scores, count
-// and padding.
+// One workgroup per batch position: the topn best keys of all the row's slices, sorted best first in LDS (rec_wide_select_row,
+// wmf_topn_wide.h), then items, scores, count and padding.
 __global__ __launch_bounds__(256) void recommend_select_wide_kernel(const unsigned long long* __restrict__ keys, const int32_t* __restrict__ counts,
                                                                     int64_t n_users, int n_slices, int topn, int cap,
                                                                     int32_t* __restrict__ out_items, float* __restrict__ out_scores,
                                                                     int32_t* __restrict__ out_count) {
     __shared__ unsigned long long sel[WMF_RECOMMEND_WIDE_MAX_TOPN];
     __shared__ unsigned hist[256];
-    __shared__ int total_s, fill_s;
+    __shared__ int counters[2];
     const int t = threadIdx.x;
     for (int64_t b = blockIdx.x; b < n_users; b += gridDim.x) {
-        const unsigned long long* K = keys + (size_t)b * n_slices * cap;
-        const int32_t* C = counts + b * n_slices;
-        if (t == 0) { total_s = 0; fill_s = 0; }
-        __syncthreads();
-        int mine = 0;
-        for (int s = t; s < n_slices; s += 256) mine += min(C[s], cap);
-        if (mine) atomicAdd(&total_s, mine);
-        __syncthreads();
-        const int m = total_s, count = min(m, topn);               // (uniform: the select below holds barriers)
-        unsigned long long T = 1ull;                               // every key of an item is above 0
-        if (m > topn) T = rec_wide_kth<256>(K, C, n_slices, cap, 0, cap, topn, hist, t);
-        int P = 1;
-        while (P < count) P <<= 1;
-        for (int i = t; i < P; i += 256) sel[i] = 0ull;
-        __syncthreads();
-        for (int s = 0; s < n_slices; ++s) {
-            const int c = min(C[s], cap);
-            for (int e = t; e < c; e += 256) {
-                const unsigned long long key = K[(size_t)s * cap + e];
-                if (key >= T) {
-                    const int slot = atomicAdd(&fill_s, 1);        // exactly `count` keys are at or above T
-                    if (slot < topn) sel[slot] = key;
-                }
-            }
-        }
-        __syncthreads();
-        for (int k = 2; k <= P; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int i = t; i < P; i += 256) {
-                    const int o = i ^ j;
-                    if (o > i) {
-                        const unsigned long long x = sel[i], y = sel[o];
-                        if ((i & k) == 0 ? x < y : x > y) { sel[i] = y; sel[o] = x; }
-                    }
-                }
-                __syncthreads();
-            }
-        }
+        const int count = rec_wide_select_row(keys + (size_t)b * n_slices * cap, counts + b * n_slices, n_slices, topn, cap, sel, hist, counters, t);
         for (int k = t; k < topn; k += 256) rec_write_slot(out_items, out_scores, b * topn + k, k < count ? sel[k] : 0ull);
         if (t == 0 && out_count) out_count[b] = count;
         __syncthreads();                                           // sel and the counters are read before the next row resets them
@@ -250,6 +198,8 @@ static int64_t rec_wide_auto_lists(int64_t n_users) {
     const int64_t want = n_users > WMF_RECOMMEND_WIDE_AUTO_LISTS ? n_users : WMF_RECOMMEND_WIDE_AUTO_LISTS;
     return most < want ? most : want;
 }
+// (the lists of a call's workspace, for the scans of wmf_sample.hip that cut their slices alike)
+int64_t wmf_recommend_wide_lists(int64_t n_users, int32_t n_slices) { return n_slices == 0 ? rec_wide_auto_lists(n_users) : n_users * n_slices; }
 // ... and the slice count that fits them
 static int64_t rec_wide_auto_bound(int64_t n_users) { return rec_wide_auto_lists(n_users) / n_users; }
 

@@ -24,6 +24,12 @@ __device__ __forceinline__ unsigned long long wmf_item_key(float s, int64_t item
     return ((unsigned long long)wmf_score_key(s) << 32) | (unsigned long long)(~(uint32_t)item);
 }
 
+// slot `at` of a top-n call's outputs: the item and the score of `key`, or the padding for 0 (no key of an item is 0: its low word is ~id)
+__device__ __forceinline__ void rec_write_slot(int32_t* __restrict__ out_items, float* __restrict__ out_scores, int64_t at, unsigned long long key) {
+    out_items[at] = key ? (int32_t)(~(uint32_t)(key & 0xFFFFFFFFull)) : -1;
+    if (out_scores) out_scores[at] = key ? wmf_key_float((uint32_t)(key >> 32)) : -__builtin_inff();
+}
+
 __device__ __forceinline__ void wmf_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();

@@ -96,6 +96,54 @@ __device__ __forceinline__ unsigned long long rec_wide_cut_buffer(unsigned long 
     return T;
 }
 
+// The topn best keys of all of a row's slices -- K: the row's n_slices buffers of cap keys as the scan left them, C: their counts --
+// sorted best first into sel (LDS, WMF_RECOMMEND_WIDE_MAX_TOPN keys): the exact select above over the buffers, then a bitonic sort
+// (the keys are distinct: one result).  By the 256 threads of a workgroup together, t the thread; hist: 256 words and counters: two
+// ints of LDS.  Every thread returns the number of keys, min(topn, the row's keys); the caller holds a barrier between its reads of
+// sel and the next row.  What recommend_select_wide_kernel (wmf_recommend.hip) and sample_select_kernel (wmf_sample.hip) share.
+__device__ __forceinline__ int rec_wide_select_row(const unsigned long long* __restrict__ K, const int32_t* __restrict__ C, int n_slices,
+                                                   int topn, int cap, unsigned long long* sel, unsigned* hist, int* counters, int t) {
+    int& total_s = counters[0];
+    int& fill_s = counters[1];
+    if (t == 0) { total_s = 0; fill_s = 0; }
+    __syncthreads();
+    int mine = 0;
+    for (int s = t; s < n_slices; s += 256) mine += min(C[s], cap);
+    if (mine) atomicAdd(&total_s, mine);
+    __syncthreads();
+    const int m = total_s, count = min(m, topn);                   // (uniform: the select below holds barriers)
+    unsigned long long T = 1ull;                                   // every key of an item is above 0
+    if (m > topn) T = rec_wide_kth<256>(K, C, n_slices, cap, 0, cap, topn, hist, t);
+    int P = 1;
+    while (P < count) P <<= 1;
+    for (int i = t; i < P; i += 256) sel[i] = 0ull;
+    __syncthreads();
+    for (int s = 0; s < n_slices; ++s) {
+        const int c = min(C[s], cap);
+        for (int e = t; e < c; e += 256) {
+            const unsigned long long key = K[(size_t)s * cap + e];
+            if (key >= T) {
+                const int slot = atomicAdd(&fill_s, 1);            // exactly `count` keys are at or above T
+                if (slot < topn) sel[slot] = key;
+            }
+        }
+    }
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = t; i < P; i += 256) {
+                const int o = i ^ j;
+                if (o > i) {
+                    const unsigned long long x = sel[i], y = sel[o];
+                    if ((i & k) == 0 ? x < y : x > y) { sel[i] = y; sel[o] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    return count;
+}
+
 // The scan's epilogue.  Workspace: keys[(b * n_slices + slice) * cap + e], e < counts[b * n_slices + slice], in no order, the topn
 // best eligible keys of that slice among them.  LDS past the stages: [thresholds: 16 per wave, 8 B][counts: 16 per wave][histogram:
 // 256 per wave].  MASK as in RecTopN.

@@ -130,6 +130,58 @@ class _Allow:
         return filt.upload() if filt is not None else (lambda b0: (None, 0, 0, None, None, 0))
 
 
+class _Sample:
+    """The sampling arguments of ``sample_items`` / ``sample_items_for``, checked on the host (every error a ValueError, before the
+    GPU is asked for): ``n`` in 1..CANDIDATES_MAX, a finite ``temperature >= 0`` (> 0 with ``return_log_prob``), ``seed`` in [0, 2^64)
+    and ``streams``, one uint64 per row (None: ``default``).  ``logz``: the rows' log-partitions, left here by _sample_scan."""
+
+    def __init__(self, n, temperature, seed, streams, default, return_log_prob):
+        self.n = int(n)
+        if self.n < 1 or self.n > CANDIDATES_MAX:
+            raise ValueError(f"n must be between 1 and {CANDIDATES_MAX}, not {self.n}")
+        self.temperature = _checked_temperature(temperature, allow_zero=not return_log_prob)
+        if isinstance(seed, (bool, float)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f"seed must be an integer in [0, 2^64), not {seed!r}")
+        self.seed = int(seed)
+        if streams is None:
+            streams = default
+        else:
+            given, streams = streams, np.asarray(streams)
+            if streams.dtype.kind not in "iu":                     # Python integers beyond int64 arrive as objects or floats
+                streams = np.asarray(given, dtype=object)
+                if streams.ndim == 1 and all(isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_)) and 0 <= x < 2 ** 64
+                                             for x in streams):
+                    streams = np.array([int(x) for x in streams], dtype=np.uint64)
+            if streams.dtype.kind not in "iu" or streams.ndim != 1 or len(streams) != len(default):
+                raise ValueError(f"streams must be a 1-D integer array with one entry per row ({len(default)})")
+            if len(streams) and streams.dtype != np.uint64 and streams.min() < 0:
+                raise ValueError("streams must lie in [0, 2^64)")
+        self.streams = np.ascontiguousarray(streams, dtype=np.uint64)
+        self.want_logp, self.logz = bool(return_log_prob), None
+
+    def result(self, out_items, out_scores, good, one, return_scores):
+        """What the sampling calls return: the items, then the scores with ``return_scores``, then with ``return_log_prob`` the
+        float64 ``score / temperature - log Z`` of every pick (-inf in the padding); ``good``: the rows that have a list."""
+        out = [out_items] + ([out_scores] if return_scores else [])
+        if self.want_logp:
+            logp = np.full(out_items.shape, -np.inf, dtype=np.float64)
+            if self.logz is not None:
+                with np.errstate(invalid="ignore"):                # (the padding: -inf - -inf)
+                    got = out_scores.astype(np.float64) / np.float64(np.float32(self.temperature)) - self.logz.astype(np.float64)[:, None]
+                keep = (out_items >= 0) & good[:, None]
+                logp[keep] = got[keep]
+            out.append(logp)
+        out = [a[0] for a in out] if one else out
+        return out[0] if len(out) == 1 else tuple(out)
+
+
+def _checked_temperature(temperature, allow_zero):
+    t = float(temperature)
+    if not 0 <= t <= float(np.finfo(np.float32).max) or (not allow_zero and np.float32(t) <= 0):    # (a NaN fails the first)
+        raise ValueError(f"temperature must be finite and {'>= 0' if allow_zero else '> 0'}, not {temperature!r}")
+    return t
+
+
 def _padded(*shape):
     """The outputs every top-n call fills: int64 items padded with -1 and float32 scores padded with -inf, of ``shape``."""
     return np.full(shape, -1, dtype=np.int64), np.full(shape, -np.inf, dtype=np.float32)
@@ -462,6 +514,74 @@ class WMF(RecModel):
             raise ValueError(f"n must be between 1 and {CANDIDATES_MAX}, not {n}")
         return self._recommend(users, n, exclude, return_scores, allow, allow_idx, True)
 
+    # ------------------------------------------------------------------ a18: sampled lists and their propensities
+    def sample_items(self, users, n=10, temperature=1.0, seed=0, exclude=None, allow=None, allow_idx=None, streams=None,
+                     return_scores=False, return_log_prob=False):
+        """``n`` items for each of ``users`` DRAWN without replacement with probability proportional to ``exp(score / temperature)``
+        over the items the user may see -- a Plackett-Luce draw, in draw order -- instead of the argmax of ``candidates``: an
+        exploration slate, or hard negatives in proportion to the model's own softmax.  One scan of the catalogue per batch
+        (wmf_sample_topn: the ``n`` largest of ``score + temperature * Gumbel noise``); ``users``, ``exclude``, ``allow`` /
+        ``allow_idx``, padding and dtypes as in ``candidates``.  1 <= n <= CANDIDATES_MAX, ``temperature`` finite and >= 0, ``seed``
+        an integer in [0, 2^64), ``streams`` one unsigned integer per entry of ``users``: a ValueError otherwise, before the GPU is
+        asked for.  The noise of an item is a pure function of (``seed``, the row's stream, the item), and the default stream of a row
+        is its USER ID: the same user under the same seed gets the same list however the batch is cut, and a user listed twice gets
+        one list twice -- give ``streams`` to draw several lists for one user.  ``temperature == 0`` is ``candidates``.  Gumbel
+        variates beyond [-2.81, 16.64] are never drawn: relative probabilities below about e^-16 are not resolved.
+        Returns int64 [len(users), n], padded with -1; with ``return_scores`` also the MODEL's float32 scores of the picks (not the
+        perturbed keys), padded with -inf; with ``return_log_prob`` also float64 ``score / temperature - log Z``, the log of the
+        probability with which the item is drawn FIRST among the same eligible items (its single-draw propensity), -inf in the
+        padding; ``log Z`` comes from wmf_log_partition in the same call, and ``temperature`` must then be > 0.  An int user gives
+        one row."""
+        n_items = self.items.shape[0]
+        one, u = self._checked_users(users, exclude)
+        sample = _Sample(n, temperature, seed, streams, u.astype(np.uint64), return_log_prob)
+        filt = None if allow is None and allow_idx is None else _Allow(allow, allow_idx, n_items, len(u), "item")
+        _lib.require_gpu()
+        out_items, out_scores = _padded(len(u), sample.n)
+        if len(u) and not (filt is not None and filt.empty):
+            users_t, items_t, f, ld = self._device_factors()
+            out_items[:], scores = self._recommend_scan(users_t, items_t, f, ld, u, sample.n, self._seen_rows(exclude, u),
+                                                        return_scores or sample.want_logp, filt, sample=sample)
+            if scores is not None:
+                out_scores[:] = scores
+        return sample.result(out_items, out_scores, np.ones(len(u), dtype=bool), one, return_scores)
+
+    def sample_items_for(self, count_rows, n=10, temperature=1.0, seed=0, exclude_history=True, allow=None, allow_idx=None, streams=None,
+                         return_scores=False, return_log_prob=False, alpha=10, beta=1, pre_process_count='log'):
+        """``sample_items`` for histories instead of user ids, as ``candidates_for`` is to ``candidates``: the rows of ``count_rows``
+        are folded in on the device and ``n`` items are drawn for each.  The default stream of a row is its position in
+        ``count_rows``.  A row whose fold-in failed is all -1 / -inf.  Bit for bit the output of ``sample_items`` on a model whose
+        ``users`` are ``fold_in(count_rows)``, given the same streams."""
+        mat, _ = self._foldin_arguments(count_rows, pre_process_count)
+        sample = _Sample(n, temperature, seed, streams, np.arange(mat.shape[0], dtype=np.uint64), return_log_prob)
+        return self._recommend_for(mat, sample.n, CANDIDATES_MAX, "n", exclude_history, return_scores, alpha, beta, pre_process_count,
+                                   allow, allow_idx, sample=sample)
+
+    def log_partition(self, users, temperature=1.0, exclude=None, allow=None, allow_idx=None):
+        """``log sum_j exp(score(u, j) / temperature)`` over the items each of ``users`` may see (``exclude``, ``allow`` / ``allow_idx``
+        as in ``recommend``): what turns a score into the log-probability of ``sample_items``.  One scan per batch
+        (wmf_log_partition); ``temperature`` finite and > 0, a ValueError otherwise.  Returns float32 [len(users)], -inf for a user
+        with nothing eligible; an int user gives a scalar."""
+        n_items = self.items.shape[0]
+        one, u = self._checked_users(users, exclude)
+        T = float(np.float32(_checked_temperature(temperature, allow_zero=False)))
+        filt = None if allow is None and allow_idx is None else _Allow(allow, allow_idx, n_items, len(u), "item")
+        _lib.require_gpu()
+        out = np.full(len(u), -np.inf, dtype=np.float32)
+        if len(u) and not (filt is not None and filt.empty):
+            users_t, items_t, f, ld = self._device_factors()
+            lib = _lib.load()
+            seen = self._seen_rows(exclude, u)
+            logz_d = torch.empty(len(u), dtype=torch.float32, device="cuda")
+            head = (_ptr(users_t), _ptr(items_t), f, ld, int(self.bias is True))
+            at = _Allow.at(filt)
+            need = lambda rows: int(lib.wmf_log_partition_workspace_bytes(rows, 0))   # noqa: E731
+            out[:] = self._scan_batches(
+                u, [None if seen is None else (seen.indptr, seen.indices)], need, [logz_d],
+                lambda b0, nb, ids, csrs, *ws: lib.wmf_log_partition(*head, ids, nb, n_items, *csrs[0], *at(b0), T, 0, _ptr(logz_d[b0:]), None, *ws),
+                self._windows(len(u), need))[0]
+        return out[0] if one else out
+
     # ------------------------------------------------------------------ a17: one list per shelf
     def recommend_shelves(self, users, groups, topn=10, exclude=None, return_scores=False, allow=None, allow_idx=None, n_groups=None):
         """The ``topn`` best items of EVERY SHELF for each of ``users``, from one scan of the catalogue (wmf_recommend_topn_grouped):
@@ -777,11 +897,41 @@ class WMF(RecModel):
                                       None, ws[-1])
         return self._scan_batches(u, [None if seen is None else (seen.indptr, seen.indices)], need, [items_d, scores_d], call, rows)
 
-    def _recommend_scan(self, users_t, items_t, f, ld, u, topn, seen, want_scores, filt, wide=False, mmr=None):
+    def _sample_scan(self, users_t, items_t, f, ld, u, n, seen, want_scores, filt, sample):
+        """wmf_sample_topn on the rows ``u`` of the device matrix ``users_t`` in batches (_scan_batches), the streams' window moving
+        with the ids'; with ``sample.want_logp`` wmf_log_partition follows in the same window, on the same stream and workspace, and
+        the rows' log Z is left in ``sample.logz``.  Returns the host (items, scores or None)."""
+        lib = _lib.load()
+        n_items = self.items.shape[0]
+        items_d = torch.empty(len(u), n, dtype=torch.int32, device="cuda")
+        scores_d = torch.empty(len(u), n, dtype=torch.float32, device="cuda") if want_scores else None
+        logz_d = torch.empty(len(u), dtype=torch.float32, device="cuda") if sample.want_logp else None
+        streams_d = torch.from_numpy(sample.streams.view(np.int64)).cuda()
+        head = (_ptr(users_t), _ptr(items_t), f, ld, int(self.bias is True))
+        at = _Allow.at(filt)
+        T = float(np.float32(sample.temperature))
+
+        def need(rows):
+            most = int(lib.wmf_sample_workspace_bytes(rows, n, 0))
+            return max(most, int(lib.wmf_log_partition_workspace_bytes(rows, 0))) if sample.want_logp else most
+
+        def call(b0, nb, ids, csrs, *ws):
+            rc = lib.wmf_sample_topn(*head, ids, nb, n_items, *csrs[0], *at(b0), n, 0, T, sample.seed, _ptr(streams_d[b0:]), _ptr(items_d[b0:]),
+                                     _ptr(scores_d[b0:]) if want_scores else None, None, None, *ws)
+            if rc != _lib.WMF_OK or logz_d is None:
+                return rc
+            return lib.wmf_log_partition(*head, ids, nb, n_items, *csrs[0], *at(b0), T, 0, _ptr(logz_d[b0:]), None, *ws)
+        items, scores, sample.logz = self._scan_batches(u, [None if seen is None else (seen.indptr, seen.indices)], need,
+                                                        [items_d, scores_d, logz_d], call, self._windows(len(u), need))
+        return items, scores
+
+    def _recommend_scan(self, users_t, items_t, f, ld, u, topn, seen, want_scores, filt, wide=False, mmr=None, sample=None):
         """The fused top-n of the rows ``u`` of the device matrix ``users_t`` in batches (_scan_batches): wmf_recommend_topn, or with
         a filter wmf_recommend_topn_filtered -- its masks or ids uploaded once, the allow_idx window moving with the ids'.  Returns
         the host (items, scores or None).  ``wide``: wmf_recommend_topn_wide for either, in windows whose workspace stays within
-        CANDIDATES_WS_BYTES (one row at least).  ``mmr``: _diverse_scan instead."""
+        CANDIDATES_WS_BYTES (one row at least).  ``mmr``: _diverse_scan instead; ``sample``: _sample_scan instead."""
+        if sample is not None:
+            return self._sample_scan(users_t, items_t, f, ld, u, topn, seen, want_scores, filt, sample)
         if mmr is not None:
             return self._diverse_scan(users_t, items_t, f, ld, u, topn, seen, want_scores, filt, mmr)
         lib = _lib.load()
@@ -1212,9 +1362,10 @@ class WMF(RecModel):
         return (out_items, out_scores) if return_scores else out_items
 
     def _recommend_for(self, count_rows, topn, limit, name, exclude_history, return_scores, alpha, beta, pre_process_count, allow, allow_idx,
-                       mmr=None):
+                       mmr=None, sample=None):
         """recommend_for (limit RECOMMEND_MAX_TOPN: the LDS kernels) and candidates_for (limit CANDIDATES_MAX: the wide ones);
-        ``mmr``: the checked (pool, lam, cosine) of recommend_diverse_for (_diverse_scan)."""
+        ``mmr``: the checked (pool, lam, cosine) of recommend_diverse_for (_diverse_scan); ``sample``: the _Sample of
+        sample_items_for (_sample_scan), which also shapes the result."""
         mat, mode = self._foldin_arguments(count_rows, pre_process_count)
         topn = int(topn)
         if topn < 1 or topn > limit:
@@ -1223,18 +1374,22 @@ class WMF(RecModel):
         filt = None if allow is None and allow_idx is None else _Allow(allow, allow_idx, self.items.shape[0], B, "item")
         _lib.require_gpu()
         out_items, out_scores = _padded(B, topn)
+        want_scores = return_scores or (sample is not None and sample.want_logp)
+        good = np.zeros(B, dtype=bool)
         if B and not (filt is not None and filt.empty):
             X_d, items_t, f, ld = self._fold_in_device(mat, alpha, beta, mode)
             seen = None
             if exclude_history:
                 seen = mat.copy()                                  # the seen list as ``recommend`` prepares ``exclude``
                 seen.sort_indices()
-            got_items, got_scores = self._recommend_scan(X_d, items_t, f, ld, np.arange(B, dtype=np.int64), topn, seen, return_scores, filt,
-                                                         limit == CANDIDATES_MAX, mmr)
+            got_items, got_scores = self._recommend_scan(X_d, items_t, f, ld, np.arange(B, dtype=np.int64), topn, seen, want_scores, filt,
+                                                         limit == CANDIDATES_MAX, mmr, sample)
             good = ~torch.isnan(X_d[:, :f]).any(dim=1).cpu().numpy()
             out_items[good] = got_items[good]
-            if return_scores:
+            if want_scores:
                 out_scores[good] = got_scores[good]
+        if sample is not None:
+            return sample.result(out_items, out_scores, good, False, return_scores)
         return (out_items, out_scores) if return_scores else out_items
 
     def _foldin_arguments(self, count_rows, pre_process_count):
