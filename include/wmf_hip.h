@@ -300,6 +300,71 @@ int wmf_foldin_rows(const float* Y, int64_t m, int f, int ld, int bias, const fl
                     float* X_out, int32_t* fail_count,
                     void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- the posterior of a folded-in row: Thompson draws, and the mean and variance of a score ----------------------------------
+ * The probabilistic reading of the row system of wmf_foldin_rows: a Gaussian likelihood with precision w_e + 1 on a stored entry and
+ * 1 on every other item, a Gaussian prior of precision lambda and unit noise give the row the posterior N(x_u, A_u^-1) -- x_u and
+ * A_u as defined there.  In whitened coordinates q = y~ W_white, with I + E_u = L L^T (float32 Cholesky), b = sum_e (w_e + 1) q_j and
+ * c = L^-1 b:  A_u^-1 = W_white L^-T L^-1 W_white^T, because W_white W_white^T = (G~ + lambda I)^-1.
+ *
+ * wmf_posterior_draw_rows: n_draws draws of every row,
+ *     X_out[u * n_draws + s] = x~_s = W_white L^-T (c + sigma xi_s),      xi_s: f standard normal variates,
+ *   with mean x_u and covariance sigma^2 A_u^-1.  The right-hand side is fmaf(sigma, xi, c), component by component; sigma == 0 takes c
+ *   itself (no product), and the result is then wmf_foldin_rows's, bit for bit, in every one of the n_draws rows.
+ *   The noise is a pure function of (seed, stream, draw, component) -- no generator with state (mix: see wmf_sample_topn):
+ *     a  = mix(seed + 0x9E3779B97F4A7C15 * (stream + 1))             the row prefix of wmf_sample_topn
+ *     h  = mix(a + 0x9E3779B97F4A7C15 * (2^32 * (draw + 1) + component + 1))
+ *     k1 = h >> 41;  k2 = (h >> 18) & 0x7FFFFF                       23 bits each
+ *     u1 = (2 k1 + 1) * 2^-24;  t = (2 k2 + 1) * 2^-23               both exact in float32
+ *     xi = sqrtf(-2 logf(u1)) * cospif(t)                            the accurate functions
+ *   stream: row_stream[u], a uint64 per row on the device; row_stream == NULL: stream = u.  The keys are at least 2^32 + 1, those of
+ *   wmf_sample_topn's items at most 2^32: one (seed, stream) serves both without a shared hash input.  The tail is cut off:
+ *   |xi| <= sqrt(48 ln 2) = 5.768 (a variate beyond it, probability 8e-9, is never drawn).  Draw s has the same bits whatever n_draws
+ *   is, whatever the row's position and whatever the other rows of the launch are.
+ *   X_out is [n * n_draws, ld] in the library's layout, the padding columns written as zeros: a block of rows of `users` for
+ *   wmf_recommend_topn*.  An EMPTY row has I + E_u = I and c = 0: its draws are the prior's, W_white sigma xi_s (zeros at sigma == 0,
+ *   as wmf_foldin_rows).  Limits: 1 <= n_draws <= WMF_POSTERIOR_MAX_DRAWS, n * n_draws < 2^31, sigma finite and >= 0.
+ *
+ * wmf_posterior_score_rows: for targets int32 [n, n_targets] (item ids in [0, m), -1 for an empty slot), with z_i = L^-1 q_i,
+ *     out_var[u, t]  = z_i . z_i          = y~_i^T A_u^-1 y~_i: the variance of the score, a sum of squares and so never negative;
+ *     out_mean[u, t] = z_i . c + beta_i   = y~_i . x_u + beta_i in exact arithmetic: wmf_explain_rows's total, predict on the folded-in row.
+ *   An empty row gives var = |q_i|^2, the prior variance, and mean = beta_i.  A -1 slot writes 0 to both.  Either output may be NULL,
+ *   not both.  A target's outputs do not depend on the other targets of its row.  Limits: 1 <= n_targets <=
+ *   WMF_POSTERIOR_MAX_TARGETS (split longer lists; WMF.score_posterior does).
+ *
+ * Both: the inputs of wmf_foldin_rows (all arrays on the device, Y un-whitened, indptr possibly a window; 1 <= m < 2^31, 0 <= n <
+ *   2^31, n == 0 a no-op).  One 256-thread workgroup per row, the row's system in LDS at every width f = 1 .. WMF_MAX_F; the gather and
+ *   the factorisation are wmf_foldin_rows's, operation for operation; then 16 right-hand sides at a time, a 16-lane group each.  A row
+ *   whose I + E_u is not positive definite gets NaN in the f columns of all its draws (zeros in the padding), or in both outputs of
+ *   its non-empty slots, and is counted once in fail_count (device int32, the caller zeroes it).  Every output element is written.
+ *   workspace: wmf_posterior_{draw,score}_workspace_bytes (a small constant: reserved, not written).  The call only enqueues.
+ *   WMF_EINVAL, before any HIP call and with the outputs untouched, for a bad shape, a null pointer (row_stream and one score output
+ *   excepted), a count out of range, n * n_draws >= 2^31, a sigma that is negative or not finite, or a workspace that is too small.
+ *   No floating-point atomics and fixed reduction orders: two runs give the same bits; a row's outputs depend on nothing but the row
+ *   and, for the draws, its stream.
+ * wmf_posterior_noise: xi (out_xi, may be NULL) and k1, k2 (out_k1k2 uint32 [n, 2], may be NULL) of n arbitrary (row_stream[i],
+ *   draws[i], components[i]) triples from the draw kernel's own device function (row_stream == NULL: stream = i; draws and components
+ *   int32 in [0, 2^31)): what the exact tests stand on.  WMF_EINVAL for n < 0, a null draws or components, or both outputs null.
+ * Measured (MI355X, 2048 rows, 1 000 000 items, k = 128 + biases, about 10 / 100 entries per row; profiles/r26_posterior.json): one draw
+ *   per row 1.15 / 2.35 ms where wmf_foldin_rows takes 1.15 / 2.53 ms, 16 draws 1.26 / 2.44 ms; 100 targets per row 3.5 / 4.7 ms, 1000
+ *   targets 24.6 / 25.7 ms (a pass of 16 targets costs a whitening and f barriers: torch's batched float64 Cholesky route is the
+ *   faster one for the variances of many targets, 4.05 / 4.61 ms for the mean, 16 draws and 100 variances). */
+#define WMF_POSTERIOR_MAX_DRAWS 4096
+#define WMF_POSTERIOR_MAX_TARGETS 4096
+int64_t wmf_posterior_draw_workspace_bytes(int64_t n, int f, int32_t n_draws);
+int wmf_posterior_draw_rows(const float* Y, int64_t m, int f, int ld, int bias, const float* W_white,
+                            const int64_t* indptr, const int32_t* indices, const float* values, int64_t n,
+                            int32_t n_draws, float sigma, uint64_t seed, const uint64_t* row_stream,
+                            float* X_out, int32_t* fail_count,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+int64_t wmf_posterior_score_workspace_bytes(int64_t n, int f, int32_t n_targets);
+int wmf_posterior_score_rows(const float* Y, int64_t m, int f, int ld, int bias, const float* W_white,
+                             const int64_t* indptr, const int32_t* indices, const float* values, int64_t n,
+                             const int32_t* targets, int32_t n_targets,
+                             float* out_mean, float* out_var, int32_t* fail_count,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+int wmf_posterior_noise(uint64_t seed, const uint64_t* row_stream, const int32_t* draws, const int32_t* components, int64_t n,
+                        float* out_xi, uint32_t* out_k1k2, void* stream);
+
 /* out[p] = predict(users_idx[p], items_idx[p])   wmf_model.py:205-211.
  * n_u == 1 or n_i == 1 broadcasts that index (the reference's one-user / one-item form).
  * An empty side (n_u == 0 or n_i == 0, the other 0 or 1) has no pairs: WMF_OK, nothing is read or written. */

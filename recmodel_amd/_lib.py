@@ -52,6 +52,13 @@ SIGNATURES = {
                                  c_vp]),
     "wmf_foldin_workspace_bytes": (c_i64, [c_i64, c_int]),
     "wmf_foldin_rows": (c_int, [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "wmf_posterior_draw_workspace_bytes": (c_i64, [c_i64, c_int, c_int]),
+    "wmf_posterior_draw_rows": (c_int, [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, ctypes.c_float,
+                                        ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "wmf_posterior_score_workspace_bytes": (c_i64, [c_i64, c_int, c_int]),
+    "wmf_posterior_score_rows": (c_int, [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp,
+                                         c_vp, c_i64, c_vp]),
+    "wmf_posterior_noise": (c_int, [ctypes.c_uint64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "wmf_predict_pairs": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "wmf_partial_row_floats": (c_i64, [c_int]),
     "wmf_accumulate_rows": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp]),

@@ -631,6 +631,74 @@ int wmf_foldin_rows(const float* Y, int64_t m, int f, int ld, int bias, const fl
                         "wmf_foldin_rows", f, ld, "");
 }
 
+int64_t wmf_posterior_draw_workspace_bytes(int64_t n, int f, int32_t n_draws) {
+    (void)n; (void)f; (void)n_draws;
+    return wmf_posterior_ws_bytes();
+}
+int64_t wmf_posterior_score_workspace_bytes(int64_t n, int f, int32_t n_targets) {
+    (void)n; (void)f; (void)n_targets;
+    return wmf_posterior_ws_bytes();
+}
+
+// the checks the two posterior calls share: the shape, the row arguments of wmf_foldin_rows, the count per row and the workspace
+static int check_posterior(const char* what, int f, int ld, bool null_pointer, int64_t m, int64_t n, const char* per_row, int32_t count,
+                           int32_t max_count, int64_t workspace_bytes) {
+    int rc = check_shape(f, ld);
+    if (rc) return rc;
+    if (null_pointer) { wmf_set_error("%s: null pointer", what); return WMF_EINVAL; }
+    if (m < 1 || m > 0x7fffffffLL || n < 0 || n > 0x7fffffffLL || count < 1 || count > max_count) {
+        wmf_set_error("%s: need 1 <= m < 2^31, 0 <= n < 2^31, 1 <= %s <= %d (m=%lld, n=%lld, %s=%d)", what, per_row, (int)max_count,
+                      (long long)m, (long long)n, per_row, (int)count);
+        return WMF_EINVAL;
+    }
+    if (workspace_bytes < wmf_posterior_ws_bytes()) {
+        wmf_set_error("%s: workspace too small (%lld < %lld bytes)", what, (long long)workspace_bytes, (long long)wmf_posterior_ws_bytes());
+        return WMF_EINVAL;
+    }
+    return WMF_OK;
+}
+
+int wmf_posterior_draw_rows(const float* Y, int64_t m, int f, int ld, int bias, const float* W_white, const int64_t* indptr,
+                            const int32_t* indices, const float* values, int64_t n, int32_t n_draws, float sigma, uint64_t seed,
+                            const uint64_t* row_stream, float* X_out, int32_t* fail_count, void* workspace, int64_t workspace_bytes,
+                            void* stream) {
+    const char* what = "wmf_posterior_draw_rows";
+    int rc = check_posterior(what, f, ld, !Y || !W_white || !indptr || !indices || !values || !X_out || !fail_count || !workspace, m, n,
+                             "n_draws", n_draws, WMF_POSTERIOR_MAX_DRAWS, workspace_bytes);
+    if (rc) return rc;
+    if (n * n_draws > 0x7fffffffLL) {
+        wmf_set_error("%s: need n * n_draws < 2^31 (n=%lld, n_draws=%d)", what, (long long)n, (int)n_draws);
+        return WMF_EINVAL;
+    }
+    if (!(sigma >= 0.f && sigma <= 3.4028234663852886e38f)) { wmf_set_error("%s: need a finite sigma >= 0", what); return WMF_EINVAL; }
+    if (n == 0) return WMF_OK;
+    return launch_error(wmf_launch_posterior_draw(Y, f, ld, bias != 0, W_white, indptr, indices, values, n, n_draws, sigma, seed, row_stream,
+                                                  X_out, fail_count, (hipStream_t)stream), what, f, ld, "");
+}
+
+int wmf_posterior_score_rows(const float* Y, int64_t m, int f, int ld, int bias, const float* W_white, const int64_t* indptr,
+                             const int32_t* indices, const float* values, int64_t n, const int32_t* targets, int32_t n_targets,
+                             float* out_mean, float* out_var, int32_t* fail_count, void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* what = "wmf_posterior_score_rows";
+    int rc = check_posterior(what, f, ld, !Y || !W_white || !indptr || !indices || !values || !targets || (!out_mean && !out_var) ||
+                             !fail_count || !workspace, m, n, "n_targets", n_targets, WMF_POSTERIOR_MAX_TARGETS, workspace_bytes);
+    if (rc) return rc;
+    if (n == 0) return WMF_OK;
+    return launch_error(wmf_launch_posterior_score(Y, f, ld, bias != 0, W_white, indptr, indices, values, n, targets, n_targets, out_mean,
+                                                   out_var, fail_count, (hipStream_t)stream), what, f, ld, "");
+}
+
+int wmf_posterior_noise(uint64_t seed, const uint64_t* row_stream, const int32_t* draws, const int32_t* components, int64_t n, float* out_xi,
+                        uint32_t* out_k1k2, void* stream) {
+    if (n < 0 || !draws || !components || (!out_xi && !out_k1k2)) {
+        wmf_set_error("wmf_posterior_noise: negative n, null draws or components, or no output");
+        return WMF_EINVAL;
+    }
+    if (n == 0) return WMF_OK;
+    wmf_launch_posterior_noise(seed, row_stream, draws, components, n, out_xi, out_k1k2, (hipStream_t)stream);
+    return check_launch("wmf_posterior_noise");
+}
+
 int wmf_predict_pairs(const float* users, const float* items, int f, int ld, int bias, const int32_t* users_idx,
                       int64_t n_u, const int32_t* items_idx, int64_t n_i, float* out, void* stream) {
     int rc = check_shape(f, ld);

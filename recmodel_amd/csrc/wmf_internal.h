@@ -225,6 +225,17 @@ int wmf_launch_explain(const float* Y, int f, int ld, int bias, const float* W, 
 int64_t wmf_foldin_ws_bytes(int64_t n, int f);
 int wmf_launch_foldin(const float* Y, int f, int ld, int bias, const float* W, const int64_t* indptr, const int32_t* indices,
                       const float* values, int64_t n, float* X_out, int32_t* fail_count, hipStream_t st);
+// wmf_posterior.hip: draws from the posterior of a folded-in row, mean and variance of its scores, and the noise of arbitrary
+// (stream, draw, component) triples
+int64_t wmf_posterior_ws_bytes(void);
+int wmf_launch_posterior_draw(const float* Y, int f, int ld, int bias, const float* W, const int64_t* indptr, const int32_t* indices,
+                              const float* values, int64_t n, int n_draws, float sigma, uint64_t seed, const uint64_t* row_stream,
+                              float* X_out, int32_t* fail_count, hipStream_t st);
+int wmf_launch_posterior_score(const float* Y, int f, int ld, int bias, const float* W, const int64_t* indptr, const int32_t* indices,
+                               const float* values, int64_t n, const int32_t* targets, int n_targets, float* out_mean, float* out_var,
+                               int32_t* fail_count, hipStream_t st);
+void wmf_launch_posterior_noise(uint64_t seed, const uint64_t* row_stream, const int32_t* draws, const int32_t* components, int64_t n,
+                                float* out_xi, uint32_t* out_k1k2, hipStream_t st);
 int wmf_launch_predict(const float* users, const float* items, int f, int ld, int bias, const int32_t* ui, int64_t n_u,
                        const int32_t* ii, int64_t n_i, float* out, hipStream_t st);
 int wmf_launch_hits(const float* users, const float* items, int ld, int bias, const int32_t* pair_user,

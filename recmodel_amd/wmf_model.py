@@ -41,6 +41,8 @@ MMR_MAX_POOL = 4096             # WMF_MMR_MAX_POOL of include/wmf_hip.h: the lar
 ILS_MAX_WIDTH = 128               # WMF_ILS_MAX_WIDTH of include/wmf_hip.h: the longest list of intra_list_similarity()
 RANKPOS_MAX_TARGETS = 16          # WMF_RANKPOS_MAX_TARGETS of include/wmf_hip.h: rank_positions() splits longer rows
 EXPLAIN_MAX_TARGETS = 16          # WMF_EXPLAIN_MAX_TARGETS of include/wmf_hip.h: explain() splits longer target lists
+POSTERIOR_MAX_DRAWS = 4096        # WMF_POSTERIOR_MAX_DRAWS of include/wmf_hip.h: the draws of a row in one posterior_draws() call
+POSTERIOR_MAX_TARGETS = 4096      # WMF_POSTERIOR_MAX_TARGETS of include/wmf_hip.h: score_posterior() splits longer item lists
 
 
 def _wrapped_ids(ids, n, what, dtype=np.int32):
@@ -140,23 +142,7 @@ class _Sample:
         if self.n < 1 or self.n > CANDIDATES_MAX:
             raise ValueError(f"n must be between 1 and {CANDIDATES_MAX}, not {self.n}")
         self.temperature = _checked_temperature(temperature, allow_zero=not return_log_prob)
-        if isinstance(seed, (bool, float)) or not 0 <= int(seed) < 2 ** 64:
-            raise ValueError(f"seed must be an integer in [0, 2^64), not {seed!r}")
-        self.seed = int(seed)
-        if streams is None:
-            streams = default
-        else:
-            given, streams = streams, np.asarray(streams)
-            if streams.dtype.kind not in "iu":                     # Python integers beyond int64 arrive as objects or floats
-                streams = np.asarray(given, dtype=object)
-                if streams.ndim == 1 and all(isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_)) and 0 <= x < 2 ** 64
-                                             for x in streams):
-                    streams = np.array([int(x) for x in streams], dtype=np.uint64)
-            if streams.dtype.kind not in "iu" or streams.ndim != 1 or len(streams) != len(default):
-                raise ValueError(f"streams must be a 1-D integer array with one entry per row ({len(default)})")
-            if len(streams) and streams.dtype != np.uint64 and streams.min() < 0:
-                raise ValueError("streams must lie in [0, 2^64)")
-        self.streams = np.ascontiguousarray(streams, dtype=np.uint64)
+        self.seed, self.streams = _checked_seed(seed), _checked_streams(streams, default)
         self.want_logp, self.logz = bool(return_log_prob), None
 
     def result(self, out_items, out_scores, good, one, return_scores):
@@ -173,6 +159,47 @@ class _Sample:
             out.append(logp)
         out = [a[0] for a in out] if one else out
         return out[0] if len(out) == 1 else tuple(out)
+
+
+class _Draw:
+    """The noise arguments of ``posterior_draws`` / ``recommend_thompson_for``, checked on the host (every error a ValueError, before
+    the GPU is asked for): ``draws`` in 1..POSTERIOR_MAX_DRAWS, a finite ``sigma >= 0``, ``seed`` in [0, 2^64) and ``streams``, one
+    uint64 per row (None: ``default``)."""
+
+    def __init__(self, draws, sigma, seed, streams, default):
+        self.draws = int(draws)
+        if self.draws < 1 or self.draws > POSTERIOR_MAX_DRAWS:
+            raise ValueError(f"draws must be between 1 and {POSTERIOR_MAX_DRAWS}, not {self.draws}")
+        s = float(sigma)
+        if not 0 <= s <= float(np.finfo(np.float32).max):          # (a NaN fails the first)
+            raise ValueError(f"sigma must be finite and >= 0, not {sigma!r}")
+        self.sigma = float(np.float32(s))
+        self.seed, self.streams = _checked_seed(seed), _checked_streams(streams, default)
+
+
+def _checked_seed(seed):
+    if isinstance(seed, (bool, float)) or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"seed must be an integer in [0, 2^64), not {seed!r}")
+    return int(seed)
+
+
+def _checked_streams(streams, default):
+    """``streams`` as contiguous uint64, one per row (None: ``default``): a ValueError for anything but a 1-D array of integers in
+    [0, 2^64) of ``len(default)``."""
+    if streams is None:
+        streams = default
+    else:
+        given, streams = streams, np.asarray(streams)
+        if streams.dtype.kind not in "iu":                         # Python integers beyond int64 arrive as objects or floats
+            streams = np.asarray(given, dtype=object)
+            if streams.ndim == 1 and all(isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_)) and 0 <= x < 2 ** 64
+                                         for x in streams):
+                streams = np.array([int(x) for x in streams], dtype=np.uint64)
+        if streams.dtype.kind not in "iu" or streams.ndim != 1 or len(streams) != len(default):
+            raise ValueError(f"streams must be a 1-D integer array with one entry per row ({len(default)})")
+        if len(streams) and streams.dtype != np.uint64 and streams.min() < 0:
+            raise ValueError("streams must lie in [0, 2^64)")
+    return np.ascontiguousarray(streams, dtype=np.uint64)
 
 
 def _checked_temperature(temperature, allow_zero):
@@ -1361,11 +1388,161 @@ class WMF(RecModel):
                 out_scores[good] = got_scores[good]
         return (out_items, out_scores) if return_scores else out_items
 
+    # ------------------------------------------------------------------ a19: the posterior of a folded-in row
+    def posterior_draws(self, count_rows, draws=1, sigma=1.0, seed=0, streams=None, alpha=10, beta=1, pre_process_count='log'):
+        """Draws from the posterior of the folded-in rows: in the probabilistic reading of the row system of ``fold_in`` -- Gaussian
+        likelihood, precision ``w + 1`` on a stored entry and 1 on every other item, prior precision ``gamma`` -- row u is
+        ``N(x_u, A_u^-1)`` with ``x_u = fold_in(count_rows)[u]``, and each draw is ``x_u + sigma * A_u^-1/2 xi`` for standard normal
+        ``xi`` (covariance ``sigma^2 A_u^-1``): wide for a visitor with three entries, narrow for one with three hundred.
+        ``count_rows``, ``alpha``, ``beta``, ``pre_process_count`` as in ``fold_in``; 1 <= draws <= POSTERIOR_MAX_DRAWS, ``sigma``
+        finite and >= 0, ``seed`` an integer in [0, 2^64), ``streams`` one unsigned integer per row (default: the row's position):
+        a ValueError otherwise, before the GPU is asked for.  The noise is a pure function of (``seed``, the row's stream, the draw's
+        number, the component): draw s of a row is the same whatever ``draws`` is and however the batch is cut, and the same
+        (seed, stream) can serve ``sample_items_for`` as well.  Normal variates beyond 5.77 in size are never drawn.  Returns float32
+        [B, draws, f]; ``sigma=0`` gives ``fold_in`` in every draw, bit for bit.  An empty row is drawn from the prior (zeros at
+        ``sigma=0``); a row whose system is not positive definite gives NaN.  One workgroup per row on the device
+        (wmf_posterior_draw_rows); a float64 model is served from its float32 copies."""
+        mat, mode = self._foldin_arguments(count_rows, pre_process_count)
+        draw = _Draw(draws, sigma, seed, streams, np.arange(mat.shape[0], dtype=np.uint64))
+        f = self.items.shape[1]
+        _lib.require_gpu()
+        if mat.shape[0] == 0:
+            return np.zeros((0, draw.draws, f), dtype=np.float32)
+        X_d = self._fold_in_device(mat, alpha, beta, mode, draw)[0]
+        return np.ascontiguousarray(X_d[:, :f].cpu().numpy()).reshape(mat.shape[0], draw.draws, f)
+
+    def recommend_thompson_for(self, count_rows, topn=10, sigma=1.0, seed=0, streams=None, exclude_history=True, return_scores=False,
+                               alpha=10, beta=1, pre_process_count='log', allow=None, allow_idx=None):
+        """Thompson sampling for histories: ``recommend_for`` on ONE draw from each row's posterior (``posterior_draws`` with
+        ``draws=1``) instead of on its mean -- the exploration of a factor model, proportionate to what the model does not know
+        about the row.  The draw never leaves the device; the scores returned are the draw's.  The arguments of ``recommend_for`` and
+        the ``sigma`` / ``seed`` / ``streams`` of ``posterior_draws``; ``topn`` up to CANDIDATES_MAX, beyond RECOMMEND_MAX_TOPN by
+        the wide kernels, as in ``recommend``.  Bit for bit ``recommend`` on a model whose ``users`` are
+        ``posterior_draws(count_rows, 1, ...)[:, 0]``; ``sigma=0`` is ``recommend_for``.  A failed row is all -1 / -inf."""
+        mat, _ = self._foldin_arguments(count_rows, pre_process_count)
+        draw = _Draw(1, sigma, seed, streams, np.arange(mat.shape[0], dtype=np.uint64))
+        return self._recommend_for(mat, topn, CANDIDATES_MAX, "topn", exclude_history, return_scores, alpha, beta, pre_process_count,
+                                   allow, allow_idx, draw=draw, wide=int(topn) > RECOMMEND_MAX_TOPN)
+
+    def recommend_thompson(self, users, count_mat, topn=10, sigma=1.0, seed=0, streams=None, return_scores=False, alpha=10, beta=1,
+                           pre_process_count='log', allow=None, allow_idx=None):
+        """``recommend_thompson_for`` for trained ids: the rows ``count_mat[users]`` (``count_mat``: the [users, items] count matrix
+        of ``train``), their stored entries excluded, and the default stream of a row its USER ID: the same user under the same seed
+        gets the same list however the batch is cut.  An int user gives one row."""
+        one, u = self._checked_users(users, count_mat)
+        if count_mat is None:
+            raise ValueError("count_mat must be the sparse [users, items] count matrix")
+        rows = scipy.sparse.csr_matrix(count_mat)[u]
+        out = self.recommend_thompson_for(rows, topn, sigma, seed, u.astype(np.uint64) if streams is None else streams, True, return_scores,
+                                          alpha, beta, pre_process_count, allow, allow_idx)
+        if one:
+            out = tuple(o[0] for o in out) if return_scores else out[0]
+        return out
+
+    def score_posterior(self, count_rows, items, alpha=10, beta=1, pre_process_count='log'):
+        """Mean and variance of the scores of ``items`` under the posterior of the folded-in rows (``posterior_draws``): ``items``
+        int [B, T] for any T, -1 an empty slot -- the output of ``recommend_for`` can be passed straight in.  Returns ``(mean,
+        var)``, float32 [B, T]: ``var = y~_i^T A_u^-1 y~_i``, never negative, the prior variance for an empty row; ``mean`` the
+        score of the folded-in row, ``predict`` on ``fold_in(count_rows)`` up to rounding.  A -1 slot gives 0 in both, a row whose
+        system is not positive definite NaN.  One workgroup per row (wmf_posterior_score_rows), POSTERIOR_MAX_TARGETS items a call."""
+        mat, mode = self._foldin_arguments(count_rows, pre_process_count)
+        B, n_items = mat.shape[0], self.items.shape[0]
+        tg = np.asarray(items)
+        if tg.size and tg.dtype.kind not in "iu":
+            raise ValueError(f"items must be integer ids, not {tg.dtype}")
+        if tg.ndim != 2 or tg.shape[0] != B:
+            raise ValueError(f"items must have shape [{B}, T], got {np.shape(items)}")
+        tg = tg.astype(np.int64)
+        if tg.size and (tg.min() < -1 or tg.max() >= n_items):
+            raise ValueError(f"items must be ids in [0, {n_items}) or -1 for an empty slot")
+        _lib.require_gpu()
+        mean, var = (np.zeros(tg.shape, dtype=np.float32) for _ in range(2))
+        if tg.size:
+            users_t, items_t, f, ld, W_white = self._device_whitening()
+            lib = _lib.load()
+            vals = self._device_confidences(mat, alpha, beta, mode)
+            fail = torch.zeros(1, dtype=torch.int32, device="cuda")
+            for t0 in range(0, tg.shape[1], POSTERIOR_MAX_TARGETS):
+                tg_d = torch.from_numpy(np.ascontiguousarray(tg[:, t0: t0 + POSTERIOR_MAX_TARGETS], dtype=np.int32)).cuda()
+                tc = tg_d.shape[1]
+                mean_d, var_d = (torch.empty(B, tc, dtype=torch.float32, device="cuda") for _ in range(2))
+                mean[:, t0: t0 + tc], var[:, t0: t0 + tc] = self._scan_batches(
+                    np.arange(B, dtype=np.int64), [(mat.indptr, mat.indices)], lambda rows: lib.wmf_posterior_score_workspace_bytes(rows, f, tc),
+                    [mean_d, var_d], lambda b0, nb, ids, csrs, *ws: lib.wmf_posterior_score_rows(
+                        _ptr(items_t), n_items, f, ld, int(self.bias is True), _ptr(W_white), *csrs[0], _ptr(vals), nb, _ptr(tg_d[b0:]), tc,
+                        _ptr(mean_d[b0:]), _ptr(var_d[b0:]), _ptr(fail), *ws))
+        return mean, var
+
+    def recommend_ucb_for(self, count_rows, topn=10, pool=None, c=1.0, exclude_history=True, return_scores=False, return_std=False,
+                          alpha=10, beta=1, pre_process_count='log', allow=None, allow_idx=None):
+        """Upper-confidence-bound re-ranking for histories: the ``pool`` best items of each folded-in row (``candidates_for``)
+        re-ordered by ``score + c * std``, ``std`` the posterior standard deviation of the score (``score_posterior``), and the
+        ``topn`` largest kept, equal keys to the lower id.  The pool, its scores and variances stay on the device
+        (wmf_recommend_topn_wide into wmf_posterior_score_rows, per window of rows; the sort of at most 4096 float32 keys a row is
+        torch's).  ``pool=None`` is ``min(10 * topn, CANDIDATES_MAX)``; 1 <= topn <= pool <= CANDIDATES_MAX, ``c`` finite and >= 0: a
+        ValueError otherwise, before the GPU is asked for.  Returns the items int64 [B, topn], padded with -1; with ``return_scores``
+        the MODEL's float32 scores (not the keys), padded with -inf; with ``return_std`` also the float32 standard deviations, 0 in
+        the padding.  ``c=0`` is ``recommend_for``, bit for bit.  A failed row is all -1 / -inf / 0."""
+        topn = int(topn)
+        pool = min(10 * topn, CANDIDATES_MAX) if pool is None else int(pool)
+        if pool < 1 or pool > CANDIDATES_MAX:
+            raise ValueError(f"pool must be between 1 and {CANDIDATES_MAX}, not {pool}")
+        if topn >= 1 and pool < topn:
+            raise ValueError(f"pool ({pool}) must be at least topn ({topn})")
+        cf = float(c)
+        if not 0 <= cf <= float(np.finfo(np.float32).max):         # (a NaN fails the first)
+            raise ValueError(f"c must be finite and >= 0, not {c!r}")
+        return self._recommend_for(count_rows, topn, CANDIDATES_MAX, "topn", exclude_history, return_scores, alpha, beta, pre_process_count,
+                                   allow, allow_idx, ucb=(pool, float(np.float32(cf)), bool(return_std)))
+
+    def _ucb_scan(self, users_t, items_t, f, ld, u, topn, seen, filt, ucb, mat, vals):
+        """``candidates`` re-ranked by score + c std without leaving the device: per window of _scan_batches,
+        wmf_recommend_topn_wide(topn = pool) into pool buffers of one window's rows, wmf_posterior_score_rows on the pool as the
+        rows' targets (the rows of ``mat``, ``vals`` its transformed values), and the two sorts -- by id, then stable and descending
+        by key.  Returns the host (items, scores, std)."""
+        pool, c, _ = ucb
+        lib = _lib.load()
+        W_white = self._device_whitening()[4]
+        n_items = self.items.shape[0]
+        need_scan = lambda rows: int(lib.wmf_recommend_wide_workspace_bytes(rows, pool, 0))   # noqa: E731
+        need = lambda rows: max(need_scan(rows), int(lib.wmf_posterior_score_workspace_bytes(rows, f, pool)))   # noqa: E731
+        rows = self._windows(len(u), need)
+        pool_i = torch.empty(rows, pool, dtype=torch.int32, device="cuda")
+        pool_s, pool_v = (torch.empty(rows, pool, dtype=torch.float32, device="cuda") for _ in range(2))
+        fail = torch.zeros(1, dtype=torch.int32, device="cuda")
+        items_d = torch.empty(len(u), topn, dtype=torch.int32, device="cuda")
+        scores_d, std_d = (torch.empty(len(u), topn, dtype=torch.float32, device="cuda") for _ in range(2))
+        bias = int(self.bias is True)
+        scan = _topn_call(lib.wmf_recommend_topn_wide, (_ptr(users_t), _ptr(items_t), f, ld, bias), n_items, _Allow.at(filt), pool, pool_i, pool_s,
+                          moving=False)
+
+        def call(b0, nb, ids, csrs, *ws):
+            rc = scan(b0, nb, ids, csrs, *ws)
+            if rc != _lib.WMF_OK:
+                return rc
+            rc = lib.wmf_posterior_score_rows(_ptr(items_t), n_items, f, ld, bias, _ptr(W_white), *csrs[1], _ptr(vals), nb, _ptr(pool_i), pool,
+                                              None, _ptr(pool_v), _ptr(fail), *ws)
+            if rc != _lib.WMF_OK:
+                return rc
+            ids_sorted, by_id = torch.sort(pool_i[:nb], dim=1, stable=True)
+            std = torch.sqrt(pool_v[:nb])
+            key = pool_s[:nb] + c * std                            # (the padding: -inf + c * 0)
+            order = torch.sort(key.gather(1, by_id), dim=1, descending=True, stable=True)[1][:, :topn]
+            pick = by_id.gather(1, order)
+            items_d[b0: b0 + nb] = pool_i[:nb].gather(1, pick)
+            scores_d[b0: b0 + nb] = pool_s[:nb].gather(1, pick)
+            std_d[b0: b0 + nb] = std.gather(1, pick)
+            return _lib.WMF_OK
+        return self._scan_batches(u, [None if seen is None else (seen.indptr, seen.indices), (mat.indptr, mat.indices)], need,
+                                  [items_d, scores_d, std_d], call, rows)
+
     def _recommend_for(self, count_rows, topn, limit, name, exclude_history, return_scores, alpha, beta, pre_process_count, allow, allow_idx,
-                       mmr=None, sample=None):
+                       mmr=None, sample=None, draw=None, wide=None, ucb=None):
         """recommend_for (limit RECOMMEND_MAX_TOPN: the LDS kernels) and candidates_for (limit CANDIDATES_MAX: the wide ones);
         ``mmr``: the checked (pool, lam, cosine) of recommend_diverse_for (_diverse_scan); ``sample``: the _Sample of
-        sample_items_for (_sample_scan), which also shapes the result."""
+        sample_items_for (_sample_scan), which also shapes the result; ``draw``: the _Draw (one draw a row) of
+        recommend_thompson_for -- the rows are drawn instead of folded in; ``wide``: the wide kernels or not, where the limit does not
+        say; ``ucb``: the checked (pool, c, return_std) of recommend_ucb_for (_ucb_scan), which adds the standard deviations."""
         mat, mode = self._foldin_arguments(count_rows, pre_process_count)
         topn = int(topn)
         if topn < 1 or topn > limit:
@@ -1374,22 +1551,32 @@ class WMF(RecModel):
         filt = None if allow is None and allow_idx is None else _Allow(allow, allow_idx, self.items.shape[0], B, "item")
         _lib.require_gpu()
         out_items, out_scores = _padded(B, topn)
+        out_std = np.zeros((B, topn), dtype=np.float32)
         want_scores = return_scores or (sample is not None and sample.want_logp)
         good = np.zeros(B, dtype=bool)
         if B and not (filt is not None and filt.empty):
-            X_d, items_t, f, ld = self._fold_in_device(mat, alpha, beta, mode)
+            X_d, items_t, f, ld = self._fold_in_device(mat, alpha, beta, mode, draw)
             seen = None
             if exclude_history:
                 seen = mat.copy()                                  # the seen list as ``recommend`` prepares ``exclude``
                 seen.sort_indices()
-            got_items, got_scores = self._recommend_scan(X_d, items_t, f, ld, np.arange(B, dtype=np.int64), topn, seen, want_scores, filt,
-                                                         limit == CANDIDATES_MAX, mmr, sample)
+            u = np.arange(B, dtype=np.int64)
+            if ucb is not None:
+                got_items, got_scores, got_std = self._ucb_scan(X_d, items_t, f, ld, u, topn, seen, filt, ucb, mat,
+                                                                self._device_confidences(mat, alpha, beta, mode))
+            else:
+                got_items, got_scores = self._recommend_scan(X_d, items_t, f, ld, u, topn, seen, want_scores, filt,
+                                                             limit == CANDIDATES_MAX if wide is None else wide, mmr, sample)
             good = ~torch.isnan(X_d[:, :f]).any(dim=1).cpu().numpy()
             out_items[good] = got_items[good]
             if want_scores:
                 out_scores[good] = got_scores[good]
+            if ucb is not None:
+                out_std[good] = got_std[good]
         if sample is not None:
             return sample.result(out_items, out_scores, good, False, return_scores)
+        if ucb is not None and ucb[2]:
+            return (out_items, out_scores, out_std) if return_scores else (out_items, out_std)
         return (out_items, out_scores) if return_scores else out_items
 
     def _foldin_arguments(self, count_rows, pre_process_count):
@@ -1407,21 +1594,38 @@ class WMF(RecModel):
         mat = count_rows if scipy.sparse.isspmatrix_csr(count_rows) else scipy.sparse.csr_matrix(count_rows)
         return mat, 0 if pre_process_count == 'log' else 1
 
-    def _fold_in_device(self, mat, alpha, beta, mode):
+    @staticmethod
+    def _device_confidences(mat, alpha, beta, mode):
+        """The stored values of the CSR ``mat`` on the device, transformed as ``train`` transforms them (one spare element: never
+        empty)."""
+        vals = torch.from_numpy(np.append(np.asarray(mat.data, dtype=np.float32), np.float32(0))).cuda()
+        _lib.check(_lib.load().wmf_confidence_transform(_ptr(vals), len(mat.data), float(alpha), float(beta), mode, _stream()))
+        return vals
+
+    def _fold_in_device(self, mat, alpha, beta, mode, draw=None):
         """wmf_foldin_rows in batches of rows (_scan_batches) on the rows of the CSR ``mat`` (at least one).  Returns (the folded
-        block [B, ld] on the device in the library's layout, items_t, f, ld)."""
+        block [B, ld] on the device in the library's layout, items_t, f, ld).  ``draw``: a _Draw, then wmf_posterior_draw_rows
+        instead -- the block is [B * draw.draws, ld], the draws of a row next to each other, the streams' window moving with the
+        rows'."""
         users_t, items_t, f, ld, W_white = self._device_whitening()
         lib = _lib.load()
         B = mat.shape[0]
-        vals = torch.from_numpy(np.append(np.asarray(mat.data, dtype=np.float32), np.float32(0))).cuda()   # (one spare element: never empty)
-        _lib.check(lib.wmf_confidence_transform(_ptr(vals), len(mat.data), float(alpha), float(beta), mode, _stream()))
+        vals = self._device_confidences(mat, alpha, beta, mode)
         fail = torch.zeros(1, dtype=torch.int32, device="cuda")
-        X_d = torch.empty(B, ld, dtype=torch.float32, device="cuda")
-        self._scan_batches(
-            np.arange(B, dtype=np.int64), [(mat.indptr, mat.indices)], lambda rows: lib.wmf_foldin_workspace_bytes(rows, f), [],
-            lambda b0, nb, ids, csrs, *ws: lib.wmf_foldin_rows(
-                _ptr(items_t), items_t.shape[0], f, ld, int(self.bias is True), _ptr(W_white), *csrs[0], _ptr(vals), nb,
-                _ptr(X_d[b0:]), _ptr(fail), *ws))
+        head = (_ptr(items_t), items_t.shape[0], f, ld, int(self.bias is True), _ptr(W_white))
+        if draw is None:
+            X_d = torch.empty(B, ld, dtype=torch.float32, device="cuda")
+            need = lambda rows: lib.wmf_foldin_workspace_bytes(rows, f)   # noqa: E731
+            call = lambda b0, nb, ids, csrs, *ws: lib.wmf_foldin_rows(   # noqa: E731
+                *head, *csrs[0], _ptr(vals), nb, _ptr(X_d[b0:]), _ptr(fail), *ws)
+        else:
+            D = draw.draws
+            X_d = torch.empty(B * D, ld, dtype=torch.float32, device="cuda")
+            streams_d = torch.from_numpy(draw.streams.view(np.int64)).cuda()
+            need = lambda rows: lib.wmf_posterior_draw_workspace_bytes(rows, f, D)   # noqa: E731
+            call = lambda b0, nb, ids, csrs, *ws: lib.wmf_posterior_draw_rows(   # noqa: E731
+                *head, *csrs[0], _ptr(vals), nb, D, draw.sigma, draw.seed, _ptr(streams_d[b0:]), _ptr(X_d[b0 * D:]), _ptr(fail), *ws)
+        self._scan_batches(np.arange(B, dtype=np.int64), [(mat.indptr, mat.indices)], need, [], call)
         return X_d, items_t, f, ld
 
     # ------------------------------------------------------------------ a3 / a4: operator seam
