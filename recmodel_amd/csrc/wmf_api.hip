@@ -3,6 +3,7 @@
 // (RecModel/wmf_model.py:213-240, :311-351).
 #include "../../include/wmf_hip.h"
 #include "wmf_internal.h"
+#include "wmf_rowsystem.h"                  /* WMF_ROWSYS_WS_BYTES */
 
 #include <atomic>
 #include <cstdarg>
@@ -580,82 +581,56 @@ int wmf_half_step_audit_f64(const double* X, const double* Y, int f, int bias, c
                                              (hipStream_t)stream), "wmf_half_step_audit_f64", f, f, "");
 }
 
-int64_t wmf_explain_workspace_bytes(int64_t n, int f, int32_t n_targets) { return wmf_explain_ws_bytes(n, f, n_targets); }
+// The four calls on a row's own system (wmf_rowsystem.h): the workspace is reserved, never touched
+int64_t wmf_explain_workspace_bytes(int64_t, int, int32_t) { return WMF_ROWSYS_WS_BYTES; }
+int64_t wmf_foldin_workspace_bytes(int64_t, int) { return WMF_ROWSYS_WS_BYTES; }
+int64_t wmf_posterior_draw_workspace_bytes(int64_t, int, int32_t) { return WMF_ROWSYS_WS_BYTES; }
+int64_t wmf_posterior_score_workspace_bytes(int64_t, int, int32_t) { return WMF_ROWSYS_WS_BYTES; }
+
+// the checks they share: the shape, the pointers, the bounds on the catalogue and the rows, the count per row (per_row: its name, or
+// NULL for a call without one) and the workspace
+static int check_row_call(const char* what, int f, int ld, bool null_pointer, int64_t m, int64_t n, const char* per_row, int32_t count,
+                          int32_t max_count, int64_t workspace_bytes) {
+    int rc = check_shape(f, ld);
+    if (rc) return rc;
+    if (null_pointer) { wmf_set_error("%s: null pointer", what); return WMF_EINVAL; }
+    if (m < 1 || m > 0x7fffffffLL || n < 0 || n > 0x7fffffffLL || (per_row && (count < 1 || count > max_count))) {
+        if (per_row)
+            wmf_set_error("%s: need 1 <= m < 2^31, 0 <= n < 2^31, 1 <= %s <= %d (m=%lld, n=%lld, %s=%d)", what, per_row, (int)max_count,
+                          (long long)m, (long long)n, per_row, (int)count);
+        else
+            wmf_set_error("%s: need 1 <= m < 2^31, 0 <= n < 2^31 (m=%lld, n=%lld)", what, (long long)m, (long long)n);
+        return WMF_EINVAL;
+    }
+    if (workspace_bytes < WMF_ROWSYS_WS_BYTES) {
+        wmf_set_error("%s: workspace too small (%lld < %lld bytes)", what, (long long)workspace_bytes, (long long)WMF_ROWSYS_WS_BYTES);
+        return WMF_EINVAL;
+    }
+    return WMF_OK;
+}
 
 int wmf_explain_rows(const float* Y, int64_t m, int f, int ld, int bias, const float* W_white, const int64_t* indptr, const int32_t* indices,
                      const float* values, int64_t n, const int32_t* targets, int32_t n_targets, float* out_contrib, float* out_total,
                      int32_t* fail_count, void* workspace, int64_t workspace_bytes, void* stream) {
-    int rc = check_shape(f, ld);
+    const char* what = "wmf_explain_rows";
+    int rc = check_row_call(what, f, ld, !Y || !W_white || !indptr || !indices || !values || !targets || !out_contrib || !out_total ||
+                            !fail_count || !workspace, m, n, "n_targets", n_targets, WMF_EXPLAIN_MAX_TARGETS, workspace_bytes);
     if (rc) return rc;
-    if (!Y || !W_white || !indptr || !indices || !values || !targets || !out_contrib || !out_total || !fail_count || !workspace) {
-        wmf_set_error("wmf_explain_rows: null pointer");
-        return WMF_EINVAL;
-    }
-    if (m < 1 || m > 0x7fffffffLL || n < 0 || n > 0x7fffffffLL || n_targets < 1 || n_targets > WMF_EXPLAIN_MAX_TARGETS) {
-        wmf_set_error("wmf_explain_rows: need 1 <= m < 2^31, 0 <= n < 2^31, 1 <= n_targets <= %d (m=%lld, n=%lld, n_targets=%d)",
-                      WMF_EXPLAIN_MAX_TARGETS, (long long)m, (long long)n, (int)n_targets);
-        return WMF_EINVAL;
-    }
-    if (workspace_bytes < wmf_explain_ws_bytes(n, f, n_targets)) {
-        wmf_set_error("wmf_explain_rows: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
-                      (long long)wmf_explain_ws_bytes(n, f, n_targets));
-        return WMF_EINVAL;
-    }
     if (n == 0) return WMF_OK;
     return launch_error(wmf_launch_explain(Y, f, ld, bias != 0, W_white, indptr, indices, values, n, targets, n_targets, out_contrib, out_total,
-                                           fail_count, (hipStream_t)stream), "wmf_explain_rows", f, ld, "");
+                                           fail_count, (hipStream_t)stream), what, f, ld, "");
 }
-
-int64_t wmf_foldin_workspace_bytes(int64_t n, int f) { return wmf_foldin_ws_bytes(n, f); }
 
 int wmf_foldin_rows(const float* Y, int64_t m, int f, int ld, int bias, const float* W_white, const int64_t* indptr, const int32_t* indices,
                     const float* values, int64_t n, float* X_out, int32_t* fail_count, void* workspace, int64_t workspace_bytes,
                     void* stream) {
-    int rc = check_shape(f, ld);
+    const char* what = "wmf_foldin_rows";
+    int rc = check_row_call(what, f, ld, !Y || !W_white || !indptr || !indices || !values || !X_out || !fail_count || !workspace, m, n,
+                            nullptr, 0, 0, workspace_bytes);
     if (rc) return rc;
-    if (!Y || !W_white || !indptr || !indices || !values || !X_out || !fail_count || !workspace) {
-        wmf_set_error("wmf_foldin_rows: null pointer");
-        return WMF_EINVAL;
-    }
-    if (m < 1 || m > 0x7fffffffLL || n < 0 || n > 0x7fffffffLL) {
-        wmf_set_error("wmf_foldin_rows: need 1 <= m < 2^31, 0 <= n < 2^31 (m=%lld, n=%lld)", (long long)m, (long long)n);
-        return WMF_EINVAL;
-    }
-    if (workspace_bytes < wmf_foldin_ws_bytes(n, f)) {
-        wmf_set_error("wmf_foldin_rows: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
-                      (long long)wmf_foldin_ws_bytes(n, f));
-        return WMF_EINVAL;
-    }
     if (n == 0) return WMF_OK;
     return launch_error(wmf_launch_foldin(Y, f, ld, bias != 0, W_white, indptr, indices, values, n, X_out, fail_count, (hipStream_t)stream),
-                        "wmf_foldin_rows", f, ld, "");
-}
-
-int64_t wmf_posterior_draw_workspace_bytes(int64_t n, int f, int32_t n_draws) {
-    (void)n; (void)f; (void)n_draws;
-    return wmf_posterior_ws_bytes();
-}
-int64_t wmf_posterior_score_workspace_bytes(int64_t n, int f, int32_t n_targets) {
-    (void)n; (void)f; (void)n_targets;
-    return wmf_posterior_ws_bytes();
-}
-
-// the checks the two posterior calls share: the shape, the row arguments of wmf_foldin_rows, the count per row and the workspace
-static int check_posterior(const char* what, int f, int ld, bool null_pointer, int64_t m, int64_t n, const char* per_row, int32_t count,
-                           int32_t max_count, int64_t workspace_bytes) {
-    int rc = check_shape(f, ld);
-    if (rc) return rc;
-    if (null_pointer) { wmf_set_error("%s: null pointer", what); return WMF_EINVAL; }
-    if (m < 1 || m > 0x7fffffffLL || n < 0 || n > 0x7fffffffLL || count < 1 || count > max_count) {
-        wmf_set_error("%s: need 1 <= m < 2^31, 0 <= n < 2^31, 1 <= %s <= %d (m=%lld, n=%lld, %s=%d)", what, per_row, (int)max_count,
-                      (long long)m, (long long)n, per_row, (int)count);
-        return WMF_EINVAL;
-    }
-    if (workspace_bytes < wmf_posterior_ws_bytes()) {
-        wmf_set_error("%s: workspace too small (%lld < %lld bytes)", what, (long long)workspace_bytes, (long long)wmf_posterior_ws_bytes());
-        return WMF_EINVAL;
-    }
-    return WMF_OK;
+                        what, f, ld, "");
 }
 
 int wmf_posterior_draw_rows(const float* Y, int64_t m, int f, int ld, int bias, const float* W_white, const int64_t* indptr,
@@ -663,8 +638,8 @@ int wmf_posterior_draw_rows(const float* Y, int64_t m, int f, int ld, int bias, 
                             const uint64_t* row_stream, float* X_out, int32_t* fail_count, void* workspace, int64_t workspace_bytes,
                             void* stream) {
     const char* what = "wmf_posterior_draw_rows";
-    int rc = check_posterior(what, f, ld, !Y || !W_white || !indptr || !indices || !values || !X_out || !fail_count || !workspace, m, n,
-                             "n_draws", n_draws, WMF_POSTERIOR_MAX_DRAWS, workspace_bytes);
+    int rc = check_row_call(what, f, ld, !Y || !W_white || !indptr || !indices || !values || !X_out || !fail_count || !workspace, m, n,
+                            "n_draws", n_draws, WMF_POSTERIOR_MAX_DRAWS, workspace_bytes);
     if (rc) return rc;
     if (n * n_draws > 0x7fffffffLL) {
         wmf_set_error("%s: need n * n_draws < 2^31 (n=%lld, n_draws=%d)", what, (long long)n, (int)n_draws);
@@ -680,8 +655,8 @@ int wmf_posterior_score_rows(const float* Y, int64_t m, int f, int ld, int bias,
                              const int32_t* indices, const float* values, int64_t n, const int32_t* targets, int32_t n_targets,
                              float* out_mean, float* out_var, int32_t* fail_count, void* workspace, int64_t workspace_bytes, void* stream) {
     const char* what = "wmf_posterior_score_rows";
-    int rc = check_posterior(what, f, ld, !Y || !W_white || !indptr || !indices || !values || !targets || (!out_mean && !out_var) ||
-                             !fail_count || !workspace, m, n, "n_targets", n_targets, WMF_POSTERIOR_MAX_TARGETS, workspace_bytes);
+    int rc = check_row_call(what, f, ld, !Y || !W_white || !indptr || !indices || !values || !targets || (!out_mean && !out_var) ||
+                            !fail_count || !workspace, m, n, "n_targets", n_targets, WMF_POSTERIOR_MAX_TARGETS, workspace_bytes);
     if (rc) return rc;
     if (n == 0) return WMF_OK;
     return launch_error(wmf_launch_posterior_score(Y, f, ld, bias != 0, W_white, indptr, indices, values, n, targets, n_targets, out_mean,

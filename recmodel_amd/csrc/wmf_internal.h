@@ -217,17 +217,14 @@ int wmf_launch_audit(const float* X, const float* Y, int f, int ld, int bias, co
 int wmf_launch_audit_f64(const double* X, const double* Y, int f, int bias, const int64_t* indptr, const int32_t* indices,
                          const double* values, int64_t n, const double* dense, double* out_sums, double* out_rows, void* ws, hipStream_t st);
 // wmf_explain.hip: per-entry contributions of a row's history to the scores of target items
-int64_t wmf_explain_ws_bytes(int64_t n, int f, int32_t n_targets);
 int wmf_launch_explain(const float* Y, int f, int ld, int bias, const float* W, const int64_t* indptr, const int32_t* indices,
                        const float* values, int64_t n, const int32_t* targets, int n_targets, float* out_contrib, float* out_total,
                        int32_t* fail_count, hipStream_t st);
 // wmf_foldin.hip: the folded-in factors of a row's history (the x_u whose scores wmf_explain.hip splits up)
-int64_t wmf_foldin_ws_bytes(int64_t n, int f);
 int wmf_launch_foldin(const float* Y, int f, int ld, int bias, const float* W, const int64_t* indptr, const int32_t* indices,
                       const float* values, int64_t n, float* X_out, int32_t* fail_count, hipStream_t st);
 // wmf_posterior.hip: draws from the posterior of a folded-in row, mean and variance of its scores, and the noise of arbitrary
 // (stream, draw, component) triples
-int64_t wmf_posterior_ws_bytes(void);
 int wmf_launch_posterior_draw(const float* Y, int f, int ld, int bias, const float* W, const int64_t* indptr, const int32_t* indices,
                               const float* values, int64_t n, int n_draws, float sigma, uint64_t seed, const uint64_t* row_stream,
                               float* X_out, int32_t* fail_count, hipStream_t st);

@@ -53,6 +53,18 @@ def _wrapped_ids(ids, n, what, dtype=np.int32):
     return np.where(ids < 0, ids + n, ids).astype(dtype)
 
 
+def _target_ids(items, n_items, shaped):
+    """``items`` as the int64 target array of a call on the row system: integer ids, ``shaped(array)`` the caller's own shape rule
+    (it returns the 2-D array or raises), every id in [0, n_items) or -1 for an empty slot -- a ValueError otherwise."""
+    tg = np.asarray(items)
+    if tg.size and tg.dtype.kind not in "iu":
+        raise ValueError(f"items must be integer ids, not {tg.dtype}")
+    tg = shaped(tg).astype(np.int64)
+    if tg.size and (tg.min() < -1 or tg.max() >= n_items):
+        raise ValueError(f"items must be ids in [0, {n_items}) or -1 for an empty slot")
+    return tg
+
+
 def pack_allow_masks(masks):
     """bool [G, n] as the allow masks of include/wmf_hip.h: uint32 [G, ceil(n / 32)], item j is bit j & 31 of word j >> 5."""
     masks = np.atleast_2d(np.asarray(masks, dtype=bool))
@@ -1204,6 +1216,12 @@ class WMF(RecModel):
             self._white[key] = W_white
         return dev + (self._white[key],)
 
+    def _row_system_head(self):
+        """(head, items_t, f, ld): the leading arguments (Y, m, f, ld, bias, W_white) of the library's four calls on a row's own
+        system -- wmf_explain_rows, wmf_foldin_rows, wmf_posterior_draw_rows, wmf_posterior_score_rows -- from _device_whitening."""
+        _, items_t, f, ld, W_white = self._device_whitening()
+        return (_ptr(items_t), items_t.shape[0], f, ld, int(self.bias is True), _ptr(W_white)), items_t, f, ld
+
     def explain(self, users, items, count_mat, topk=10, alpha=10, beta=1, pre_process_count='log'):
         """Why these items: the score of each of ``items`` for each of ``users`` with the user's row of ``count_mat`` folded in
         -- ``predict`` on ``recompute_factors[_bias](items, C_u, gamma)`` (wmf_model.py:213-240 / :311-351), which is the
@@ -1233,19 +1251,17 @@ class WMF(RecModel):
             raise ValueError(f"topk must be at least 1 or None, not {topk}")
         one = np.ndim(users) == 0
         u = _wrapped_ids(np.atleast_1d(np.asarray(users)).reshape(-1).astype(np.int64), n_users_model, "user", np.int64)
-        tg = np.asarray(items)
-        if tg.size and tg.dtype.kind not in "iu":
-            raise ValueError(f"items must be integer ids, not {tg.dtype}")
-        flat = tg.ndim == 1 and not one
-        if one and tg.ndim == 1:
-            tg = tg.reshape(1, -1)
-        elif flat and tg.shape[0] == len(u):
-            tg = tg.reshape(-1, 1)
-        if tg.ndim != 2 or tg.shape[0] != len(u) or tg.shape[1] < 1:
-            raise ValueError(f"items must have shape [{len(u)}, T] or [{len(u)}] (an int user: [T]), got {np.shape(items)}")
-        tg = tg.astype(np.int64)
-        if tg.size and (tg.min() < -1 or tg.max() >= n_items):
-            raise ValueError(f"items must be ids in [0, {n_items}) or -1 for an empty slot")
+        flat = np.ndim(items) == 1 and not one
+
+        def shaped(tg):
+            if one and tg.ndim == 1:
+                tg = tg.reshape(1, -1)
+            elif flat and tg.shape[0] == len(u):
+                tg = tg.reshape(-1, 1)
+            if tg.ndim != 2 or tg.shape[0] != len(u) or tg.shape[1] < 1:
+                raise ValueError(f"items must have shape [{len(u)}, T] or [{len(u)}] (an int user: [T]), got {np.shape(items)}")
+            return tg
+        tg = _target_ids(items, n_items, shaped)
         _lib.require_gpu()
         # the requested rows exactly as stored (stored zeros, duplicates and their order are kept)
         mat = count_mat if scipy.sparse.isspmatrix_csr(count_mat) else scipy.sparse.csr_matrix(count_mat)
@@ -1286,10 +1302,9 @@ class WMF(RecModel):
     def _explain_rows(self, u, indptr, indices, counts, tg, alpha, beta, mode, total, contrib):
         """wmf_explain_rows in batches of rows (_scan_batches) and slices of at most EXPLAIN_MAX_TARGETS targets; fills ``total``
         [B, T] and ``contrib`` [nnz, T]."""
-        users_t, items_t, f, ld, W_white = self._device_whitening()
+        head, _, f, _ = self._row_system_head()
         lib = _lib.load()
-        vals = torch.from_numpy(np.append(counts, np.float32(0))).cuda()          # (one spare element: never empty)
-        _lib.check(lib.wmf_confidence_transform(_ptr(vals), len(counts), float(alpha), float(beta), mode, _stream()))
+        vals = self._device_confidences(counts, alpha, beta, mode)
         fail = torch.zeros(1, dtype=torch.int32, device="cuda")
         for t0 in range(0, tg.shape[1], EXPLAIN_MAX_TARGETS):
             part = np.ascontiguousarray(tg[:, t0: t0 + EXPLAIN_MAX_TARGETS], dtype=np.int32)
@@ -1301,8 +1316,7 @@ class WMF(RecModel):
             total[:, t0: t0 + tc], got = self._scan_batches(
                 u, [(indptr, indices)], lambda rows: lib.wmf_explain_workspace_bytes(rows, f, tc), [total_d, contrib_d],
                 lambda b0, nb, ids, csrs, *ws: lib.wmf_explain_rows(
-                    _ptr(items_t), items_t.shape[0], f, ld, int(self.bias is True), _ptr(W_white), *csrs[0], _ptr(vals), nb,
-                    _ptr(tg_d[b0:]), tc, _ptr(contrib_d), _ptr(total_d[b0:]), _ptr(fail), *ws))
+                    *head, *csrs[0], _ptr(vals), nb, _ptr(tg_d[b0:]), tc, _ptr(contrib_d), _ptr(total_d[b0:]), _ptr(fail), *ws))
             contrib[:, t0: t0 + tc] = got[:len(counts)]
 
     # ------------------------------------------------------------------ a16: fold_in, recommend_for
@@ -1447,20 +1461,17 @@ class WMF(RecModel):
         system is not positive definite NaN.  One workgroup per row (wmf_posterior_score_rows), POSTERIOR_MAX_TARGETS items a call."""
         mat, mode = self._foldin_arguments(count_rows, pre_process_count)
         B, n_items = mat.shape[0], self.items.shape[0]
-        tg = np.asarray(items)
-        if tg.size and tg.dtype.kind not in "iu":
-            raise ValueError(f"items must be integer ids, not {tg.dtype}")
-        if tg.ndim != 2 or tg.shape[0] != B:
-            raise ValueError(f"items must have shape [{B}, T], got {np.shape(items)}")
-        tg = tg.astype(np.int64)
-        if tg.size and (tg.min() < -1 or tg.max() >= n_items):
-            raise ValueError(f"items must be ids in [0, {n_items}) or -1 for an empty slot")
+        def shaped(tg):
+            if tg.ndim != 2 or tg.shape[0] != B:
+                raise ValueError(f"items must have shape [{B}, T], got {np.shape(items)}")
+            return tg
+        tg = _target_ids(items, n_items, shaped)
         _lib.require_gpu()
         mean, var = (np.zeros(tg.shape, dtype=np.float32) for _ in range(2))
         if tg.size:
-            users_t, items_t, f, ld, W_white = self._device_whitening()
+            head, _, f, _ = self._row_system_head()
             lib = _lib.load()
-            vals = self._device_confidences(mat, alpha, beta, mode)
+            vals = self._device_confidences(mat.data, alpha, beta, mode)
             fail = torch.zeros(1, dtype=torch.int32, device="cuda")
             for t0 in range(0, tg.shape[1], POSTERIOR_MAX_TARGETS):
                 tg_d = torch.from_numpy(np.ascontiguousarray(tg[:, t0: t0 + POSTERIOR_MAX_TARGETS], dtype=np.int32)).cuda()
@@ -1469,8 +1480,7 @@ class WMF(RecModel):
                 mean[:, t0: t0 + tc], var[:, t0: t0 + tc] = self._scan_batches(
                     np.arange(B, dtype=np.int64), [(mat.indptr, mat.indices)], lambda rows: lib.wmf_posterior_score_workspace_bytes(rows, f, tc),
                     [mean_d, var_d], lambda b0, nb, ids, csrs, *ws: lib.wmf_posterior_score_rows(
-                        _ptr(items_t), n_items, f, ld, int(self.bias is True), _ptr(W_white), *csrs[0], _ptr(vals), nb, _ptr(tg_d[b0:]), tc,
-                        _ptr(mean_d[b0:]), _ptr(var_d[b0:]), _ptr(fail), *ws))
+                        *head, *csrs[0], _ptr(vals), nb, _ptr(tg_d[b0:]), tc, _ptr(mean_d[b0:]), _ptr(var_d[b0:]), _ptr(fail), *ws))
         return mean, var
 
     def recommend_ucb_for(self, count_rows, topn=10, pool=None, c=1.0, exclude_history=True, return_scores=False, return_std=False,
@@ -1502,7 +1512,7 @@ class WMF(RecModel):
         by key.  Returns the host (items, scores, std)."""
         pool, c, _ = ucb
         lib = _lib.load()
-        W_white = self._device_whitening()[4]
+        head = self._row_system_head()[0]
         n_items = self.items.shape[0]
         need_scan = lambda rows: int(lib.wmf_recommend_wide_workspace_bytes(rows, pool, 0))   # noqa: E731
         need = lambda rows: max(need_scan(rows), int(lib.wmf_posterior_score_workspace_bytes(rows, f, pool)))   # noqa: E731
@@ -1520,8 +1530,7 @@ class WMF(RecModel):
             rc = scan(b0, nb, ids, csrs, *ws)
             if rc != _lib.WMF_OK:
                 return rc
-            rc = lib.wmf_posterior_score_rows(_ptr(items_t), n_items, f, ld, bias, _ptr(W_white), *csrs[1], _ptr(vals), nb, _ptr(pool_i), pool,
-                                              None, _ptr(pool_v), _ptr(fail), *ws)
+            rc = lib.wmf_posterior_score_rows(*head, *csrs[1], _ptr(vals), nb, _ptr(pool_i), pool, None, _ptr(pool_v), _ptr(fail), *ws)
             if rc != _lib.WMF_OK:
                 return rc
             ids_sorted, by_id = torch.sort(pool_i[:nb], dim=1, stable=True)
@@ -1563,7 +1572,7 @@ class WMF(RecModel):
             u = np.arange(B, dtype=np.int64)
             if ucb is not None:
                 got_items, got_scores, got_std = self._ucb_scan(X_d, items_t, f, ld, u, topn, seen, filt, ucb, mat,
-                                                                self._device_confidences(mat, alpha, beta, mode))
+                                                                self._device_confidences(mat.data, alpha, beta, mode))
             else:
                 got_items, got_scores = self._recommend_scan(X_d, items_t, f, ld, u, topn, seen, want_scores, filt,
                                                              limit == CANDIDATES_MAX if wide is None else wide, mmr, sample)
@@ -1595,11 +1604,11 @@ class WMF(RecModel):
         return mat, 0 if pre_process_count == 'log' else 1
 
     @staticmethod
-    def _device_confidences(mat, alpha, beta, mode):
-        """The stored values of the CSR ``mat`` on the device, transformed as ``train`` transforms them (one spare element: never
+    def _device_confidences(counts, alpha, beta, mode):
+        """The stored values ``counts`` of a CSR on the device, transformed as ``train`` transforms them (one spare element: never
         empty)."""
-        vals = torch.from_numpy(np.append(np.asarray(mat.data, dtype=np.float32), np.float32(0))).cuda()
-        _lib.check(_lib.load().wmf_confidence_transform(_ptr(vals), len(mat.data), float(alpha), float(beta), mode, _stream()))
+        vals = torch.from_numpy(np.append(np.asarray(counts, dtype=np.float32), np.float32(0))).cuda()
+        _lib.check(_lib.load().wmf_confidence_transform(_ptr(vals), len(counts), float(alpha), float(beta), mode, _stream()))
         return vals
 
     def _fold_in_device(self, mat, alpha, beta, mode, draw=None):
@@ -1607,12 +1616,11 @@ class WMF(RecModel):
         block [B, ld] on the device in the library's layout, items_t, f, ld).  ``draw``: a _Draw, then wmf_posterior_draw_rows
         instead -- the block is [B * draw.draws, ld], the draws of a row next to each other, the streams' window moving with the
         rows'."""
-        users_t, items_t, f, ld, W_white = self._device_whitening()
+        head, items_t, f, ld = self._row_system_head()
         lib = _lib.load()
         B = mat.shape[0]
-        vals = self._device_confidences(mat, alpha, beta, mode)
+        vals = self._device_confidences(mat.data, alpha, beta, mode)
         fail = torch.zeros(1, dtype=torch.int32, device="cuda")
-        head = (_ptr(items_t), items_t.shape[0], f, ld, int(self.bias is True), _ptr(W_white))
         if draw is None:
             X_d = torch.empty(B, ld, dtype=torch.float32, device="cuda")
             need = lambda rows: lib.wmf_foldin_workspace_bytes(rows, f)   # noqa: E731

@@ -95,10 +95,9 @@ def _whiten32(R, W):
     return q
 
 
-def restated32(Y, bias, W32, indptr, indices, values, targets):
-    """The kernel's algorithm in float32, operation by operation and in the kernel's orders (csrc/wmf_explain.hip): sums over
-    the 16 lanes of a group as strided partial sums and a butterfly, fused multiply-adds where the kernel fuses.  W32 float32
-    [f, >= f] (the W_white the device is handed).  A row whose pivot is not positive and finite gives NaN."""
+# ---- the row system of csrc/wmf_rowsystem.h in float32: what restated32 here, tests/foldin_ref.py and tests/posterior_ref.py share
+def _prepared32(Y, bias, W32):
+    """(y~, beta, W_white) in float32 as the kernels read them: column 0 as 1 with a bias, W_white's upper triangle."""
     f32 = np.float32
     f = Y.shape[1]
     Yt = np.array(Y, dtype=f32)
@@ -106,7 +105,73 @@ def restated32(Y, bias, W32, indptr, indices, values, targets):
     if bias:
         beta = Yt[:, 0].copy()
         Yt[:, 0] = 1.0
-    W = np.triu(np.asarray(W32, dtype=f32)[:, :f])
+    return Yt, beta, np.triu(np.asarray(W32, dtype=f32)[:, :f])
+
+
+def _factor32(Yt, beta, W, j, vals, rhs=True):
+    """rs_factor_row: (A, dinv, good, w) with L in the lower triangle of A[:f, :f] (the upper one is not the kernel's) and, with
+    ``rhs``, c = L^-1 b in A[f, :f]; w the effective weights.  ``good`` is False where a pivot is not positive and finite."""
+    f32 = np.float32
+    f = Yt.shape[1]
+    w = np.asarray(vals, dtype=f32) - beta[j]
+    Q = _whiten32(Yt[j], W)
+    A = np.zeros((f + rhs, f + rhs), dtype=f32)
+    A[:f, :f] = np.eye(f, dtype=f32)
+    for e in range(len(j)):
+        A[:f, :f] = _fma((w[e] * Q[e])[:, None], Q[e][None, :], A[:f, :f])
+        if rhs:
+            A[f, :f] = _fma(w[e] + f32(1), Q[e], A[f, :f])
+    dinv = np.zeros(f, dtype=f32)
+    for k in range(f):
+        p = A[k, k]
+        if not (p > 0 and np.isfinite(p)):
+            return A, dinv, False, w
+        r = f32(1) / np.sqrt(p)
+        dinv[k] = r
+        col = A[k + 1:, k] * r
+        A[k + 1:, k] = col
+        A[k + 1:, k + 1:f] = _fma(-col[:, None], col[None, :f - k - 1], A[k + 1:, k + 1:f])
+    return A, dinv, True, w
+
+
+def _forward16(A, dinv, x):
+    """rs_forward16: L z = q in place for the slots x [slots, f], a 16-lane group per slot."""
+    for i in range(len(dinv)):
+        s = np.zeros((len(x), 16), dtype=np.float32)
+        for k0 in range(0, i, 16):
+            cols = np.arange(k0, min(k0 + 16, i))
+            s[:, :len(cols)] = _fma(A[i, cols][None, :], x[:, cols], s[:, :len(cols)])
+        x[:, i] = (x[:, i] - _sum16(s)) * dinv[i]
+
+
+def _backward(A, dinv, x):
+    """rs_backward16 / rs_backward_wg (the same operations on every element): L^T g = x in place for x [slots, f]."""
+    for k in range(len(dinv) - 1, -1, -1):
+        zk = x[:, k] * dinv[k]
+        x[:, :k] = _fma(-A[k, :k][None, :], zk[:, None], x[:, :k])
+        x[:, k] = zk
+
+
+def _unwhiten16(W, x):
+    """rs_unwhiten: W g over b >= a for x [slots, f], lane g of a group over the columns a + g, a + g + 16, ..."""
+    f = x.shape[1]
+    t = np.zeros_like(x)
+    for a in range(f):
+        s = np.zeros((len(x), 16), dtype=np.float32)
+        for b0 in range(a, f, 16):
+            cols = np.arange(b0, min(b0 + 16, f))
+            s[:, :len(cols)] = _fma(W[a, cols][None, :], x[:, cols], s[:, :len(cols)])
+        t[:, a] = _sum16(s)
+    return t
+
+
+def restated32(Y, bias, W32, indptr, indices, values, targets):
+    """The kernel's algorithm in float32, operation by operation and in the kernel's orders (csrc/wmf_explain.hip): sums over
+    the 16 lanes of a group as strided partial sums and a butterfly, fused multiply-adds where the kernel fuses.  W32 float32
+    [f, >= f] (the W_white the device is handed).  A row whose pivot is not positive and finite gives NaN."""
+    f32 = np.float32
+    f = Y.shape[1]
+    Yt, beta, W = _prepared32(Y, bias, W32)
     n, T = targets.shape
     contrib = np.zeros((int(indptr[-1]), T), dtype=f32)
     total = np.zeros((n, T), dtype=f32)
@@ -118,46 +183,16 @@ def restated32(Y, bias, W32, indptr, indices, values, targets):
         if hi == lo:
             total[u, ok] = beta[tg[ok]]
             continue
-        w = np.asarray(values[lo:hi], dtype=f32) - beta[j]
-        Q = _whiten32(Yt[j], W)
-        E = np.eye(f, dtype=f32)                          # (the lower triangle is the kernel's)
-        for e in range(hi - lo):
-            E = _fma((w[e] * Q[e])[:, None], Q[e][None, :], E)
-        dinv = np.zeros(f, dtype=f32)
-        good = True
-        for k in range(f):
-            p = E[k, k]
-            if not (p > 0 and np.isfinite(p)):
-                good = False
-                break
-            r = f32(1) / np.sqrt(p)
-            dinv[k] = r
-            col = E[k + 1:, k] * r
-            E[k + 1:, k] = col
-            E[k + 1:, k + 1:] = _fma(-col[:, None], col[None, :], E[k + 1:, k + 1:])
+        E, dinv, good, w = _factor32(Yt, beta, W, j, values[lo:hi], rhs=False)
         if not good:
             contrib[lo:hi][:, ok] = np.nan
             total[u, ok] = np.nan
             continue
         slots = np.nonzero(ok)[0]
         x = _whiten32(Yt[tg[ok]], W)                      # [slots, f]
-        for i in range(f):
-            s = np.zeros((len(slots), 16), dtype=f32)
-            for k0 in range(0, i, 16):
-                cols = np.arange(k0, min(k0 + 16, i))
-                s[:, :len(cols)] = _fma(E[i, cols][None, :], x[:, cols], s[:, :len(cols)])
-            x[:, i] = (x[:, i] - _sum16(s)) * dinv[i]
-        for k in range(f - 1, -1, -1):
-            zk = x[:, k] * dinv[k]
-            x[:, :k] = _fma(-E[k, :k][None, :], zk[:, None], x[:, :k])
-            x[:, k] = zk
-        t = np.zeros_like(x)
-        for a in range(f):
-            s = np.zeros((len(slots), 16), dtype=f32)
-            for b0 in range(a, f, 16):
-                cols = np.arange(b0, min(b0 + 16, f))
-                s[:, :len(cols)] = _fma(W[a, cols][None, :], x[:, cols], s[:, :len(cols)])
-            t[:, a] = _sum16(s)
+        _forward16(E, dinv, x)
+        _backward(E, dinv, x)
+        t = _unwhiten16(W, x)
         s = np.zeros((hi - lo, len(slots), 16), dtype=f32)
         for a0 in range(0, f, 16):
             cols = np.arange(a0, min(a0 + 16, f))
@@ -276,10 +311,8 @@ def case_names():
     return names + ["long_row", "grid_cap"]
 
 
-@functools.lru_cache(maxsize=None)
-def case(name):
-    """The case of that name, with its float64 reference, the restatement's pair errors and the gates: built once, shared, never
-    written (the arrays are read-only)."""
+def inputs(name):
+    """The host arrays of the case of that name (make_case), without references or gates."""
     kind = name.split("_")[0]
     seed = sum(ord(ch) * (k + 1) for k, ch in enumerate(name))
     if kind == "width":
@@ -296,6 +329,14 @@ def case(name):
     else:
         f, b = (int(part[1:]) for part in name.split("_")[1:])
         c = make_case(name, f, 0, b, kind, [0, 1, 5, 12, 40, f + 1], 4, seed)
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    """The case of that name, with its float64 reference, the restatement's pair errors and the gates: built once, shared, never
+    written (the arrays are read-only)."""
+    c = inputs(name)
     Yf = c["Y"][:, :c["f"]]
     c["ref"], c["ref_total"] = ref64(Yf, c["bias"], c["lam"], c["indptr"], c["indices"], c["values"], c["targets"])
     r32, _ = restated32(Yf, c["bias"], c["W32"], c["indptr"], c["indices"], c["values"], c["targets"])

@@ -18,8 +18,8 @@ from fractions import Fraction
 import numpy as np
 
 from explain_ref import (CHUNK, EDGE_CASES, FAMILIES, FAMILY_WIDTHS, GATE_FLOOR, GATE_MARGIN, GRID_CAP, LD_EXTRA, TINY,  # noqa: F401
-                         WIDTH_CASES, WIDTHS, _fma, _sum16, _whiten32, ld_for, make_case, orthogonal_case, padded, standard_degrees,
-                         tilde, ulp_error, whitening)
+                         WIDTH_CASES, WIDTHS, _backward, _factor32, _prepared32, _unwhiten16, ld_for, make_case, orthogonal_case, padded,
+                         standard_degrees, tilde, ulp_error, whitening)
 
 
 def ref64(Y, bias, lam, indptr, indices, values):
@@ -42,55 +42,21 @@ def ref64(Y, bias, lam, indptr, indices, values):
 def restated32(Y, bias, W32, indptr, indices, values):
     """The kernel's algorithm in float32, operation by operation and in the kernel's orders (csrc/wmf_foldin.hip).  W32 float32
     [f, >= f] (the W_white the device is handed).  float32 [n, f]; a row whose pivot is not positive and finite gives NaN."""
-    f32 = np.float32
     f = Y.shape[1]
-    Yt = np.array(Y, dtype=f32)
-    beta = np.zeros(len(Yt), dtype=f32)
-    if bias:
-        beta = Yt[:, 0].copy()
-        Yt[:, 0] = 1.0
-    W = np.triu(np.asarray(W32, dtype=f32)[:, :f])
+    Yt, beta, W = _prepared32(Y, bias, W32)
     n = len(indptr) - 1
-    X = np.zeros((n, f), dtype=f32)
+    X = np.zeros((n, f), dtype=np.float32)
     for u in range(n):
         lo, hi = int(indptr[u]), int(indptr[u + 1])
         if hi == lo:
             continue
-        j = indices[lo:hi]
-        w = np.asarray(values[lo:hi], dtype=f32) - beta[j]
-        Q = _whiten32(Yt[j], W)
-        A = np.zeros((f + 1, f + 1), dtype=f32)             # rows 0 .. f - 1: I + E_u (the lower triangle is the kernel's); row f: b
-        A[:f, :f] = np.eye(f, dtype=f32)
-        for e in range(hi - lo):
-            A[:f, :f] = _fma((w[e] * Q[e])[:, None], Q[e][None, :], A[:f, :f])
-            A[f, :f] = _fma(w[e] + f32(1), Q[e], A[f, :f])
-        dinv = np.zeros(f, dtype=f32)
-        good = True
-        for k in range(f):
-            p = A[k, k]
-            if not (p > 0 and np.isfinite(p)):
-                good = False
-                break
-            r = f32(1) / np.sqrt(p)
-            dinv[k] = r
-            col = A[k + 1:, k] * r
-            A[k + 1:, k] = col
-            A[k + 1:, k + 1:f] = _fma(-col[:, None], col[None, :f - k - 1], A[k + 1:, k + 1:f])
+        A, dinv, good, _ = _factor32(Yt, beta, W, indices[lo:hi], values[lo:hi])
         if not good:
             X[u] = np.nan
             continue
-        y = A[f, :f].copy()                                # L^-1 b
-        g = np.zeros(f, dtype=f32)
-        for k in range(f - 1, -1, -1):
-            zk = y[k] * dinv[k]
-            y[:k] = _fma(-A[k, :k], zk, y[:k])
-            g[k] = zk
-        for a in range(f):
-            s = np.zeros(16, dtype=f32)
-            for b0 in range(a, f, 16):
-                cols = np.arange(b0, min(b0 + 16, f))
-                s[:len(cols)] = _fma(W[a, cols], g[cols], s[:len(cols)])
-            X[u, a] = _sum16(s)
+        g = A[f:, :f].copy()                               # L^-1 b, the one right-hand side
+        _backward(A, dinv, g)
+        X[u] = _unwhiten16(W, g)[0]
     return X
 
 
@@ -114,10 +80,9 @@ def case_names():
     return names + ["long_row", "grid_cap"]
 
 
-@functools.lru_cache(maxsize=None)
-def case(name):
-    """The case of that name -- the inputs of tests/explain_ref.py::case, name for name -- with its float64 reference, the
-    restatement's row errors and the gates: built once, shared, never written (the arrays are read-only)."""
+def inputs(name):
+    """The host arrays of the case of that name -- the inputs of tests/explain_ref.py::case, name for name, without the targets --
+    without references or gates."""
     kind = name.split("_")[0]
     seed = sum(ord(ch) * (k + 1) for k, ch in enumerate(name))
     if kind == "width":
@@ -132,6 +97,14 @@ def case(name):
         f, b = (int(part[1:]) for part in name.split("_")[1:])
         c = make_case(name, f, 0, b, kind, [0, 1, 5, 12, 40, f + 1], 4, seed)
     del c["targets"]
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    """The case of that name with its float64 reference, the restatement's row errors and the gates: built once, shared, never
+    written (the arrays are read-only)."""
+    c = inputs(name)
     Yf = c["Y"][:, :c["f"]]
     c["ref"] = ref64(Yf, c["bias"], c["lam"], c["indptr"], c["indices"], c["values"])
     c["gate"], c["restated_err"] = gates(Yf, c["bias"], c["W32"], c["indptr"], c["indices"], c["values"], c["ref"])

@@ -8,7 +8,8 @@ the cases the CPU and GPU tests share.
 ``scores64``                      mean = y~_i . x_u + beta_i with x_u the fold-in's definition, var = y~_i^T A_u^-1 y~_i by a dense
                                   solve with A_u = G~ + lambda I + sum_e w_e y~_j y~_j^T.
 ``restated_draws32`` / ``restated_scores32``   the kernels' algorithm in NumPy float32, in the kernels' own summation orders with
-                                  emulated fused multiply-adds (csrc/wmf_posterior.hip).  Their error sets the gates.
+                                  emulated fused multiply-adds (csrc/wmf_posterior.hip; the row system: tests/explain_ref.py).
+                                  Their error sets the gates.
 The gates are those of tests/foldin_ref.py: ``GATE_MARGIN`` x the error of the restatement on that element + ``GATE_FLOOR`` (8 ulps).
 A draw's error is the fold-in's row error, max_a |x - ref| / max_a |ref|.  A variance is a sum of squares: its error is relative to
 itself.  A mean is the dot product z . c (+ beta) and a float32 dot product's error is relative to sum |z_i c_i| <= |z| |c|, not to
@@ -23,8 +24,8 @@ import numpy as np
 
 import foldin_ref
 import sample_ref
-from explain_ref import (GATE_FLOOR, GATE_MARGIN, TINY, _fma, _sum16, _whiten32, orthogonal_case, tilde, ulp_error,  # noqa: F401
-                         whitening)
+from explain_ref import (GATE_FLOOR, GATE_MARGIN, TINY, _backward, _factor32, _fma, _forward16, _prepared32, _sum16,  # noqa: F401
+                         _unwhiten16, _whiten32, orthogonal_case, tilde, ulp_error, whitening)
 
 MAX_DRAWS = 4096                   # WMF_POSTERIOR_MAX_DRAWS
 MAX_TARGETS = 4096                 # WMF_POSTERIOR_MAX_TARGETS
@@ -127,42 +128,6 @@ def scores64(Y, bias, lam, indptr, indices, values, targets):
 
 
 # ---- the kernels' arithmetic, float32 -----------------------------------------------------------------------------------------------
-def _factor32(Yt, beta, W, j, vals):
-    """Phases 1 and 2 of csrc/wmf_posterior.hip (those of wmf_foldin.hip): (A, dinv, good) with L in the lower triangle of A[:f, :f]
-    and c = L^-1 b in A[f, :f]."""
-    f32 = np.float32
-    f = Yt.shape[1]
-    w = np.asarray(vals, dtype=f32) - beta[j]
-    Q = _whiten32(Yt[j], W)
-    A = np.zeros((f + 1, f + 1), dtype=f32)
-    A[:f, :f] = np.eye(f, dtype=f32)
-    for e in range(len(j)):
-        A[:f, :f] = _fma((w[e] * Q[e])[:, None], Q[e][None, :], A[:f, :f])
-        A[f, :f] = _fma(w[e] + f32(1), Q[e], A[f, :f])
-    dinv = np.zeros(f, dtype=f32)
-    for k in range(f):
-        p = A[k, k]
-        if not (p > 0 and np.isfinite(p)):
-            return A, dinv, False
-        r = f32(1) / np.sqrt(p)
-        dinv[k] = r
-        col = A[k + 1:, k] * r
-        A[k + 1:, k] = col
-        A[k + 1:, k + 1:f] = _fma(-col[:, None], col[None, :f - k - 1], A[k + 1:, k + 1:f])
-    return A, dinv, True
-
-
-def _prepared32(Y, bias, W32):
-    f32 = np.float32
-    f = Y.shape[1]
-    Yt = np.array(Y, dtype=f32)
-    beta = np.zeros(len(Yt), dtype=f32)
-    if bias:
-        beta = Yt[:, 0].copy()
-        Yt[:, 0] = 1.0
-    return Yt, beta, np.triu(np.asarray(W32, dtype=f32)[:, :f])
-
-
 def _lanes16(terms_a, terms_b, width):
     """sum16 over lanes g of the fused sums over i = g, g + 16, .. of a[.., i] b[.., i]: the kernels' dot product over `width`
     components."""
@@ -187,7 +152,7 @@ def restated_draws32(Y, bias, W32, indptr, indices, values, xi32, sigma):
             continue
         x = np.zeros((D, f), dtype=f32)
         if not empty:
-            A, dinv, good = _factor32(Yt, beta, W, indices[lo:hi], values[lo:hi])
+            A, dinv, good, _ = _factor32(Yt, beta, W, indices[lo:hi], values[lo:hi])
             if not good:
                 out[u] = np.nan
                 continue
@@ -195,16 +160,8 @@ def restated_draws32(Y, bias, W32, indptr, indices, values, xi32, sigma):
         if sigma != 0:
             x = _fma(sigma, xi32[u], x)
         if not empty:
-            for k in range(f - 1, -1, -1):
-                zk = x[:, k] * dinv[k]
-                x[:, :k] = _fma(-A[k, :k][None, :], zk[:, None], x[:, :k])
-                x[:, k] = zk
-        for a in range(f):
-            s = np.zeros((D, 16), dtype=f32)
-            for b0 in range(a, f, 16):
-                cols = np.arange(b0, min(b0 + 16, f))
-                s[:, :len(cols)] = _fma(W[a, cols][None, :], x[:, cols], s[:, :len(cols)])
-            out[u, :, a] = _sum16(s)
+            _backward(A, dinv, x)
+        out[u] = _unwhiten16(W, x)
     return out
 
 
@@ -221,16 +178,11 @@ def restated_scores32(Y, bias, W32, indptr, indices, values, targets):
         tg = targets[u][ok]
         x = _whiten32(Yt[tg], W)
         if hi > lo:
-            A, dinv, good = _factor32(Yt, beta, W, indices[lo:hi], values[lo:hi])
+            A, dinv, good, _ = _factor32(Yt, beta, W, indices[lo:hi], values[lo:hi])
             if not good:
                 mean[u, ok] = var[u, ok] = np.nan
                 continue
-            for i in range(f):
-                s = np.zeros((len(tg), 16), dtype=f32)
-                for k0 in range(0, i, 16):
-                    cols = np.arange(k0, min(k0 + 16, i))
-                    s[:, :len(cols)] = _fma(A[i, cols][None, :], x[:, cols], s[:, :len(cols)])
-                x[:, i] = (x[:, i] - _sum16(s)) * dinv[i]
+            _forward16(A, dinv, x)
             sm = _lanes16(x, np.broadcast_to(A[f, :f], x.shape), f)
         else:
             sm = np.zeros(len(tg), dtype=f32)
